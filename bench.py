@@ -33,6 +33,10 @@ Extra objects on that line:
                 aborts (non-zero exit, rank named) if it does not; per-rank peak device memory and the attention workspace size.
 A rank that fails (process-group init, an RCCL error, a kernel error) prints `[bench] rank R: ...` and exits non-zero; the process
 group carries a timeout, so the other ranks do not wait on a barrier for ever.
+
+--dump-outputs DIR writes what the last timed step computed (rank 0's model outputs and the parameter gradients; large tensors as
+fixed, seeded samples) as DIR/<name>.npy, at most 64 MB.  Weights and batch are seeded, so the same arguments give the same inputs
+on every run, and two builds can be compared output for output.
 """
 from __future__ import annotations
 
@@ -108,6 +112,61 @@ def make_batch(config, w, rank: int, device):
         pick = (torch.rand(w["B"], w["S"], generator=g) < 0.15).to(device)
         batch["labels"] = torch.where(pick & (batch["attention_mask"] != 0), batch["input_ids"], torch.full_like(batch["input_ids"], -100))
     return batch
+
+
+DUMP_BUDGET_BYTES = 64 << 20  # --dump-outputs writes at most this much in all
+DUMP_SAMPLE = 1 << 20  # elements kept of an output tensor larger than this: a fixed, seeded sample
+DUMP_GRAD_SAMPLE = 1 << 22  # elements kept of the parameter gradients, all of them concatenated in named_parameters() order
+DUMP_SEED = 20240901
+
+
+def _dump_sample(t: torch.Tensor, n: int) -> torch.Tensor:
+    """t as it is when it has at most n elements, else n of its flattened elements at positions drawn (sorted, with repeats) from a
+    generator seeded with DUMP_SEED: the positions depend on t's size only, so two builds dump the same elements."""
+    if t.numel() <= n:
+        return t
+    g = torch.Generator().manual_seed(DUMP_SEED)
+    pos = torch.randint(t.numel(), (n,), generator=g).sort().values
+    return t.reshape(-1)[pos.to(t.device)]
+
+
+def _output_tensors(prefix: str, v, acc: dict) -> dict:
+    """name -> tensor for every tensor in a (nested) model output; nested fields are joined with dots."""
+    if torch.is_tensor(v):
+        acc[prefix] = v
+    elif isinstance(v, dict):  # ModelOutput (holds its non-None fields only)
+        for k, x in v.items():
+            _output_tensors(f"{prefix}.{k}" if prefix else k, x, acc)
+    elif isinstance(v, (tuple, list)):
+        for i, x in enumerate(v):
+            _output_tensors(f"{prefix}.{i}", x, acc)
+    return acc
+
+
+def dump_outputs(out_dir: str, out, model) -> dict:
+    """What one training step hands its caller: every tensor of the model output (loss, logits, embeddings, the towers' outputs) and
+    the parameter gradients, as <out_dir>/<name>.npy in float64 (float64 and integer tensors) or float32 (everything else).
+    Tensors larger than DUMP_SAMPLE elements and the gradients are written as fixed, seeded samples (_dump_sample): `grad_sample`
+    over all gradients concatenated in named_parameters() order, `grad_norm` the float64 L2 norm of each gradient in that order.
+    -> name -> (shape, dtype) of what was written."""
+    import numpy as np
+
+    arrays = {}
+    for name, t in _output_tensors("", out, {}).items():
+        t = _dump_sample(t.detach(), DUMP_SAMPLE)
+        arrays[name] = t.double() if (t.dtype == torch.float64 or not t.dtype.is_floating_point) else t.float()
+    grads = [p.grad.detach() for _, p in model.named_parameters() if p.grad is not None]
+    if grads:
+        arrays["grad_sample"] = _dump_sample(torch.cat([g.reshape(-1).float() for g in grads]), DUMP_GRAD_SAMPLE)
+        arrays["grad_norm"] = torch.stack([g.double().norm() for g in grads])
+    arrays = {k: v.cpu().numpy() for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_BUDGET_BYTES:
+        raise RuntimeError(f"--dump-outputs: {total} bytes exceed the budget of {DUMP_BUDGET_BYTES}")
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{k}.npy"), a)
+    return {k: (tuple(a.shape), str(a.dtype)) for k, a in arrays.items()}
 
 
 def pmc_value(kind: str, workload: str, tag: str, field: str = ""):
@@ -371,7 +430,12 @@ def main():
                          "the judged run keeps to the legs that only reuse the judged region's own collectives")
     ap.add_argument("--grad-compress", default="none", choices=["none", "bf16"],
                     help="N > 1: DDP communication hook (bf16 halves the 545 MB fp32 gradient all-reduce; off in the judged run)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last of them computed (model outputs and parameter gradients, rank 0's) "
+                         "as DIR/<name>.npy, float32 / float64, at most 64 MB (see dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     import torch.distributed as dist
 
@@ -437,11 +501,13 @@ def main():
     if args.unpad:
         model.unpad_inputs = True
 
-    def step():
+    def step(keep=None):
         for p in model.parameters():
             p.grad = None
         out = step_model(**batch)
         out.loss.backward()
+        if keep is not None:
+            keep["out"] = out
         return out.loss
 
     step.batch = batch  # (scaling_diagnosis runs the same batch through a second DDP wrapper)
@@ -519,9 +585,10 @@ def main():
     fence()
     if profile:
         _lib.profile_begin(only=dom_tag, every=PROFILE_EVERY)
+    kept = {}  # --dump-outputs: the last timed step's output (held only from that step on)
     t0 = time.perf_counter()
-    for _ in range(args.steps):
-        loss = step()
+    for i in range(args.steps):
+        loss = step(kept if args.dump_outputs and i == args.steps - 1 else None)
     fence()
     elapsed = time.perf_counter() - t0
     elapsed_local = elapsed  # this rank's own clock over the judged region (the reported time is the max over ranks)
@@ -530,6 +597,10 @@ def main():
         t = torch.tensor([elapsed], device=device, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if kept and rank == 0:  # (before anything else runs a step: the gradients are still the last timed step's)
+        written = dump_outputs(args.dump_outputs, kept["out"], model)
+        print(f"[bench] --dump-outputs: {len(written)} arrays in {args.dump_outputs}", file=sys.stderr, flush=True)
+    kept.clear()
 
     ms_per_step = elapsed / args.steps * 1e3
     pairs_per_s = world * w["B"] * args.steps / elapsed

@@ -5,10 +5,10 @@ leg may import this module; the product (`cm3p_amd/`) never does and has no CPU 
 
 Parity status: PINNED.  `tests/test_oracle_golden.py` checks every function here against fixtures in
 `tests/golden/` that were produced by running the reference itself (`tests/golden/make_golden.py`:
-reference wrapper imported unmodified from /root/reference + installed transformers 5.15.0, CPU, fp32,
+reference wrapper imported unmodified from a reference checkout + installed transformers 5.15.0, CPU, fp32,
 attn_implementation="sdpa").
 
-Conventions: `ref:` = /root/reference/, `TF:` = the installed third-party transformers 5.15.0 that
+Conventions: `ref:` = the reference checkout (OliBomby/CM3P), `TF:` = the installed third-party transformers 5.15.0 that
 carries the encoder arithmetic (pinned 4.55.0 by ref:Dockerfile:4; see SURVEY.md §8c for the skew).
 A model is a flat `dict[str, Tensor]` using the reference's state-dict keys plus a plain config dict;
 no `transformers` import is needed to run the oracle.

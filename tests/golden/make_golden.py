@@ -1,11 +1,11 @@
 #!/usr/bin/env python3
 """Generate golden fixtures by running the REFERENCE itself (CPU, fp32, attn_implementation="sdpa").
 
-Run in the build container only (needs /root/reference, which does not exist on the GPU box):
+Needs a checkout of the reference, named by CM3P_REFERENCE (not needed by the tests, which read the stored fixtures):
 
-    python tests/golden/make_golden.py            # writes tests/golden/*.safetensors
+    CM3P_REFERENCE=/path/to/OliBomby-CM3P python tests/golden/make_golden.py      # writes tests/golden/*.safetensors
 
-The reference package is imported from /root/reference unmodified.  It targets transformers 4.55; the
+The reference package is imported from that checkout unmodified.  It targets transformers 4.55; the
 installed transformers is 5.15, whose ModernBertModel reads four derived attributes the reference's
 config classes do not define.  `_shim_config` adds exactly the derivation the installed
 ModernBertConfig performs; no reference file is touched or copied.
@@ -26,14 +26,15 @@ from safetensors.torch import save_file
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
-sys.path.insert(0, "/root/reference")
+REFERENCE = os.path.abspath(os.environ.get("CM3P_REFERENCE") or sys.exit("set CM3P_REFERENCE to a checkout of the reference"))
+sys.path.insert(0, REFERENCE)
 
 from cases import CASES, make_inputs  # noqa: E402
 
 import cm3p  # noqa: E402  (the reference package)
 from cm3p import CM3PConfig, CM3PModel  # noqa: E402
 
-assert cm3p.__file__.startswith("/root/reference/"), cm3p.__file__
+assert cm3p.__file__.startswith(REFERENCE + os.sep), cm3p.__file__
 
 GRAD_KEYS = [
     "logit_scale",

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Generate the Muon golden fixture by running the REFERENCE's own optimizer class on the CPU.
 
-Build container only (needs /root/reference):   python tests/golden/make_golden_muon.py
+Needs a checkout of the reference:   CM3P_REFERENCE=/path/to/OliBomby-CM3P python tests/golden/make_golden_muon.py
 Writes tests/golden/muon_steps.safetensors: for each variant, the parameters after every step and the final optimizer state.
 The parameter split is the one ref:train.py:331-340 performs.
 """
@@ -15,13 +15,14 @@ from safetensors.torch import save_file
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
-sys.path.insert(0, "/root/reference")
+REFERENCE = os.path.abspath(os.environ.get("CM3P_REFERENCE") or sys.exit("set CM3P_REFERENCE to a checkout of the reference"))
+sys.path.insert(0, REFERENCE)
 
 from muon_cases import N_STEPS, VARIANTS, gradients, initial_params  # noqa: E402
 
 import utils.muon_utils as ref_muon  # noqa: E402  (the reference module)
 
-assert ref_muon.__file__.startswith("/root/reference/"), ref_muon.__file__
+assert ref_muon.__file__.startswith(REFERENCE + os.sep), ref_muon.__file__
 
 
 def main():

@@ -2,7 +2,8 @@
 """Golden fixtures for the stand-alone model classes (CM3PBeatmapModelWithProjection, CM3PMetadataModelWithProjection,
 CM3PForMaskedLM), produced by running the REFERENCE classes on the CPU (fp32, sdpa) with the d64 weights.
 
-Build container only:   python tests/golden/make_golden_variants.py   -> tests/golden/variants_d64.safetensors
+Needs a checkout of the reference:   CM3P_REFERENCE=/path/to/OliBomby-CM3P python tests/golden/make_golden_variants.py
+    -> tests/golden/variants_d64.safetensors
 """
 from __future__ import annotations
 
@@ -14,7 +15,6 @@ from safetensors.torch import load_file, save_file
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
-sys.path.insert(0, "/root/reference")
 
 from cases import CASES, make_inputs  # noqa: E402
 from make_golden import _shim_config  # noqa: E402  (also imports the reference package and asserts where it came from)

@@ -34,6 +34,32 @@ def test_bench_prints_one_json_line_with_the_contract_keys():
     assert c["kind"] in ("port", "reference") and c["cores"] >= 1 and c["value"] > 0 and isinstance(c["sample"], str) and c["unit"] == "pairs/s"
 
 
+def test_bench_dumps_the_last_timed_step_the_same_on_every_run(tmp_path):
+    """--dump-outputs: what the last timed step computed, float32 / float64 .npy files within 64 MB; two runs with the same arguments
+    start from the same weights and batch and write the same arrays."""
+    import numpy as np
+
+    lines = {}
+    for run in ("a", "b"):
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "2",
+                            "--no-cpu-baseline", "--no-optimizer", "--dump-outputs", str(tmp_path / run)],
+                           capture_output=True, text=True, timeout=900, cwd=ROOT)
+        assert p.returncode == 0, p.stderr[-2000:]
+        lines[run] = json.loads([l for l in p.stdout.splitlines() if l.strip()][-1])
+    assert lines["a"]["steps"] == 3 and lines["a"]["ms_per_step"] > 0
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == sorted(os.listdir(tmp_path / "b"))
+    for n in ("loss.npy", "logits_per_metadata.npy", "beatmap_embeds.npy", "beatmap_model_output.last_hidden_state.npy", "grad_sample.npy",
+              "grad_norm.npy"):
+        assert n in names, names
+    assert sum(os.path.getsize(tmp_path / "a" / n) for n in names) <= 64 << 20
+    for n in names:
+        a, b = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+        assert a.dtype in (np.float32, np.float64) and np.isfinite(a).all(), n
+        np.testing.assert_array_equal(a, b, err_msg=n)
+    assert float(np.load(tmp_path / "a" / "loss.npy")) == lines["a"]["config"]["loss"]  # the loss the result line reports: the last step's
+
+
 def test_bench_two_ranks_share_the_card_over_gloo():
     """The N > 1 code path of bench.py (DDP wrapper, gathered negatives, barrier + max-over-ranks timing, rank 0 prints) rehearsed
     with two ranks on the one GPU of this box; the driver's runs use one rank per GPU over RCCL."""

@@ -74,8 +74,13 @@ def _worker(rank, world, port, b, out):
 def test_gathered_loss_and_grads_equal_single_process_reference(world, b):
     from oracle import cm3p_oracle as O
 
+    # A rank's first backward() initialises the HIP runtime even on CPU tensors (the autograd engine asks every device type for its
+    # device count), so on a machine with a GPU every rank holds it open.  Eight of them beside the test process is more than one
+    # shared GPU should carry for a CPU test: world 8 runs where no GPU is visible (the non-GPU suite), world 2 and 4 everywhere.
+    if world > 4 and torch.cuda.is_available():
+        pytest.skip("world 8 would hold the visible GPU open in 8 rank processes; covered by the run without a GPU")
     port = _free_port()
-    mgr = mp.Manager()
+    mgr = mp.get_context("spawn").Manager()  # (a forked manager would inherit this process's open GPU handle)
     out = mgr.dict()
     mp.spawn(_worker, args=(world, port, b, out), nprocs=world, join=True)
 

@@ -2,7 +2,7 @@
 """Embedding + LayerNorm backward at the C2 shape (131072 tokens, 3167 x 768 table): the atomic scatter-add against the id-ordered
 kernels (CM3P_EMBED_BWD=atomic | sorted), uniform ids and 40 % of the tokens on one id.  Development aid."""
 import os, sys, torch
-sys.path.insert(0, '/root/repo')
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from cm3p_amd import kernels as K, _lib
 T, V, H = 131072, 3167, 768
 g = torch.Generator().manual_seed(0)
