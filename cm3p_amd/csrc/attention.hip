@@ -18,8 +18,6 @@
 //            dV^T += dO^T P and dK^T += Q^T dS consume the accumulators directly as B operands.
 // LDS tiles use one swizzled image (128-byte rows) that is bank-conflict free for ds_read_b128 row fragments AND for
 // ds_read_b64_tr_b16 transposed reads, so a tile consumed both ways (K in dq; Q and dO in dk/dv) is stored once.
-#include <stdlib.h>
-
 #include "attn_common.h"
 
 #ifndef CM3P_BABL
@@ -734,16 +732,10 @@ __global__ __launch_bounds__(256) void attn_probs_kernel(const uint16_t* __restr
 // attention_fwd.hip: the global layers' forward as one software-pipelined stream per wave (r05; pre-scaled q only)
 int cm3p_launch_attn_fwd_global(const void* qkv, void* out, float* lse, const uint8_t* key_mask, int B, int S, int nh, const int* cu_seqlens,
                                 int64_t total, hipStream_t s);
-// CM3P_ATTN_FWD_IMPL=wave3 keeps the global layers on attn_fwd_kernel (three compiler-scheduled waves per SIMD): the A/B partner and
-// the independent implementation the pipelined kernel is cross-checked against in the tests
-static bool fwd_pipelined() {  // (read per call: the tests run both in one process)
-    const char* e = getenv("CM3P_ATTN_FWD_IMPL");
-    return !(e && e[0] == 'w');
-}
 
 // the routing rule, also exported (cm3p_attn_fwd_impl): (TileDma::rows: 32-bit row * pitch source offsets, attn_common.h)
 static bool fwd_takes_pipelined(int S, int nh, int window, int pre) {
-    return window < 0 && pre && fwd_pipelined() && (int64_t)S * 3 * nh * 128 < (int64_t(1) << 31);
+    return window < 0 && pre && (int64_t)S * 3 * nh * 128 < (int64_t(1) << 31);
 }
 
 static int launch_attn_fwd(const void* qkv, void* out, float* lse, const uint8_t* key_mask, int B, int S, int nh, int window,
@@ -765,24 +757,10 @@ static int launch_attn_fwd(const void* qkv, void* out, float* lse, const uint8_t
     return CM3P_OK;
 }
 
-// attention_bwd.hip: the global-layer (window < 0) backward kernels
-int cm3p_launch_attn_bwd_global(const void* qkv, const void* out, const void* dout, const float* lse, float* delta, void* dqkv,
-                                const uint8_t* key_mask, int B, int S, int nh, float scale, const float* cos_tab, const float* sin_tab,
-                                int64_t pos_batch_stride, const int* cu_seqlens, int64_t total, int stages, int pre, hipStream_t s);
-
-// Kernel experiments only: CM3P_ATTN_BAND_EVERYWHERE=1 routes global layers through the band kernels of this file as well.
-static bool band_kernels_everywhere() {
-    static const bool v = [] { const char* e = getenv("CM3P_ATTN_BAND_EVERYWHERE"); return e && e[0] == '1'; }();
-    return v;
-}
-
 // stages: CM3P_ATTN_BWD_DQ (dq and delta) | CM3P_ATTN_BWD_DKV (dk, dv; reads the delta the dq stage wrote)
 static int launch_attn_bwd(const void* qkv, const void* out, const void* dout, const float* lse, float* delta, void* dqkv,
                            const uint8_t* key_mask, int B, int S, int nh, int window, float scale, const float* cos_tab,
                            const float* sin_tab, int64_t pos_batch_stride, VarLen vl, int stages, int pre, hipStream_t s) {
-    if (window < 0 && !band_kernels_everywhere())
-        return cm3p_launch_attn_bwd_global(qkv, out, dout, lse, delta, dqkv, key_mask, B, S, nh, scale, cos_tab, sin_tab, pos_batch_stride,
-                                           vl.cu, vl.total, stages, pre, s);
     const dim3 grid(((S + 127) / 128) * nh * B);  // 1-D: decode_block() maps it XCD-aware
     if (stages & CM3P_ATTN_BWD_DQ) {
 #define CM3P_DQ_ARGS (const uint16_t*)qkv, (const uint16_t*)dout, (const uint16_t*)out, lse, delta, (uint16_t*)dqkv, key_mask, S, nh, window, scale, cos_tab, sin_tab, pos_batch_stride, vl

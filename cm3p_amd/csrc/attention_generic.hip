@@ -1,7 +1,7 @@
 // Attention for head sizes other than 64 (16 and 32; 64 is instantiated as a cross-check of the MFMA kernels).
 //
 // Every tower of the reference's default configuration has head_dim 64 (768 / 12, 256 / 4, 512 / 8:
-// ref:configs/model/default.yaml:16-19,88-91) and that is what attention.hip / attention_bwd*.hip are built for.  BASELINE.json's
+// ref:configs/model/default.yaml:16-19,88-91) and that is what attention.hip / attention_fwd.hip / attention_bwd_fused.hip are built for.  BASELINE.json's
 // configs[0], the reference's own tiny test configuration (hidden 64, 4 heads: head_dim 16), used to raise NotImplementedError on the
 // GPU.  These kernels make such configurations RUN with the same semantics - they are plain fp32 loops, one thread per query (or key)
 // row, no matrix cores - so that a user of the reference can point any of its configurations at the library; they are not on the

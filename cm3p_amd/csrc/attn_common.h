@@ -1,5 +1,5 @@
-// Device helpers shared by the attention kernels (attention.hip: forward and the sliding-window backward;
-// attention_bwd.hip: the global-layer backward).  See attention.hip's header comment for the MFMA formulation.
+// Device helpers shared by the attention kernels (attention.hip: forward and backward for any window; attention_fwd.hip and
+// attention_bwd_fused.hip: the global layers' forward and backward).  See attention.hip's header comment for the MFMA formulation.
 #pragma once
 #include <limits.h>
 
@@ -146,7 +146,7 @@ __device__ __forceinline__ void lstore64_R(char* tile, const TileRegs64& t, int 
 }
 
 
-// ---- hand-scheduled kernels (attention_bwd.hip, attention_fwd.hip) --------------------------------------------------------------
+// ---- hand-scheduled kernels (attention_fwd.hip, attention_bwd_fused.hip) -------------------------------------------------------
 // With the 512-entry register budget of one wave per SIMD hipcc selects the AGPR form of every MFMA it generates, and the VALU
 // cannot read AGPRs.  Products whose results the VALU consumes are therefore issued as inline-asm MFMAs with VGPR destinations;
 // their stationary B operands live in AGPRs ("a").  hipcc pads no hazards for an asm statement: a result is first read one
@@ -164,10 +164,6 @@ __device__ __forceinline__ void mfma_va(f32x16& d, const bf16x8& a, const bf16x8
 }
 __device__ __forceinline__ bf16x8 ld_frag(const char* p) { return *reinterpret_cast<const bf16x8*>(p); }
 __device__ __forceinline__ bf16x8 ld_fragT(const char* lo, const char* hi) { return cat_bf16x4(lds_read_tr16(lo), lds_read_tr16(hi)); }
-// D (VGPRs) = A (VGPRs) * B (AGPRs), from zero
-__device__ __forceinline__ void mfma_v0(f32x16& d, const bf16x8& a, const bf16x8& b) {
-    asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, 0" : "=&v"(d) : "v"(a), "a"(b));
-}
 
 
 // A 32 x 64 block held as two accumulator blocks (lane = row l31, half hh; register i of block blk = column

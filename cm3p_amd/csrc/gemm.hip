@@ -297,7 +297,6 @@ static inline int big_gemm(const void* A, const void* B, void* C, const float* R
 static inline int64_t tiles_of(int64_t M, int64_t N, int t) { return ((M + t - 1) / t) * ((N + t - 1) / t); }
 
 int cm3p_ablation_flags_attention();
-int cm3p_ablation_flags_attention_bwd();
 int cm3p_ablation_flags_attention_bwd_fused();
 int cm3p_ablation_flags_gemm256();
 int cm3p_ablation_flags_gemm8p();
@@ -313,7 +312,7 @@ int cm3p_audit_set_attention_bwd_fused(void*);
 extern "C" {
 
 int cm3p_build_ablation_flags(void) {
-    return (cm3p_ablation_flags_attention() != 0) | (cm3p_ablation_flags_attention_bwd() != 0) << 1 | (cm3p_ablation_flags_attention_bwd_fused() != 0) << 2 |
+    return (cm3p_ablation_flags_attention() != 0) | (cm3p_ablation_flags_attention_bwd_fused() != 0) << 2 |  // (bit 1: unused)
            (cm3p_ablation_flags_gemm256() != 0) << 3 | (cm3p_ablation_flags_gemm8p() != 0) << 4 | (CM3P_DMA_AUDIT != 0) << 5 |
            (cm3p_ablation_flags_attention_fwd() != 0) << 6;
 }

@@ -1,7 +1,7 @@
 """Compile-time checks of the generated ISA for the kernels whose CORRECTNESS depends on what hipcc emits (no GPU needed).
 
-Four files synchronise LDS-DMA rings with counted `s_waitcnt vmcnt(N)` and / or issue inline-asm MFMAs that hipcc pads no
-hazards for: attention_fwd.hip (r05), attention_bwd.hip, attention_bwd_fused.hip and gemm8p.hip.  A different hipcc, other flags or an innocent source edit
+Three files synchronise LDS-DMA rings with counted `s_waitcnt vmcnt(N)` and / or issue inline-asm MFMAs that hipcc pads no
+hazards for: attention_fwd.hip (r05), attention_bwd_fused.hip and gemm8p.hip.  A different hipcc, other flags or an innocent source edit
 can add a spill reload, a scratch access or an accumulator copy to their loops; the counted waits then cover the wrong loads and
 the results are silently wrong.  `build.py` runs these checks whenever it recompiles one of the files (a failed check fails the
 build) and tests/test_kernel_isa.py runs them on every test run.
@@ -91,21 +91,6 @@ def check_gemm8p(isa: str):
         _need(total == 14 + 16 * n, f"{sym}: {total} LDS-DMA instructions in the kernel, expected {14 + 16 * n}")
         _need(body.count("s_waitcnt vmcnt(0)") >= 1, f"{sym}: the final drain of the ring is missing")
         _need(re.search(r"s_nop 15\s*\n\s*s_nop 7", body), f"{sym}: the epilogue's wait states behind the asm MFMAs are missing")
-
-
-# ------------------------------------------------------------------------------------------------ attention_bwd.hip
-def check_attention_bwd(isa: str):
-    no_scratch(isa, "attention_bwd.hip")
-    for name, mfma_per_block in (("attn_bwd_dkv3_kernel", 64), ("attn_bwd_dq3_kernel", 48)):
-        for sym, body in kernel_bodies(isa, name).items():
-            blocks = [b for b in re.split(r"\n(?=\.LBB\d+_\d+:)", body) if b.count("v_mfma_f32_32x32x16_bf16") >= mfma_per_block]
-            _need(blocks, f"{sym}: main loop not found")
-            for b in blocks:
-                _need("v_accvgpr_write" not in b and "v_accvgpr_read" not in b, f"{sym}: accumulator copies in the main loop "
-                                                                                 "(an AGPR operand re-materialised in front of an asm MFMA is read stale)")
-                _need("scratch_" not in b, f"{sym}: scratch access in the main loop")
-                _need(re.search(r"v_mfma_f32_32x32x16_bf16 v\[\d+:\d+\], v\[\d+:\d+\], a\[\d+:\d+\]", b), f"{sym}: VGPR-result MFMA form missing")
-                _need(re.search(r"v_mfma_f32_32x32x16_bf16 a\[\d+:\d+\], v\[\d+:\d+\], v\[\d+:\d+\], a\[\d+:\d+\]", b), f"{sym}: AGPR-accumulating MFMA form missing")
 
 
 # ------------------------------------------------------------------------------------------------ attention_bwd_fused.hip
@@ -199,8 +184,7 @@ def check_attention_fwd(isa: str):
         _need(body.count("s_waitcnt vmcnt(0)") >= 2, f"{sym}: the prologue wait / the final drain of the ring is missing")
 
 
-CHECKS = {"gemm8p.hip": check_gemm8p, "attention_fwd.hip": check_attention_fwd, "attention_bwd.hip": check_attention_bwd,
-          "attention_bwd_fused.hip": check_attention_bwd_fused}
+CHECKS = {"gemm8p.hip": check_gemm8p, "attention_fwd.hip": check_attention_fwd, "attention_bwd_fused.hip": check_attention_bwd_fused}
 
 
 def check_file(src: str, flags: list[str]) -> None:

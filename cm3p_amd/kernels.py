@@ -300,8 +300,8 @@ def gemm8p_get_grid() -> int:
 
 def _attn_fwd_name(window: int, prescaled: bool, masked: bool, S: int, nh: int) -> str:
     """The forward kernel a call lands on, as rocprofv3 names it.  The routing is the library's (cm3p_attn_fwd_impl: global layers with
-    pre-scaled q run the pipelined kernel of csrc/attention_fwd.hip unless CM3P_ATTN_FWD_IMPL=wave3 or the sequence is too long for its
-    32-bit row offsets); this function only spells the answer (r05 advisor: it used to re-derive the rule)."""
+    pre-scaled q run the pipelined kernel of csrc/attention_fwd.hip unless the sequence is too long for its 32-bit row offsets);
+    this function only spells the answer (r05 advisor: it used to re-derive the rule)."""
     if query("cm3p_attn_fwd_impl", S, nh, window, int(prescaled)):
         return "attn_fwd_g_kernel<4, " + ("true>" if masked else "false>")
     return "attn_fwd_kernel<1, %s, " + ("true>" if window >= 0 else "false>")
@@ -356,7 +356,7 @@ ATTN_BWD_DQ, ATTN_BWD_DKV = 1, 2  # stages of cm3p_attn_bwd (include/cm3p_hip.h)
 
 def _attn_tag(fmt: str, window: int, prescaled: bool, varlen: bool = False) -> str:
     """Profiler tag = the kernel's name as rocprofv3 prints it (the template argument is the q_prescaled mode) + which layers it
-    served: "attn_bwd_dkv3_kernel<true> [global]".  bench.py matches the part before " [" against the rocprof / PMC rows."""
+    served: "attn_bwd_fused_kernel<true, false> [global]".  bench.py matches the part before " [" against the rocprof / PMC rows."""
     name = fmt % ("true" if prescaled else "false") if "%s" in fmt else fmt
     return f"{name} [{'global' if window < 0 else 'local'}{', varlen' if varlen else ''}]"
 
@@ -377,12 +377,6 @@ def release_workspaces() -> None:
     _fused_ws.clear()
     for c in _other_caches:
         c.clear()
-
-
-def attn_bwd_fused_enabled() -> bool:
-    """Global layers run the five-product kernel of csrc/attention_bwd_fused.hip unless CM3P_ATTN_BWD_FUSED=0 (then the
-    query-parallel + key-parallel pair of csrc/attention_bwd.hip; same results up to bf16 rounding of partial sums)."""
-    return os.environ.get("CM3P_ATTN_BWD_FUSED", "1") != "0"
 
 
 def _attn_bwd_fused(qkv, out, dout, lse, key_mask, cu, B, S, total, nh, scale, rope, per_batch, prescaled) -> Tensor:
@@ -419,18 +413,17 @@ def _attn_bwd_fused(qkv, out, dout, lse, key_mask, cu, B, S, total, nh, scale, r
 def attn_bwd(qkv: Tensor, out: Tensor, dout: Tensor, lse: Tensor, key_mask: Optional[Tensor], B: int, S: int, nh: int,
              window: int, scale: float, rope: Optional[tuple] = None, per_batch: bool = False, prescaled: bool = False) -> Tensor:
     """rope = (cos, sin): also applies the inverse rotary rotation to dq / dk (backward of the fused Wqkv+RoPE GEMM).
-    The two kernels are issued as two C calls so that each has its own profiler tag (one rocprof row per tag).  `work` is the
+    Global layers (window < 0) run the five-product kernel of csrc/attention_bwd_fused.hip; sliding-window layers the band kernels
+    of csrc/attention.hip, issued as two C calls so that each has its own profiler tag (one rocprof row per tag).  `work` is the
     algorithmic count of SURVEY.md section 8(d) (backward = 2 x forward = four matmuls: dQ is the dq kernel's, dP / dV / dK the
     dkv kernel's); the scores each kernel recomputes are not credited."""
-    if window < 0 and attn_bwd_fused_enabled():
+    if window < 0:
         return _attn_bwd_fused(qkv, out, dout, lse, key_mask, None, B, S, 0, nh, scale, rope, per_batch, prescaled)
     dqkv = torch.empty_like(qkv)
     delta = torch.empty_like(lse)
-    keys = S if window < 0 else min(S, 2 * window + 1)
+    keys = min(S, 2 * window + 1)
     cos, sin = rope if rope is not None else (None, None)
-    # global layers: the hand-scheduled kernels of csrc/attention_bwd.hip; sliding-window layers: the band kernels of attention.hip
-    names = ("attn_bwd_dq3_kernel", "attn_bwd_dkv3_kernel<%s>") if window < 0 else ("attn_bwd_dq_kernel<%s>", "attn_bwd_dkv_kernel<%s>")
-    for stage, name, products in ((ATTN_BWD_DQ, names[0], 1), (ATTN_BWD_DKV, names[1], 3)):
+    for stage, name, products in ((ATTN_BWD_DQ, "attn_bwd_dq_kernel<%s>", 1), (ATTN_BWD_DKV, "attn_bwd_dkv_kernel<%s>", 3)):
         call("cm3p_attn_bwd", ptr(qkv), ptr(out), ptr(dout), ptr(lse, torch.float32), ptr(delta), ptr(dqkv), ptr(key_mask, torch.uint8), B, S, nh,
              window, scale, ptr(cos, torch.float32), ptr(sin, torch.float32), S if per_batch else 0, stage, int(prescaled), stream(), tag=_attn_tag(name, window, prescaled),
              work=2.0 * products * B * nh * S * keys * 64)
@@ -450,13 +443,12 @@ def attn_fwd_varlen(qkv: Tensor, cu: Tensor, B: int, max_s: int, nh: int, window
 def attn_bwd_varlen(qkv: Tensor, out: Tensor, dout: Tensor, lse: Tensor, cu: Tensor, B: int, max_s: int, nh: int, window: int,
                     scale: float, rope: Optional[tuple] = None, prescaled: bool = False) -> Tensor:
     """rope = (cos, sin) per packed token [total, 32]: also applies the inverse rotation to dq / dk."""
-    if window < 0 and attn_bwd_fused_enabled():
+    if window < 0:
         return _attn_bwd_fused(qkv, out, dout, lse, None, cu, B, max_s, qkv.shape[0], nh, scale, rope, False, prescaled)
     dqkv = torch.empty_like(qkv)
     delta = torch.empty_like(lse)
     cos, sin = rope if rope is not None else (None, None)
-    names = ("attn_bwd_dq3_kernel", "attn_bwd_dkv3_kernel<%s>") if window < 0 else ("attn_bwd_dq_kernel<%s>", "attn_bwd_dkv_kernel<%s>")
-    for stage, name in ((ATTN_BWD_DQ, names[0]), (ATTN_BWD_DKV, names[1])):
+    for stage, name in ((ATTN_BWD_DQ, "attn_bwd_dq_kernel<%s>"), (ATTN_BWD_DKV, "attn_bwd_dkv_kernel<%s>")):
         call("cm3p_attn_bwd_varlen", ptr(qkv), ptr(out), ptr(dout), ptr(lse, torch.float32), ptr(delta), ptr(dqkv), ptr(cu, torch.int32), B, max_s,
              qkv.shape[0], nh, window, scale, ptr(cos, torch.float32), ptr(sin, torch.float32), stage, int(prescaled), stream(), tag=_attn_tag(name, window, prescaled, True))
     return dqkv

@@ -128,10 +128,11 @@ int cm3p_gemm_bf16(const void* A, const void* B, void* C, const float* R, int64_
 int cm3p_gemm8p_set_grid(int workgroups);
 int cm3p_gemm8p_get_grid(void);
 
-/* Host-only.  The hand-scheduled kernels carry compile-time TIMING probes (macros CM3P_ABL, CM3P_FABL, CM3P_BABL, CM3P_G256_ABL,
+/* Host-only.  The hand-scheduled kernels carry compile-time TIMING probes (macros CM3P_FABL, CM3P_BABL, CM3P_GABL, CM3P_G256_ABL,
  * CM3P_G8P_ABL: builds that skip barriers, loads or stores and whose results are wrong by construction; the _ablate.sh scripts under tools/ubench).
  * Returns a bit mask of the objects in THIS library that were built with any of them set: 0 for every library that may be used
- * for results (cm3p_amd/_lib.py refuses to load anything else; tests/test_cabi.py). */
+ * for results (cm3p_amd/_lib.py refuses to load anything else; tests/test_cabi.py).  Bit 1 is unused (it named the deleted two-kernel
+ * global backward); the other bits keep their meaning. */
 int cm3p_build_ablation_flags(void);
 
 /* Debug builds only (libcm3p_hip_audit.so, -DCM3P_DMA_AUDIT=1; bit 5 of cm3p_build_ablation_flags): every LDS-DMA staging helper of the
@@ -204,8 +205,7 @@ int cm3p_rope_apply(void* qkv, const float* cos_tab, const float* sin_tab, int B
 int cm3p_attn_fwd(const void* qkv, void* out, float* lse, const uint8_t* key_mask, int B, int S, int nh, int window,
                   float scale, int q_prescaled, void* stream);
 /* Host-only: which forward kernel cm3p_attn_fwd / cm3p_attn_fwd_varlen launches for this call - 1: the pipelined global kernel of
- * csrc/attention_fwd.hip (window < 0, pre-scaled q, row offsets within 32 bits, CM3P_ATTN_FWD_IMPL not "wave3"), 0: attn_fwd_kernel of
- * csrc/attention.hip.  The ONE place the routing is decided; callers that label launches (profiler tags) ask instead of re-deriving it. */
+ * csrc/attention_fwd.hip (window < 0, pre-scaled q, row offsets within 32 bits), 0: attn_fwd_kernel of csrc/attention.hip.  The ONE place the routing is decided; callers that label launches (profiler tags) ask instead of re-deriving it. */
 int cm3p_attn_fwd_impl(int S, int nh, int window, int q_prescaled);
 
 /* output_attentions: the attention probabilities [B, nh, S, S] fp32 of one layer from qkv and the lse cm3p_attn_fwd stored - what
@@ -222,7 +222,9 @@ int cm3p_attn_probs(const void* qkv, const float* lse, const uint8_t* key_mask, 
  * CM3P_ATTN_BWD_DKV (the dk and dv thirds; reads the delta a DQ stage wrote earlier on the same stream), or both (3).
  * Callers that time kernels one by one issue the stages as two calls; the results are identical.
  * dqkv's q third is the gradient w.r.t. the UN-scaled rotated q in both q_prescaled modes (the chain rule through q_scale is
- * applied inside), i.e. what the Wqkv GEMM's backward expects. */
+ * applied inside), i.e. what the Wqkv GEMM's backward expects.
+ * Every window, window < 0 included, runs the kernels of csrc/attention.hip; the global layers of the model take
+ * cm3p_attn_bwd_fused instead, which these kernels cross-check. */
 #define CM3P_ATTN_BWD_DQ 1
 #define CM3P_ATTN_BWD_DKV 2
 int cm3p_attn_bwd(const void* qkv, const void* out, const void* dout, const float* lse, float* delta, void* dqkv,

@@ -111,7 +111,7 @@ def test_fused_attention_backward_rejects_bad_arguments_without_a_gpu(lib_path):
 
 
 def test_shipped_library_carries_no_timing_ablations(lib_path, tmp_path):
-    """The hand-scheduled kernels have compile-time timing probes (CM3P_ABL / CM3P_FABL / CM3P_BABL / CM3P_G256_ABL / CM3P_G8P_ABL)
+    """The hand-scheduled kernels have compile-time timing probes (CM3P_FABL / CM3P_BABL / CM3P_GABL / CM3P_G256_ABL / CM3P_G8P_ABL)
     whose results are wrong by construction.  The in-tree library reports a zero mask, and the binding refuses a library that
     does not (checked on an object built with one probe set, linked with the shipped objects; compile only, no GPU)."""
     import subprocess

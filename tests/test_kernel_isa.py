@@ -1,5 +1,5 @@
 """Compile-time checks of the kernels whose correctness depends on the emitted ISA (no GPU needed): the counted-vmcnt LDS-DMA rings
-of gemm8p.hip and attention_bwd_fused.hip and the inline-asm MFMAs of attention_bwd.hip / attention_bwd_fused.hip.  The checks live in
+and the inline-asm MFMAs of gemm8p.hip, attention_fwd.hip and attention_bwd_fused.hip.  The checks live in
 cm3p_amd/isa_check.py because cm3p_amd/build.py runs the same ones on every rebuild of these objects (a failed check fails the
 build); here they run on every test run, plus a negative control that the checker really looks at the ring."""
 import os

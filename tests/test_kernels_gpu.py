@@ -486,14 +486,13 @@ def test_attention_global_nopad(K):
     _attn_case(K, 2, 256, 2, -1, None, 1)
 
 
-@pytest.mark.parametrize("impl", ["fused", "pair"])
+@pytest.mark.parametrize("impl", ["fused", "band"])
 @pytest.mark.parametrize("S,lens,prescaled", [(700, [700, 513, 64], True), (1536, None, True), (330, [330, 257, 1], False), (64, None, False)])
-def test_attention_global_backward_both_implementations(K, monkeypatch, impl, S, lens, prescaled):
-    """Global layers have two backward implementations behind one call: the five-product kernel (attention_bwd_fused.hip, the
-    default) and the query-parallel + key-parallel pair (attention_bwd.hip, CM3P_ATTN_BWD_FUSED=0).  Both are held to the same
-    tolerance against the fp32 reference, over several 256-key blocks, ragged padding and both q modes."""
-    monkeypatch.setenv("CM3P_ATTN_BWD_FUSED", "1" if impl == "fused" else "0")
-    _attn_case(K, 2 if lens is None else 3, S, 2, -1, lens, 21, prescaled=prescaled)
+def test_attention_global_backward_both_implementations(K, impl, S, lens, prescaled):
+    """The global mask has two backward implementations: the five-product kernel (attention_bwd_fused.hip, window = -1) and the
+    query-parallel + key-parallel band kernels (attention.hip) with a window that covers every key (window = S, the same mask).
+    Both are held to the same tolerance against the fp32 reference, over several 256-key blocks, ragged padding and both q modes."""
+    _attn_case(K, 2 if lens is None else 3, S, 2, -1 if impl == "fused" else S, lens, 21, prescaled=prescaled)
 
 
 @pytest.mark.parametrize("seed", list(range(12)))
@@ -534,18 +533,17 @@ def test_attention_global_arbitrary_key_masks(K, seed):
     _attn_case(K, B, S, nh, -1, m, 7100 + seed, prescaled=seed % 4 != 3)
 
 
-def test_attention_fused_backward_matches_pair_and_is_deterministic(K, monkeypatch):
+def test_attention_fused_backward_matches_band_kernels_and_is_deterministic(K):
+    """The fused backward (window = -1) against the band kernels of attention.hip with every key inside the window (window = S)."""
     B, S, nh = 3, 1100, 3
     g = torch.Generator().manual_seed(5)
     qkv = _bf(torch.randn(B, S, 3, nh, 64, generator=g)).to(DEV)
     do = _bf(torch.randn(B * S, nh * 64, generator=g)).to(DEV)
     km = (torch.arange(S)[None] < torch.tensor([1100, 777, 300])[:, None]).to(torch.uint8).to(DEV)
     out, lse = K.attn_fwd(qkv, km, B, S, nh, -1, 0.125)
-    monkeypatch.setenv("CM3P_ATTN_BWD_FUSED", "1")
     a = K.attn_bwd(qkv, out, do, lse, km, B, S, nh, -1, 0.125)
     a2 = K.attn_bwd(qkv, out, do, lse, km, B, S, nh, -1, 0.125)
-    monkeypatch.setenv("CM3P_ATTN_BWD_FUSED", "0")
-    b = K.attn_bwd(qkv, out, do, lse, km, B, S, nh, -1, 0.125)
+    b = K.attn_bwd(qkv, out, do, lse, km, B, S, nh, S, 0.125)
     assert torch.equal(a, a2)  # partial dq slabs are summed in a fixed order
     for i, (nm, tol) in enumerate((("dq", 6e-3), ("dk", 1e-4), ("dv", 1e-6))):  # dq: one extra bf16 rounding per 256-key partial
         x, y = a[:, :, i].float(), b[:, :, i].float()
@@ -555,11 +553,10 @@ def test_attention_fused_backward_matches_pair_and_is_deterministic(K, monkeypat
     assert a[:, :, 1:][dead].abs().max().item() == 0.0 and b[:, :, 1:][dead].abs().max().item() == 0.0
 
 
-def test_attention_fused_backward_masked_keys_with_unbounded_scores(K, monkeypatch):
+def test_attention_fused_backward_masked_keys_with_unbounded_scores(K):
     """Keys under the padding mask are not bounded by the row maximum (lse covers visible keys only): with large K rows there,
     exp2(s - lse) overflows.  The fused kernel clamps p to [0, 1] and stores such keys as zero rows of its K image, so they
     contribute exact zeros to dq and get dk = dv = 0."""
-    monkeypatch.setenv("CM3P_ATTN_BWD_FUSED", "1")
     B, S, nh = 2, 520, 2
     g = torch.Generator().manual_seed(6)
     qkv = torch.randn(B, S, 3, nh, 64, generator=g)
@@ -755,9 +752,10 @@ def test_audio_conv_frontend_matches_conv1d(K):
 
 # ------------------------------------------------------------------------------------------------- unpadded attention
 @pytest.mark.parametrize("S,lens,nh", [(1100, [1100, 1023, 65, 1], 2), (512, None, 3), (4096 + 77, [4096 + 77, 2049], 1), (200, [200, 1, 199], 2)])
-def test_pipelined_global_forward_agrees_with_the_three_wave_kernel(K, monkeypatch, S, lens, nh):
-    """Global layers with pre-scaled q have two forward implementations behind one call: the software-pipelined one-wave-per-SIMD kernel
-    (attention_fwd.hip, the default) and attn_fwd_kernel (attention.hip, CM3P_ATTN_FWD_IMPL=wave3).  Same mathematics, different order
+def test_pipelined_global_forward_agrees_with_the_three_wave_kernel(K, S, lens, nh):
+    """The global mask with pre-scaled q has two forward implementations: the software-pipelined one-wave-per-SIMD kernel
+    (attention_fwd.hip, window = -1) and attn_fwd_kernel (attention.hip, three waves per SIMD) with a window that covers every key
+    (window = S, the same mask: attn_fwd_kernel<1, true, true>).  Same mathematics, different order
     of the row sums and a different moment at which the lazily moved reference point moves: outputs agree to two bf16 roundings, lse to
     fp32 rounding, rows without a visible key are exact zeros / +inf in both, and the pipelined kernel is bit-reproducible."""
     g = torch.Generator().manual_seed(S + nh)
@@ -769,9 +767,7 @@ def test_pipelined_global_forward_agrees_with_the_three_wave_kernel(K, monkeypat
     if lens is not None:
         km = (torch.arange(S)[None] < torch.tensor(lens)[:, None]).to(torch.uint8).to(DEV)
         km[0, 3] = 0  # a hole inside the valid range
-    monkeypatch.setenv("CM3P_ATTN_FWD_IMPL", "wave3")
-    o3, l3 = K.attn_fwd(qkv, km, B, S, nh, -1, 0.125, prescaled=True)
-    monkeypatch.delenv("CM3P_ATTN_FWD_IMPL")
+    o3, l3 = K.attn_fwd(qkv, km, B, S, nh, S, 0.125, prescaled=True)
     o1, l1 = K.attn_fwd(qkv, km, B, S, nh, -1, 0.125, prescaled=True)
     o2, l2 = K.attn_fwd(qkv, km, B, S, nh, -1, 0.125, prescaled=True)
     torch.cuda.synchronize()
@@ -797,7 +793,6 @@ def test_fused_backward_with_four_key_blocks_per_slab_at_short_sequences(K, monk
     S = 256 * nkb - (17 if lens is None else 0)
     if lens is not None:
         S = lens[0]
-    monkeypatch.setenv("CM3P_ATTN_BWD_FUSED", "1")
     monkeypatch.setenv("CM3P_FUSED_SLAB_GROUP", "4")
     assert _lib_query("cm3p_attn_bwd_fused_slab_group", S) == 4
     _attn_case(K, 2 if lens is None else len(lens), S, 2, -1, lens, 77 + nkb, prescaled=True)

@@ -1,10 +1,9 @@
 #!/usr/bin/env python3
 """One-process A/B of the attention backward kernels at the C2 / C4 global-layer shapes (development aid).
 
-arm "fused": window = -1                         -> attention_bwd_fused.hip (prep + five-product kernel + slab reduce)
-arm "pair":  window = -1, CM3P_ATTN_BWD_FUSED=0  -> attention_bwd.hip (attn_bwd_dq3_kernel + attn_bwd_dkv3_kernel, seven products)
-arm "band":  window = S                          -> attention.hip's band kernels with every key inside the window (the same
-                                                    mathematics), i.e. the kernels that served the global layers in round 1
+arm "fused": window = -1  -> attention_bwd_fused.hip (prep + five-product kernel + slab reduce)
+arm "band":  window = S   -> attention.hip's band kernels with every key inside the window (the same mathematics, seven products),
+                             i.e. the kernels that served the global layers in round 1 and the tests' cross-check partner
 Interleaved rounds, per-stage HIP-event timing, and a check that the arms agree (and against an fp32 torch reference with --ref).
 
     python tools/attn_bwd_ab.py [--seq 4096] [--batch 32] [--rounds 5]
@@ -28,7 +27,7 @@ def main():
     ap.add_argument("--batch", type=int, default=32)
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--padded", action="store_true", help="right-pad every second row to 3/4 of the length (key mask path)")
-    ap.add_argument("--arms", default="fused,pair,band")
+    ap.add_argument("--arms", default="fused,band")
     ap.add_argument("--window", type=int, default=-1, help="sliding-window layers: |q - k| <= window (arms fused / band only)")
     ap.add_argument("--plain-q", action="store_true", help="q_prescaled = 0 kernels (the model runs the prescaled ones)")
     args = ap.parse_args()
@@ -47,15 +46,11 @@ def main():
     rope = K.rope_table(pos.contiguous(), inv)
     pre = not args.plain_q
     out, lse = K.attn_fwd(qkv, mask, B, S, nh, args.window, 0.125, pre)
-    all_arms = {"fused": (-1, "1"), "pair": (-1, "0"), "band": (S, "0")}
-    if args.window >= 0:
-        all_arms = {"fused": (args.window, "1"), "band": (args.window, "0")}
+    all_arms = {"fused": -1, "band": S} if args.window < 0 else {"fused": args.window, "band": args.window}
     arms = {k: all_arms[k] for k in args.arms.split(",") if k in all_arms}
 
     def run(name):
-        w, fused = arms[name]
-        os.environ["CM3P_ATTN_BWD_FUSED"] = fused
-        return K.attn_bwd(qkv, out, do, lse, mask, B, S, nh, w, 0.125, rope, False, pre)
+        return K.attn_bwd(qkv, out, do, lse, mask, B, S, nh, arms[name], 0.125, rope, False, pre)
 
     res = {name: run(name) for name in arms}
     torch.cuda.synchronize()

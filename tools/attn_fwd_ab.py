@@ -2,7 +2,7 @@
 """Global attention forward: the pipelined kernel (attention_fwd.hip) against an fp32 restatement, and its time at the C2 / C4 shapes.
 
     python tools/attn_fwd_ab.py [check] [time] [--iters 20]
-    CM3P_ATTN_FWD_IMPL=wave3 python tools/attn_fwd_ab.py time      # the three-waves-per-SIMD kernel (attention.hip), same shapes
+    python tools/attn_fwd_ab.py time --band     # the three-waves-per-SIMD kernel (attention.hip) at window = S, same shapes
 """
 import math
 import os
@@ -76,16 +76,17 @@ def timeit(fn, iters):
     return e0.elapsed_time(e1) / iters
 
 
-def time_shapes(iters):
+def time_shapes(iters, band):
     g = torch.Generator(device="cuda").manual_seed(0)
     for B, S, nh in ((32, 4096, 12), (16, 8192, 12)):
         qkv = torch.randn(B, S, 3, nh, 64, device="cuda", generator=g).to(torch.bfloat16)
         qkv[:, :, 0] *= 0.18
-        ms = timeit(lambda: K.attn_fwd(qkv, None, B, S, nh, -1, 0.125, True), iters)
+        w = S if band else -1  # (window = S: every key visible, the global mask, on attn_fwd_kernel)
+        ms = timeit(lambda: K.attn_fwd(qkv, None, B, S, nh, w, 0.125, True), iters)
         fl = 4.0 * B * nh * S * S * 64
-        print(f"impl={os.environ.get('CM3P_ATTN_FWD_IMPL', 'pipe')} B={B} S={S}: {ms:.3f} ms = {fl / ms / 1e9:.0f} TFLOP/s = {fl / ms / 1e9 / 2500:.3f} of 2.5 PF")
+        print(f"impl={'band' if band else 'pipe'} B={B} S={S}: {ms:.3f} ms = {fl / ms / 1e9:.0f} TFLOP/s = {fl / ms / 1e9 / 2500:.3f} of 2.5 PF")
         mask = torch.ones(B, S, dtype=torch.uint8, device="cuda")
-        ms = timeit(lambda: K.attn_fwd(qkv, mask, B, S, nh, -1, 0.125, True), iters)
+        ms = timeit(lambda: K.attn_fwd(qkv, mask, B, S, nh, w, 0.125, True), iters)
         print(f"   with an all-ones key mask: {ms:.3f} ms")
 
 
@@ -95,4 +96,4 @@ if __name__ == "__main__":
     if "check" in what:
         check()
     if "time" in what:
-        time_shapes(iters)
+        time_shapes(iters, "--band" in sys.argv)

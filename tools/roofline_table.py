@@ -44,7 +44,7 @@ def short(name: str) -> str:
 def family(k: str) -> str:
     if k.startswith(("gemm8p_kernel", "gemm256_kernel", "gemm_bf16_kernel", "splitk_reduce", "reduce_many")):
         return "gemm"
-    if k.startswith(("attn_fwd_g_kernel", "attn_bwd_fused_kernel", "attn_bwd_dq_reduce", "attn_bwd_prep", "attn_bwd_dq3", "attn_bwd_dkv3")):
+    if k.startswith(("attn_fwd_g_kernel", "attn_bwd_fused_kernel", "attn_bwd_dq_reduce", "attn_bwd_prep")):
         return "attn_global"
     if k.startswith(("attn_fwd_kernel", "attn_bwd_dq_kernel", "attn_bwd_dkv_kernel")):
         return "attn_band"
