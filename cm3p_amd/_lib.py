@@ -8,18 +8,18 @@ from __future__ import annotations
 
 import ctypes
 import os
-from ctypes import c_float, c_int, c_int64, c_void_p
+from ctypes import c_float, c_int, c_int64, c_uint64, c_void_p
 
 import torch
 
 F32, BF16 = 0, 1
 EPI_BF16, EPI_F32, EPI_F32_RESID, EPI_F32_BIAS = 0, 1, 2, 5
-ABI_VERSION = 16
+ABI_VERSION = 17
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("CM3P_HIP_LIB") or os.path.join(_HERE, "csrc", "libcm3p_hip.so")  # env override: kernel experiments
 
-_P, _I, _L, _F = c_void_p, c_int, c_int64, c_float
+_P, _I, _L, _F, _U64 = c_void_p, c_int, c_int64, c_float, c_uint64
 _RETURNS_INT64 = {"cm3p_attn_bwd_fused_workspace_bytes", "cm3p_token_order_workspace_ints"}  # size queries that do not fit an int
 
 # name -> argtypes, mirrors include/cm3p_hip.h one to one
@@ -54,11 +54,22 @@ SIGNATURES = {
     "cm3p_attn_generic_supported": [_I],
     "cm3p_attn_fwd_generic": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _P],
     "cm3p_attn_bwd_generic": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _P],
+    "cm3p_attn_fwd_generic_dropout": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _I, _I, _U64, _P],
+    "cm3p_attn_bwd_generic_dropout": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _I, _I, _U64, _P],
     "cm3p_rope_apply_generic": [_P, _P, _P, _I, _I, _I, _I, _L, _I, _P],
     "cm3p_attn_bwd": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _P, _P, _L, _I, _I, _P],
     "cm3p_geglu_fwd": [_P, _P, _L, _I, _P],
     "cm3p_gemm_geglu": [_P, _P, _P, _L, _L, _L, _P],
     "cm3p_geglu_bwd": [_P, _P, _P, _L, _I, _P],
+    "cm3p_dropout_f32": [_P, _P, _P, _P, _L, _I, _I, _P, _I, _I, _I, _I, _U64, _P],
+    "cm3p_attn_fwd_dropout": [_P, _P, _P, _P, _I, _I, _I, _I, _F, _I, _I, _I, _U64, _P],
+    "cm3p_attn_bwd_dropout": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _P, _P, _L, _I, _I, _I, _I, _U64, _P],
+    "cm3p_attn_fwd_dropout_varlen": [_P, _P, _P, _P, _I, _I, _L, _I, _I, _F, _I, _I, _I, _U64, _P],
+    "cm3p_attn_bwd_dropout_varlen": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _L, _I, _I, _F, _P, _P, _I, _I, _I, _I, _U64, _P],
+    "cm3p_geglu_fwd_dropout": [_P, _P, _L, _I, _I, _P, _I, _I, _I, _U64, _P],
+    "cm3p_geglu_bwd_dropout": [_P, _P, _P, _L, _I, _I, _P, _I, _I, _I, _U64, _P],
+    "cm3p_dropout_keep": [_P, _I, _I, _I, _I, _I, _I, _U64, _P],
+    "cm3p_philox4x32_10_host": [_P, _P, _P, _L],
     "cm3p_gelu_fwd": [_P, _P, _L, _P],
     "cm3p_gelu_bwd": [_P, _P, _P, _L, _P],
     "cm3p_im2col_k3": [_P, _I, _P, _I, _I, _I, _I, _I, _P],

@@ -19,6 +19,7 @@
 // LDS tiles use one swizzled image (128-byte rows) that is bank-conflict free for ds_read_b128 row fragments AND for
 // ds_read_b64_tr_b16 transposed reads, so a tile consumed both ways (K in dq; Q and dO in dk/dv) is stored once.
 #include "attn_common.h"
+#include "dropout_rng.h"
 
 #ifndef CM3P_BABL
 #define CM3P_BABL 0  // timing-only ablations of attn_bwd_dkv_kernel: 1 no products, 2 no epilogue, 4 no tile DMA
@@ -98,10 +99,21 @@ constexpr int kFwdStage = 8192 + 8192 + 64 + 16;  // K image R, V image T, mask 
 // fp32 v_fma per score - q is never re-rounded to bf16.
 // BAND: sliding-window layers (window >= 0); the global instance (window = -1 at compile time) carries no band arithmetic and
 // shows up as its own row in a profile.
-template <int QSUB, bool PRE, bool BAND>
+// Drop = {cm3p_drop::DropCfg}: attention-probability dropout (dropout_rng.h, site 1): l sums the undropped p, PV takes p o keep,
+// 1 / (1 - p) joins 1 / l at the store; lse is unchanged.  Drop = {} (every instance without dropout) compiles to the kernel without it:
+// same signature, same code.
+template <typename... T>
+__device__ __forceinline__ cm3p_drop::DropCfg drop_cfg(T... t) {
+    if constexpr (sizeof...(T) > 0) return (t, ...);
+    else return cm3p_drop::DropCfg{};
+}
+
+template <int QSUB, bool PRE, bool BAND, typename... Drop>
 __global__ __launch_bounds__(256, QSUB == 1 ? 2 : 1) void attn_fwd_kernel(const uint16_t* __restrict__ qkv, uint16_t* __restrict__ out,
                                                                         float* __restrict__ lse, const uint8_t* __restrict__ kmask,
-                                                                        int Smax, int nh, int window_arg, float scale, VarLen vl) {
+                                                                        int Smax, int nh, int window_arg, float scale, VarLen vl, Drop... drop) {
+    constexpr bool DROP = sizeof...(Drop) > 0;
+    const cm3p_drop::DropCfg dc = drop_cfg(drop...);
     const int window = BAND ? window_arg : -1;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int QW = 32 * QSUB;  // queries per wave
@@ -248,6 +260,18 @@ __global__ __launch_bounds__(256, QSUB == 1 ? 2 : 1) void attn_fwd_kernel(const 
                         psum += p;
                     }
                 l_run[u] += psum;
+                if constexpr (DROP) {  // key rows 8 g + 4 hh + r of each 32-key block: half of one Philox call per 8 keys
+                    const uint32_t c2 = (uint32_t)(b * nh + head);
+#pragma unroll
+                    for (int blk = 0; blk < 2; ++blk)
+#pragma unroll
+                        for (int g = 0; g < 4; ++g) {
+                            const uint32_t m =
+                                cm3p_drop::keep8(dc.seed, (uint32_t)(key0 + 32 * blk + 8 * g) >> 3, (uint32_t)qrow[u], c2, dc.c3, dc.thr) >> (4 * hh);
+#pragma unroll
+                            for (int r = 0; r < 4; ++r) sacc[u][blk][4 * g + r] = (m >> r) & 1u ? sacc[u][blk][4 * g + r] : 0.f;
+                        }
+                }
             }
             // O^T += V^T P^T: each V^T fragment (two transposed LDS reads) feeds every sub-block
 #pragma unroll
@@ -271,7 +295,7 @@ __global__ __launch_bounds__(256, QSUB == 1 ? 2 : 1) void attn_fwd_kernel(const 
         const float l_tot = l_run[u] + __shfl_xor(l_run[u], 32, 64);
         const float inv = l_tot > 0.f ? 1.0f / l_tot : 0.f;
         // (the loop's last barrier is behind every wave: the stages are free and serve as the waves' transposition buffers)
-        store_rows32(smem + 4608 * wid, oacc[u][0], oacc[u][1], inv, out + (sv.row0 + q0 + 32 * u) * nh * 64 + head * 64, (int64_t)nh * 64,
+        store_rows32(smem + 4608 * wid, oacc[u][0], oacc[u][1], DROP ? inv * dc.scale : inv, out + (sv.row0 + q0 + 32 * u) * nh * 64 + head * 64, (int64_t)nh * 64,
                      S - (q0 + 32 * u), lane);
         if (qrow[u] < S && hh == 0)
             lse[sv.stat0 + qrow[u]] = l_tot > 0.f ? (mc_run[u] + __log2f(l_tot)) * 0.69314718055994531f : __builtin_huge_valf();
@@ -303,13 +327,14 @@ __device__ unsigned long long* g_band_trace = nullptr;
 constexpr int kDqStage = 2 * 8192 + 256;  // K image, V image, one validity dword per key
 constexpr int kDqSlots = 4;               // LDS-DMA ring: tile t+3 is requested while tile t is consumed
 
-template <bool PRE, bool MASK>
+// DROP: dS = P o (Z o dP - delta), Z = keep / (1 - p) regenerated from dropout_rng.h (delta = rowsum(dO o O) of the dropped O)
+template <bool PRE, bool MASK, bool DROP = false>
 __device__ __forceinline__ void band_dq_block(char* smem, int qblk, int head, int b, const uint16_t* __restrict__ qkv,
                                               const uint16_t* __restrict__ d_o, const uint16_t* __restrict__ o_rows,
                                               const float* __restrict__ lse, float* __restrict__ delta, uint16_t* __restrict__ dqkv,
                                               const uint8_t* __restrict__ kmask, int Smax, int nh, int window, float scale,
                                               const float* __restrict__ rope_cos, const float* __restrict__ rope_sin,
-                                              int64_t pos_batch_stride, VarLen vl) {
+                                              int64_t pos_batch_stride, VarLen vl, const cm3p_drop::DropCfg& dc = cm3p_drop::DropCfg{}) {
     const int tid = threadIdx.x, lane = tid & 63, hh = lane >> 5;
     const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int Q0 = qblk * 128;
@@ -429,10 +454,26 @@ __device__ __forceinline__ void band_dq_block(char* smem, int qblk, int head, in
                     dp = mfma32(frag_R(st + 8192, 32 * blk, s, lane), dof[s], dp);
                 }
                 if (!unmasked) mask_scores_keyrows_d<MASK>(sacc, mb, blk, key0, lo, hi, hh);
+                if constexpr (DROP) {
+                    const uint32_t c2 = (uint32_t)(b * nh + head);
 #pragma unroll
-                for (int i = 0; i < 16; ++i) {
-                    const float p = __builtin_amdgcn_exp2f(PRE ? sacc[i] : sacc[i] * c);
-                    sacc[i] = p * dp[i];  // dS^T / scale (the scale is applied once, to dQ)
+                    for (int g = 0; g < 4; ++g) {
+                        const uint32_t m = cm3p_drop::keep8(dc.seed, (uint32_t)(key0 + 32 * blk + 8 * g) >> 3, (uint32_t)qrow, c2, dc.c3, dc.thr) >> (4 * hh);
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) {
+                            const int i = 4 * g + r;
+                            const float p = __builtin_amdgcn_exp2f(PRE ? sacc[i] : sacc[i] * c);
+                            // dp holds dP - delta: Z o dP - delta = keep ? dp + (1 / (1 - p) - 1) (dp + delta) : -delta
+                            // (written so that thr = 0, scale 1, gives p * dp exactly: the dropout-free kernel's bits)
+                            sacc[i] = p * ((m >> r) & 1u ? __builtin_fmaf(dc.scale - 1.0f, dp[i] + dlt, dp[i]) : -dlt);
+                        }
+                    }
+                } else {
+#pragma unroll
+                    for (int i = 0; i < 16; ++i) {
+                        const float p = __builtin_amdgcn_exp2f(PRE ? sacc[i] : sacc[i] * c);
+                        sacc[i] = p * dp[i];  // dS^T / scale (the scale is applied once, to dQ)
+                    }
                 }
 #pragma unroll
                 for (int sp = 0; sp < 2; ++sp) {
@@ -477,6 +518,21 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(const uint16_t* __r
                                     pos_batch_stride, vl);
 }
 
+template <bool PRE, bool MASK>
+__global__ __launch_bounds__(256, 2) void attn_bwd_dq_drop_kernel(const uint16_t* __restrict__ qkv, const uint16_t* __restrict__ d_o,
+                                                                  const uint16_t* __restrict__ o_rows, const float* __restrict__ lse,
+                                                                  float* __restrict__ delta, uint16_t* __restrict__ dqkv,
+                                                                  const uint8_t* __restrict__ kmask, int Smax, int nh, int window, float scale,
+                                                                  const float* __restrict__ rope_cos, const float* __restrict__ rope_sin,
+                                                                  int64_t pos_batch_stride, VarLen vl, cm3p_drop::DropCfg dc) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    int qblk, head, b;
+    if (window >= 0) decode_block_band((Smax + 127) / 128, nh, qblk, head, b);
+    else decode_block((Smax + 127) / 128, nh, qblk, head, b);
+    band_dq_block<PRE, MASK, true>(smem, qblk, head, b, qkv, d_o, o_rows, lse, delta, dqkv, kmask, Smax, nh, window, scale, rope_cos, rope_sin,
+                                   pos_batch_stride, vl, dc);
+}
+
 // ---------------------------------------------------------------------------------------------------------------
 // dK, dV: one workgroup = 4 waves = 128 keys of one (batch, head); each wave owns 32 keys (key on the lane) and keeps
 // dK^T, dV^T (64 x 32 each) in accumulators while the workgroup sweeps query tiles of 64 rows.
@@ -486,13 +542,14 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(const uint16_t* __r
 constexpr int kDkvStage = 2 * 8192 + 512;  // Q image, dO image, the rows' lse and delta (raw, 64 floats each)
 constexpr int kDkvSlots = 4;               // LDS-DMA ring, as in the dq kernel
 
-template <bool PRE>
+// DROP: dV = (P o Z)^T dO and dS = P o (Z o dP - delta), one Philox call per (query, this lane's key)
+template <bool PRE, bool DROP = false>
 __device__ __forceinline__ void band_dkv_block(char* smem, int kblk, int head, int b, const uint16_t* __restrict__ qkv,
                                                const uint16_t* __restrict__ d_o, const float* __restrict__ lse,
                                                const float* __restrict__ delta, uint16_t* __restrict__ dqkv,
                                                const uint8_t* __restrict__ kmask, int Smax, int nh, int window, float scale,
                                                const float* __restrict__ rope_cos, const float* __restrict__ rope_sin,
-                                               int64_t pos_batch_stride, VarLen vl) {
+                                               int64_t pos_batch_stride, VarLen vl, const cm3p_drop::DropCfg& dc = cm3p_drop::DropCfg{}) {
     const int tid = threadIdx.x, lane = tid & 63, hh = lane >> 5;
     const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int K0 = kblk * 128;
@@ -587,7 +644,7 @@ __device__ __forceinline__ void band_dkv_block(char* smem, int kblk, int head, i
                 // (a 64-row tile that touches the wave's band may still hold a 32-row block that lies outside it: a quarter of the
                 //  blocks of a +-64 window)
                 if (qt0 + 32 * qb > whi || qt0 + 32 * qb + 31 < wlo) continue;
-                f32x16 sacc, dp;
+                f32x16 sacc, dp, dl;
                 // initial accumulators: row constants -lse*log2(e) and -delta (rows = queries)
 #pragma unroll
                 for (int g = 0; g < 4; ++g) {
@@ -597,6 +654,7 @@ __device__ __forceinline__ void band_dkv_block(char* smem, int kblk, int head, i
                     for (int r = 0; r < 4; ++r) {
                         sacc[4 * g + r] = a[r] * lse_mul;
                         dp[4 * g + r] = -d[r];
+                        if constexpr (DROP) dl[4 * g + r] = d[r];
                     }
 
                 }
@@ -608,7 +666,21 @@ __device__ __forceinline__ void band_dkv_block(char* smem, int kblk, int head, i
                 // every (query, key) pair of this 32 x 32 block visible?  (queries past S carry -inf and give p = 0 anyway)
                 const int qb0 = qt0 + 32 * qb;
                 const bool plain = keys_all_ok && (window < 0 || (qb0 >= k0 + 31 - window && qb0 + 31 <= k0 + window));
-                if (plain) {
+                if constexpr (DROP) {
+                    const uint32_t c2 = (uint32_t)(b * nh + head);
+#pragma unroll
+                    for (int g = 0; g < 4; ++g)
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) {
+                            const int i = 4 * g + r;
+                            const int q = qb0 + 8 * g + 4 * hh + r;
+                            const bool ok = key_ok & (q >= lo) & (q <= hi);
+                            const float p = ok ? __builtin_amdgcn_exp2f(PRE ? sacc[i] : sacc[i] * c) : 0.f;
+                            const bool kept = (cm3p_drop::keep8(dc.seed, (uint32_t)krow >> 3, (uint32_t)q, c2, dc.c3, dc.thr) >> (krow & 7)) & 1u;
+                            sacc[i] = kept ? p * dc.scale : 0.f;                                           // (P o Z): dV
+                            dp[i] = p * (kept ? __builtin_fmaf(dc.scale - 1.0f, dp[i] + dl[i], dp[i]) : -dl[i]);  // dS / scale: dK (as in dq)
+                        }
+                } else if (plain) {
 #pragma unroll
                     for (int i = 0; i < 16; ++i) {
                         const float p = __builtin_amdgcn_exp2f(PRE ? sacc[i] : sacc[i] * c);
@@ -673,6 +745,21 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(const uint16_t* __
     if (window >= 0) decode_block_band((Smax + 127) / 128, nh, kblk, head, b);
     else decode_block((Smax + 127) / 128, nh, kblk, head, b);
     band_dkv_block<PRE>(smem, kblk, head, b, qkv, d_o, lse, delta, dqkv, kmask, Smax, nh, window, scale, rope_cos, rope_sin, pos_batch_stride, vl);
+}
+
+template <bool PRE>
+__global__ __launch_bounds__(256, 2) void attn_bwd_dkv_drop_kernel(const uint16_t* __restrict__ qkv, const uint16_t* __restrict__ d_o,
+                                                                   const float* __restrict__ lse, const float* __restrict__ delta,
+                                                                   uint16_t* __restrict__ dqkv, const uint8_t* __restrict__ kmask, int Smax, int nh,
+                                                                   int window, float scale, const float* __restrict__ rope_cos,
+                                                                   const float* __restrict__ rope_sin, int64_t pos_batch_stride, VarLen vl,
+                                                                   cm3p_drop::DropCfg dc) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    int kblk, head, b;
+    if (window >= 0) decode_block_band((Smax + 127) / 128, nh, kblk, head, b);
+    else decode_block((Smax + 127) / 128, nh, kblk, head, b);
+    band_dkv_block<PRE, true>(smem, kblk, head, b, qkv, d_o, lse, delta, dqkv, kmask, Smax, nh, window, scale, rope_cos, rope_sin, pos_batch_stride,
+                              vl, dc);
 }
 
 
@@ -754,6 +841,58 @@ static int launch_attn_fwd(const void* qkv, void* out, float* lse, const uint8_t
         else attn_fwd_kernel<1, false, false><<<grid, 256, 2 * kFwdStage, s>>>(CM3P_FWD_ARGS);
     }
 #undef CM3P_FWD_ARGS
+    return CM3P_OK;
+}
+
+// attention-probability dropout: the band kernels at every window (global layers at window -1), never the pipelined forward
+static int launch_attn_fwd_drop(const void* qkv, void* out, float* lse, const uint8_t* key_mask, int B, int S, int nh, int window,
+                                float scale, VarLen vl, int pre, const cm3p_drop::DropCfg& dc, hipStream_t s) {
+    const dim3 grid(((S + 127) / 128) * nh * B);
+#define CM3P_FWD_ARGS (const uint16_t*)qkv, (uint16_t*)out, lse, key_mask, S, nh, window, scale, vl, dc
+    if (window >= 0) {
+        if (pre) attn_fwd_kernel<1, true, true, cm3p_drop::DropCfg><<<grid, 256, 2 * kFwdStage, s>>>(CM3P_FWD_ARGS);
+        else attn_fwd_kernel<1, false, true, cm3p_drop::DropCfg><<<grid, 256, 2 * kFwdStage, s>>>(CM3P_FWD_ARGS);
+    } else {
+        if (pre) attn_fwd_kernel<1, true, false, cm3p_drop::DropCfg><<<grid, 256, 2 * kFwdStage, s>>>(CM3P_FWD_ARGS);
+        else attn_fwd_kernel<1, false, false, cm3p_drop::DropCfg><<<grid, 256, 2 * kFwdStage, s>>>(CM3P_FWD_ARGS);
+    }
+#undef CM3P_FWD_ARGS
+    return CM3P_OK;
+}
+
+static int launch_attn_bwd_drop(const void* qkv, const void* out, const void* dout, const float* lse, float* delta, void* dqkv,
+                                const uint8_t* key_mask, int B, int S, int nh, int window, float scale, const float* cos_tab,
+                                const float* sin_tab, int64_t pos_batch_stride, VarLen vl, int stages, int pre, const cm3p_drop::DropCfg& dc,
+                                hipStream_t s) {
+    const dim3 grid(((S + 127) / 128) * nh * B);
+    if (stages & CM3P_ATTN_BWD_DQ) {
+#define CM3P_DQ_ARGS (const uint16_t*)qkv, (const uint16_t*)dout, (const uint16_t*)out, lse, delta, (uint16_t*)dqkv, key_mask, S, nh, window, scale, cos_tab, sin_tab, pos_batch_stride, vl, dc
+        static Cm3pDevOnce once;
+        const int rc_once = once.run([] {
+            return cm3p_set_max_lds({reinterpret_cast<const void*>(&attn_bwd_dq_drop_kernel<true, true>), reinterpret_cast<const void*>(&attn_bwd_dq_drop_kernel<true, false>),
+                                     reinterpret_cast<const void*>(&attn_bwd_dq_drop_kernel<false, true>), reinterpret_cast<const void*>(&attn_bwd_dq_drop_kernel<false, false>)},
+                                    kDqSlots * kDqStage);
+        });
+        if (rc_once != CM3P_OK) return rc_once;
+        if (pre && key_mask) attn_bwd_dq_drop_kernel<true, true><<<grid, 256, kDqSlots * kDqStage, s>>>(CM3P_DQ_ARGS);
+        else if (pre) attn_bwd_dq_drop_kernel<true, false><<<grid, 256, kDqSlots * kDqStage, s>>>(CM3P_DQ_ARGS);
+        else if (key_mask) attn_bwd_dq_drop_kernel<false, true><<<grid, 256, kDqSlots * kDqStage, s>>>(CM3P_DQ_ARGS);
+        else attn_bwd_dq_drop_kernel<false, false><<<grid, 256, kDqSlots * kDqStage, s>>>(CM3P_DQ_ARGS);
+#undef CM3P_DQ_ARGS
+        if (hipGetLastError() != hipSuccess) return CM3P_ERR_LAUNCH;
+    }
+    if (stages & CM3P_ATTN_BWD_DKV) {
+#define CM3P_DKV_ARGS (const uint16_t*)qkv, (const uint16_t*)dout, lse, delta, (uint16_t*)dqkv, key_mask, S, nh, window, scale, cos_tab, sin_tab, pos_batch_stride, vl, dc
+        static Cm3pDevOnce once2;
+        const int rc_once = once2.run([] {
+            return cm3p_set_max_lds({reinterpret_cast<const void*>(&attn_bwd_dkv_drop_kernel<true>), reinterpret_cast<const void*>(&attn_bwd_dkv_drop_kernel<false>)},
+                                    kDkvSlots * kDkvStage);
+        });
+        if (rc_once != CM3P_OK) return rc_once;
+        if (pre) attn_bwd_dkv_drop_kernel<true><<<grid, 256, kDkvSlots * kDkvStage, s>>>(CM3P_DKV_ARGS);
+        else attn_bwd_dkv_drop_kernel<false><<<grid, 256, kDkvSlots * kDkvStage, s>>>(CM3P_DKV_ARGS);
+#undef CM3P_DKV_ARGS
+    }
     return CM3P_OK;
 }
 
@@ -849,6 +988,70 @@ int cm3p_attn_bwd_varlen(const void* qkv, const void* out, const void* dout, con
     CM3P_LAUNCH_CHECK();
     return CM3P_OK;
 }
+
+#define CM3P_ATTN_DROP_REQUIRE() CM3P_REQUIRE(thr >= 0 && thr <= 65536 && layer >= 0 && layer < (1 << 29))
+
+int cm3p_attn_fwd_dropout(const void* qkv, void* out, float* lse, const uint8_t* key_mask, int B, int S, int nh, int window, float scale,
+                          int q_prescaled, int layer, int thr, uint64_t seed, void* stream) {
+    CM3P_REQUIRE(qkv && out && lse && B > 0 && S > 0 && nh > 0 && scale > 0.f);
+    CM3P_REQUIRE(cm3p_aligned16(qkv) && cm3p_aligned16(out));
+    CM3P_ATTN_DROP_REQUIRE();
+    const int rc = launch_attn_fwd_drop(qkv, out, lse, key_mask, B, S, nh, window, scale, VarLen{nullptr, 0}, q_prescaled != 0,
+                                        cm3p_drop::make_cfg(layer, cm3p_drop::kSiteAttnProbs, thr, seed), static_cast<hipStream_t>(stream));
+    if (rc != CM3P_OK) return rc;
+    CM3P_LAUNCH_CHECK();
+    return CM3P_OK;
+}
+
+int cm3p_attn_bwd_dropout(const void* qkv, const void* out, const void* dout, const float* lse, float* delta, void* dqkv,
+                          const uint8_t* key_mask, int B, int S, int nh, int window, float scale, const float* cos_tab,
+                          const float* sin_tab, int64_t pos_batch_stride, int stages, int q_prescaled, int layer, int thr, uint64_t seed,
+                          void* stream) {
+    CM3P_REQUIRE((cos_tab == nullptr) == (sin_tab == nullptr));
+    CM3P_REQUIRE(stages >= 1 && stages <= 3);
+    CM3P_REQUIRE(pos_batch_stride == 0 || pos_batch_stride == S);
+    CM3P_REQUIRE(qkv && out && dout && lse && delta && dqkv && B > 0 && S > 0 && nh > 0 && scale > 0.f);
+    CM3P_REQUIRE(cm3p_aligned16(qkv) && cm3p_aligned16(out) && cm3p_aligned16(dout) && cm3p_aligned16(dqkv));
+    CM3P_REQUIRE((int64_t)S * 3 * nh * 128 < (int64_t(1) << 31));
+    CM3P_ATTN_DROP_REQUIRE();
+    const int rc = launch_attn_bwd_drop(qkv, out, dout, lse, delta, dqkv, key_mask, B, S, nh, window, scale, cos_tab, sin_tab, pos_batch_stride,
+                                        VarLen{nullptr, 0}, stages, q_prescaled != 0, cm3p_drop::make_cfg(layer, cm3p_drop::kSiteAttnProbs, thr, seed),
+                                        static_cast<hipStream_t>(stream));
+    if (rc != CM3P_OK) return rc;
+    CM3P_LAUNCH_CHECK();
+    return CM3P_OK;
+}
+
+int cm3p_attn_fwd_dropout_varlen(const void* qkv, void* out, float* lse, const int* cu_seqlens, int B, int max_seqlen, int64_t total, int nh,
+                                 int window, float scale, int q_prescaled, int layer, int thr, uint64_t seed, void* stream) {
+    CM3P_REQUIRE(qkv && out && lse && cu_seqlens && B > 0 && max_seqlen > 0 && total > 0 && nh > 0 && scale > 0.f);
+    CM3P_REQUIRE(cm3p_aligned16(qkv) && cm3p_aligned16(out));
+    CM3P_ATTN_DROP_REQUIRE();
+    const int rc = launch_attn_fwd_drop(qkv, out, lse, nullptr, B, max_seqlen, nh, window, scale, VarLen{cu_seqlens, total}, q_prescaled != 0,
+                                        cm3p_drop::make_cfg(layer, cm3p_drop::kSiteAttnProbs, thr, seed), static_cast<hipStream_t>(stream));
+    if (rc != CM3P_OK) return rc;
+    CM3P_LAUNCH_CHECK();
+    return CM3P_OK;
+}
+
+int cm3p_attn_bwd_dropout_varlen(const void* qkv, const void* out, const void* dout, const float* lse, float* delta, void* dqkv,
+                                 const int* cu_seqlens, int B, int max_seqlen, int64_t total, int nh, int window, float scale,
+                                 const float* cos_tab, const float* sin_tab, int stages, int q_prescaled, int layer, int thr, uint64_t seed,
+                                 void* stream) {
+    CM3P_REQUIRE((cos_tab == nullptr) == (sin_tab == nullptr));
+    CM3P_REQUIRE(stages >= 1 && stages <= 3);
+    CM3P_REQUIRE(qkv && out && dout && lse && delta && dqkv && cu_seqlens && B > 0 && max_seqlen > 0 && total > 0 && nh > 0 && scale > 0.f);
+    CM3P_REQUIRE(cm3p_aligned16(qkv) && cm3p_aligned16(out) && cm3p_aligned16(dout) && cm3p_aligned16(dqkv));
+    CM3P_REQUIRE((int64_t)max_seqlen * 3 * nh * 128 < (int64_t(1) << 31));
+    CM3P_ATTN_DROP_REQUIRE();
+    const int rc = launch_attn_bwd_drop(qkv, out, dout, lse, delta, dqkv, nullptr, B, max_seqlen, nh, window, scale, cos_tab, sin_tab, 0,
+                                        VarLen{cu_seqlens, total}, stages, q_prescaled != 0,
+                                        cm3p_drop::make_cfg(layer, cm3p_drop::kSiteAttnProbs, thr, seed), static_cast<hipStream_t>(stream));
+    if (rc != CM3P_OK) return rc;
+    CM3P_LAUNCH_CHECK();
+    return CM3P_OK;
+}
+#undef CM3P_ATTN_DROP_REQUIRE
 
 int cm3p_attn_probs(const void* qkv, const float* lse, const uint8_t* key_mask, float* probs, int B, int S, int nh, int window, float scale,
                     int q_prescaled, void* stream) {

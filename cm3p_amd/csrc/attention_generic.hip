@@ -11,8 +11,18 @@
 //     visible(b, q, kv) = key_mask[b, kv] AND (window < 0 OR |q - kv| <= window);  rows with no visible key: exact zeros, lse = +inf.
 // Layout: qkv [B, S, 3, nh, D] bf16 (q, k already rotated: cm3p_rope_apply_generic), out [B, S, nh, D] bf16, lse / delta [B, nh, S] fp32.
 #include "common.h"
+#include "dropout_rng.h"
 
 namespace {
+
+// Drop = {cm3p_drop::DropCfg}: attention-probability dropout (dropout_rng.h, site 1; the rule of attention.hip's band kernels): l sums the
+// undropped p, PV takes p o keep, dS = P o (Z o dP - delta), dV = (P o Z)^T dO.  Drop = {} is the kernel without dropout: same signature,
+// same code.
+template <typename... T>
+__device__ __forceinline__ cm3p_drop::DropCfg gen_drop_cfg(T... t) {
+    if constexpr (sizeof...(T) > 0) return (t, ...);
+    else return cm3p_drop::DropCfg{};
+}
 
 constexpr float kLog2eG = 1.4426950408889634f;
 
@@ -36,9 +46,12 @@ __device__ __forceinline__ void store_row_bf16(uint16_t* dst, const float (&src)
 }
 
 // one workgroup = 64 queries of one (batch, head), one thread per query; key tiles of 64 rows staged in LDS as fp32
-template <int D>
+template <int D, typename... Drop>
 __global__ __launch_bounds__(64) void attn_gen_fwd_kernel(const uint16_t* __restrict__ qkv, uint16_t* __restrict__ out, float* __restrict__ lse,
-                                                          const uint8_t* __restrict__ kmask, int S, int nh, int window, float scale) {
+                                                          const uint8_t* __restrict__ kmask, int S, int nh, int window, float scale,
+                                                          Drop... drop) {
+    constexpr bool DROP = sizeof...(Drop) > 0;
+    const cm3p_drop::DropCfg dc = gen_drop_cfg(drop...);
     __shared__ float Ks[64][D + 1], Vs[64][D + 1];
     __shared__ int Ms[64];
     const int tid = threadIdx.x, head = blockIdx.y, b = blockIdx.z;
@@ -67,7 +80,11 @@ __global__ __launch_bounds__(64) void attn_gen_fwd_kernel(const uint16_t* __rest
             Ms[tid] = key < S && (kmask ? kmask[(int64_t)b * S + key] != 0 : true);
         }
         __syncthreads();
+        uint32_t m8 = 0;
         for (int k = 0; k < 64; ++k) {
+            if constexpr (DROP) {  // one Philox call per 8 keys of this query
+                if ((k & 7) == 0) m8 = cm3p_drop::keep8(dc.seed, (uint32_t)(t * 64 + k) >> 3, (uint32_t)q, (uint32_t)(b * nh + head), dc.c3, dc.thr);
+            }
             if (!Ms[k]) continue;  // (uniform)
             const int kk = t * 64 + k;
             if (window >= 0 && (kk < q - window || kk > q + window)) continue;
@@ -84,24 +101,27 @@ __global__ __launch_bounds__(64) void attn_gen_fwd_kernel(const uint16_t* __rest
             }
             const float p = __builtin_amdgcn_exp2f(s - m);
             l += p;
+            const float pz = DROP ? ((m8 >> (k & 7)) & 1u ? p : 0.f) : p;
 #pragma unroll
-            for (int d = 0; d < D; ++d) o[d] = __builtin_fmaf(p, Vs[k][d], o[d]);
+            for (int d = 0; d < D; ++d) o[d] = __builtin_fmaf(pz, Vs[k][d], o[d]);
         }
         __syncthreads();
     }
     if (q < S) {
         const float inv = l > 0.f ? 1.0f / l : 0.f;
-        store_row_bf16<D>(out + ((int64_t)b * S + q) * nh * D + head * D, o, inv);
+        store_row_bf16<D>(out + ((int64_t)b * S + q) * nh * D + head * D, o, DROP ? inv * dc.scale : inv);
         lse[((int64_t)b * nh + head) * S + q] = l > 0.f ? (m + __log2f(l)) * 0.69314718055994531f : __builtin_huge_valf();
     }
 }
 
 // dq (gradient w.r.t. the rotated q) and delta[q] = sum_d dO[q, d] O[q, d]; one thread per query row
-template <int D>
+template <int D, typename... Drop>
 __global__ __launch_bounds__(64) void attn_gen_dq_kernel(const uint16_t* __restrict__ qkv, const uint16_t* __restrict__ o_rows,
                                                          const uint16_t* __restrict__ d_o, const float* __restrict__ lse,
                                                          float* __restrict__ delta, uint16_t* __restrict__ dqkv, const uint8_t* __restrict__ kmask,
-                                                         int S, int nh, int window, float scale) {
+                                                         int S, int nh, int window, float scale, Drop... drop) {
+    constexpr bool DROP = sizeof...(Drop) > 0;
+    const cm3p_drop::DropCfg dc = gen_drop_cfg(drop...);
     __shared__ float Ks[64][D + 1], Vs[64][D + 1];
     __shared__ int Ms[64];
     const int tid = threadIdx.x, head = blockIdx.y, b = blockIdx.z;
@@ -140,7 +160,11 @@ __global__ __launch_bounds__(64) void attn_gen_dq_kernel(const uint16_t* __restr
             Ms[tid] = key < S && (kmask ? kmask[(int64_t)b * S + key] != 0 : true);
         }
         __syncthreads();
+        uint32_t m8 = 0;
         for (int k = 0; k < 64; ++k) {
+            if constexpr (DROP) {
+                if ((k & 7) == 0) m8 = cm3p_drop::keep8(dc.seed, (uint32_t)(t * 64 + k) >> 3, (uint32_t)q, (uint32_t)(b * nh + head), dc.c3, dc.thr);
+            }
             if (!Ms[k]) continue;
             const int kk = t * 64 + k;
             if (window >= 0 && (kk < q - window || kk > q + window)) continue;
@@ -151,7 +175,8 @@ __global__ __launch_bounds__(64) void attn_gen_dq_kernel(const uint16_t* __restr
                 dp = __builtin_fmaf(dov[d], Vs[k][d], dp);
             }
             const float p = __builtin_amdgcn_exp2f(s * c - lse2);
-            const float ds = p * (dp - dlt);
+            // (thr = 0: dp * 1 - delta is dp - delta exactly, the dropout-free kernel's value)
+            const float ds = DROP ? p * ((m8 >> (k & 7)) & 1u ? dp * dc.scale - dlt : -dlt) : p * (dp - dlt);
 #pragma unroll
             for (int d = 0; d < D; ++d) dq[d] = __builtin_fmaf(ds, Ks[k][d], dq[d]);
         }
@@ -161,11 +186,13 @@ __global__ __launch_bounds__(64) void attn_gen_dq_kernel(const uint16_t* __restr
 }
 
 // dk, dv: one thread per key row; query tiles of 64 rows (q, dO, lse, delta) staged in LDS
-template <int D>
+template <int D, typename... Drop>
 __global__ __launch_bounds__(64) void attn_gen_dkv_kernel(const uint16_t* __restrict__ qkv, const uint16_t* __restrict__ d_o,
                                                           const float* __restrict__ lse, const float* __restrict__ delta,
                                                           uint16_t* __restrict__ dqkv, const uint8_t* __restrict__ kmask, int S, int nh, int window,
-                                                          float scale) {
+                                                          float scale, Drop... drop) {
+    constexpr bool DROP = sizeof...(Drop) > 0;
+    const cm3p_drop::DropCfg dc = gen_drop_cfg(drop...);
     __shared__ float Qs[64][D + 1], Gs[64][D + 1];
     __shared__ float Ls[64], Ds[64];
     const int tid = threadIdx.x, head = blockIdx.y, b = blockIdx.z;
@@ -208,10 +235,16 @@ __global__ __launch_bounds__(64) void attn_gen_dkv_kernel(const uint16_t* __rest
                     dp = __builtin_fmaf(Gs[i][d], vv[d], dp);
                 }
                 const float p = __builtin_amdgcn_exp2f(s * c - Ls[i]);
-                const float ds = p * (dp - Ds[i]);
+                float ds = p * (dp - Ds[i]), pz = p;
+                if constexpr (DROP) {  // key on the lane: one Philox call per (query, key), one of its 8 decisions
+                    const bool kept =
+                        (cm3p_drop::keep8(dc.seed, (uint32_t)key >> 3, (uint32_t)qq, (uint32_t)(b * nh + head), dc.c3, dc.thr) >> (key & 7)) & 1u;
+                    pz = kept ? p * dc.scale : 0.f;
+                    ds = p * (kept ? dp * dc.scale - Ds[i] : -Ds[i]);
+                }
 #pragma unroll
                 for (int d = 0; d < D; ++d) {
-                    dv[d] = __builtin_fmaf(p, Gs[i][d], dv[d]);
+                    dv[d] = __builtin_fmaf(pz, Gs[i][d], dv[d]);
                     dk[d] = __builtin_fmaf(ds, Qs[i][d], dk[d]);
                 }
             }
@@ -286,6 +319,46 @@ int cm3p_attn_bwd_generic(const void* qkv, const void* out, const void* dout, co
     attn_gen_dq_kernel<DD><<<grid, 64, 0, s>>>((const uint16_t*)qkv, (const uint16_t*)out, (const uint16_t*)dout, lse, delta, (uint16_t*)dqkv, \
                                                key_mask, S, nh, window, scale);                                                            \
     attn_gen_dkv_kernel<DD><<<grid, 64, 0, s>>>((const uint16_t*)qkv, (const uint16_t*)dout, lse, delta, (uint16_t*)dqkv, key_mask, S, nh, window, scale)
+    if (head_dim == 16) { CM3P_GEN_BWD(16); }
+    else if (head_dim == 32) { CM3P_GEN_BWD(32); }
+    else { CM3P_GEN_BWD(64); }
+#undef CM3P_GEN_BWD
+    CM3P_LAUNCH_CHECK();
+    return CM3P_OK;
+}
+
+int cm3p_attn_fwd_generic_dropout(const void* qkv, void* out, float* lse, const uint8_t* key_mask, int B, int S, int nh, int head_dim,
+                                  int window, float scale, int layer, int thr, uint64_t seed, void* stream) {
+    CM3P_REQUIRE(qkv && out && lse && B > 0 && S > 0 && nh > 0 && scale > 0.f && cm3p_attn_generic_supported(head_dim));
+    CM3P_REQUIRE(cm3p_aligned16(qkv) && cm3p_aligned16(out));
+    CM3P_REQUIRE(thr >= 0 && thr <= 65536 && layer >= 0 && layer < (1 << 29));
+    const dim3 grid((S + 63) / 64, nh, B);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const cm3p_drop::DropCfg dc = cm3p_drop::make_cfg(layer, cm3p_drop::kSiteAttnProbs, thr, seed);
+#define CM3P_GEN_FWD(DD) \
+    attn_gen_fwd_kernel<DD, cm3p_drop::DropCfg><<<grid, 64, 0, s>>>((const uint16_t*)qkv, (uint16_t*)out, lse, key_mask, S, nh, window, scale, dc)
+    if (head_dim == 16) CM3P_GEN_FWD(16);
+    else if (head_dim == 32) CM3P_GEN_FWD(32);
+    else CM3P_GEN_FWD(64);
+#undef CM3P_GEN_FWD
+    CM3P_LAUNCH_CHECK();
+    return CM3P_OK;
+}
+
+int cm3p_attn_bwd_generic_dropout(const void* qkv, const void* out, const void* dout, const float* lse, float* delta, void* dqkv,
+                                  const uint8_t* key_mask, int B, int S, int nh, int head_dim, int window, float scale, int layer, int thr,
+                                  uint64_t seed, void* stream) {
+    CM3P_REQUIRE(qkv && out && dout && lse && delta && dqkv && B > 0 && S > 0 && nh > 0 && scale > 0.f && cm3p_attn_generic_supported(head_dim));
+    CM3P_REQUIRE(cm3p_aligned16(qkv) && cm3p_aligned16(out) && cm3p_aligned16(dout) && cm3p_aligned16(dqkv));
+    CM3P_REQUIRE(thr >= 0 && thr <= 65536 && layer >= 0 && layer < (1 << 29));
+    const dim3 grid((S + 63) / 64, nh, B);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const cm3p_drop::DropCfg dc = cm3p_drop::make_cfg(layer, cm3p_drop::kSiteAttnProbs, thr, seed);
+#define CM3P_GEN_BWD(DD)                                                                                                                   \
+    attn_gen_dq_kernel<DD, cm3p_drop::DropCfg><<<grid, 64, 0, s>>>((const uint16_t*)qkv, (const uint16_t*)out, (const uint16_t*)dout, lse, delta,  \
+                                                                   (uint16_t*)dqkv, key_mask, S, nh, window, scale, dc);                          \
+    attn_gen_dkv_kernel<DD, cm3p_drop::DropCfg><<<grid, 64, 0, s>>>((const uint16_t*)qkv, (const uint16_t*)dout, lse, delta, (uint16_t*)dqkv,      \
+                                                                    key_mask, S, nh, window, scale, dc)
     if (head_dim == 16) { CM3P_GEN_BWD(16); }
     else if (head_dim == 32) { CM3P_GEN_BWD(32); }
     else { CM3P_GEN_BWD(64); }

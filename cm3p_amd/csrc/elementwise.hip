@@ -6,6 +6,7 @@
 //   TF:models/modernbert/modeling_modernbert.py:89-91             GeGLU with exact-erf GELU
 //   ref:cm3p/modeling_cm3p.py:385-396,631-642                     cls / masked-mean pooling
 #include "common.h"
+#include "dropout_rng.h"
 
 namespace {
 
@@ -253,12 +254,11 @@ __global__ __launch_bounds__(256) void geglu_fwd_kernel(const uint16_t* __restri
     }
 }
 
-// one item of the GeGLU backward: 8 columns of one row
-__device__ __forceinline__ void geglu_bwd_item(const uint4 ha, const uint4 hb, const uint4 hd, uint4& oa, uint4& ob) {
-    float a[8], b[8], d[8], da[8], db[8];
+// one item of the GeGLU backward: 8 columns of one row, the incoming gradient already widened
+__device__ __forceinline__ void geglu_bwd_item_f(const uint4 ha, const uint4 hb, const float (&d)[8], uint4& oa, uint4& ob) {
+    float a[8], b[8], da[8], db[8];
     unpack8(ha, a);
     unpack8(hb, b);
-    unpack8(hd, d);
 #pragma unroll
     for (int j = 0; j < 8; j += 2) {  // gelu'(a) = Phi(a) + a phi(a), gelu(a) = a Phi(a): one Phi for both
         const f32x2 av = {a[j], a[j + 1]};
@@ -272,6 +272,12 @@ __device__ __forceinline__ void geglu_bwd_item(const uint4 ha, const uint4 hb, c
     }
     oa = pack8(da);
     ob = pack8(db);
+}
+
+__device__ __forceinline__ void geglu_bwd_item(const uint4 ha, const uint4 hb, const uint4 hd, uint4& oa, uint4& ob) {
+    float d[8];
+    unpack8(hd, d);
+    geglu_bwd_item_f(ha, hb, d, oa, ob);
 }
 
 __global__ __launch_bounds__(256) void geglu_bwd_kernel(const uint16_t* __restrict__ dg, const uint16_t* __restrict__ h,
@@ -299,6 +305,114 @@ __global__ __launch_bounds__(256) void geglu_bwd_kernel(const uint16_t* __restri
             }
         }
     }
+}
+
+// ---- dropout (nn.Dropout, TF:models/modernbert/modeling_modernbert.py:70,86/91,260/300) --------------------------------------
+// Decisions come from the contract in dropout_rng.h; rows map to (sequence, position) by S when padded, by cu_seqlens when packed.
+struct DropArgs {
+    uint64_t seed;
+    uint32_t c3, thr;  // counter word 3 (4 * layer + site), threshold round(p * 65536)
+    float scale;       // 65536 / (65536 - thr)
+    int S, nseq;
+    const int* cu;
+};
+
+__device__ __forceinline__ uint32_t drop_keep8(const DropArgs& d, int64_t t, uint32_t f8) {
+    uint32_t b, s;
+    cm3p_drop::row_to_seq(t, d.S, d.cu, d.nseq, b, s);
+    return cm3p_drop::keep8(d.seed, f8, s, b, d.c3, d.thr);
+}
+
+// y = resid + x o Z on [rows, H] fp32 (H % 8 == 0; resid may be null); y_f32 may alias x; either output may be null (the bf16 twin
+// feeds a GEMM)
+__global__ __launch_bounds__(256) void dropout_f32_kernel(const float* x, const float* resid, float* y32, uint16_t* __restrict__ y16, int64_t rows,
+                                                          int H, DropArgs d) {
+    const int h8 = H / 8;
+    const int64_t n = rows * h8;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+        const int64_t t = i / h8;
+        const uint32_t m = drop_keep8(d, t, (uint32_t)(i - t * h8));
+        f32x4 v0 = reinterpret_cast<const f32x4*>(x)[2 * i], v1 = reinterpret_cast<const f32x4*>(x)[2 * i + 1];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            v0[j] = (m >> j) & 1u ? v0[j] * d.scale : 0.f;
+            v1[j] = (m >> (4 + j)) & 1u ? v1[j] * d.scale : 0.f;
+        }
+        if (resid) {
+            v0 += reinterpret_cast<const f32x4*>(resid)[2 * i];
+            v1 += reinterpret_cast<const f32x4*>(resid)[2 * i + 1];
+        }
+        if (y32) {
+            reinterpret_cast<f32x4*>(y32)[2 * i] = v0;
+            reinterpret_cast<f32x4*>(y32)[2 * i + 1] = v1;
+        }
+        if (y16)
+            reinterpret_cast<uint4*>(y16)[i] =
+                uint4{pack_bf16x2(v0.x, v0.y), pack_bf16x2(v0.z, v0.w), pack_bf16x2(v1.x, v1.y), pack_bf16x2(v1.z, v1.w)};
+    }
+}
+
+// g = (gelu_erf(h[:, :I]) * h[:, I:]) o Z, one rounding to bf16 (the product the Wo GEMM and its weight gradient read)
+__global__ __launch_bounds__(256) void geglu_drop_fwd_kernel(const uint16_t* __restrict__ h, uint16_t* __restrict__ g, int64_t T, int I,
+                                                             DropArgs d) {
+    const int i8 = I / 8;
+    const int64_t n = T * i8;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+        const int64_t t = i / i8;
+        const int c = (int)(i - t * i8);
+        const uint32_t m = drop_keep8(d, t, (uint32_t)c);
+        float a[8], b[8], y[8];
+        unpack8(*reinterpret_cast<const uint4*>(h + t * 2 * I + c * 8), a);
+        unpack8(*reinterpret_cast<const uint4*>(h + t * 2 * I + I + c * 8), b);
+#pragma unroll
+        for (int j = 0; j < 8; j += 2) {
+            const f32x2 gl = gelu_erf2(f32x2{a[j], a[j + 1]});
+            y[j] = (m >> j) & 1u ? (gl.x * b[j]) * d.scale : 0.f;
+            y[j + 1] = (m >> (j + 1)) & 1u ? (gl.y * b[j + 1]) * d.scale : 0.f;
+        }
+        *reinterpret_cast<uint4*>(g + t * I + c * 8) = pack8(y);
+    }
+}
+
+// dh from dg o Z and h
+__global__ __launch_bounds__(256) void geglu_drop_bwd_kernel(const uint16_t* __restrict__ dg, const uint16_t* __restrict__ h,
+                                                             uint16_t* __restrict__ dh, int64_t T, int I, DropArgs d) {
+    const int i8 = I / 8;
+    const int64_t n = T * i8;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+        const int64_t t = i / i8;
+        const int c = (int)(i - t * i8);
+        const uint32_t m = drop_keep8(d, t, (uint32_t)c);
+        float dz[8];
+        unpack8(*reinterpret_cast<const uint4*>(dg + t * I + c * 8), dz);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) dz[j] = (m >> j) & 1u ? dz[j] * d.scale : 0.f;
+        uint4 oa, ob;
+        geglu_bwd_item_f(*reinterpret_cast<const uint4*>(h + t * 2 * I + c * 8), *reinterpret_cast<const uint4*>(h + t * 2 * I + I + c * 8),
+                         dz, oa, ob);
+        *reinterpret_cast<uint4*>(dh + t * 2 * I + c * 8) = oa;
+        *reinterpret_cast<uint4*>(dh + t * 2 * I + I + c * 8) = ob;
+    }
+}
+
+// keep[i2, i1, i0] (one byte each) for counters c2 = i2, c1 = i1 and element i0 (c0 = i0 >> 3) of one (layer, site)
+__global__ __launch_bounds__(256) void dropout_keep_kernel(uint8_t* __restrict__ keep, int n2, int n1, int n0, uint64_t seed, uint32_t c3,
+                                                           uint32_t thr) {
+    const int n08 = (n0 + 7) / 8;
+    const int64_t n = (int64_t)n2 * n1 * n08;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+        const int64_t r = i / n08;
+        const int c0 = (int)(i - r * n08);
+        const uint32_t c1 = (uint32_t)(r % n1), c2 = (uint32_t)(r / n1);
+        const uint32_t m = cm3p_drop::keep8(seed, (uint32_t)c0, c1, c2, c3, thr);
+#pragma unroll
+        for (int j = 0; j < 8; ++j)
+            if (8 * c0 + j < n0) keep[r * n0 + 8 * c0 + j] = (uint8_t)((m >> j) & 1u);
+    }
+}
+
+DropArgs make_drop(int layer, int site, int thr, uint64_t seed, int S, const int* cu, int nseq) {
+    return DropArgs{seed, cm3p_drop::site_word(layer, (uint32_t)site), (uint32_t)thr, cm3p_drop::keep_scale((uint32_t)thr), S, nseq, cu};
 }
 
 __global__ __launch_bounds__(256) void gelu_fwd_kernel(const uint16_t* __restrict__ x, uint16_t* __restrict__ y, int64_t n8) {
@@ -504,6 +618,66 @@ int cm3p_geglu_bwd(const void* dg, const void* h, void* dh, int64_t T, int I, vo
     CM3P_LAUNCH_CHECK();
     return CM3P_OK;
 }
+
+// row layout of the dropout entries: padded rows of S positions (cu_seqlens null) or n_seqs packed sequences
+#define CM3P_DROP_REQUIRE()                                                                                                          \
+    CM3P_REQUIRE(thr >= 0 && thr <= 65536 && layer >= 0 && site >= 0 && site <= 3 && layer < (1 << 29));                          \
+    CM3P_REQUIRE(cu_seqlens ? n_seqs > 0 : S > 0)
+
+int cm3p_dropout_f32(const float* x, const float* resid, float* y_f32, void* y_bf16, int64_t rows, int H, int S, const int* cu_seqlens, int n_seqs,
+                     int layer, int site, int thr, uint64_t seed, void* stream) {
+    CM3P_REQUIRE(x && (y_f32 || y_bf16) && rows >= 0 && H > 0 && H % 8 == 0);
+    CM3P_REQUIRE(cm3p_aligned16(x) && cm3p_aligned16(resid) && cm3p_aligned16(y_f32) && cm3p_aligned16(y_bf16));
+    CM3P_DROP_REQUIRE();
+    if (rows == 0) return CM3P_OK;
+    dropout_f32_kernel<<<ew_grid(rows * (H / 8)), 256, 0, static_cast<hipStream_t>(stream)>>>(
+        x, resid, y_f32, (uint16_t*)y_bf16, rows, H, make_drop(layer, site, thr, seed, S, cu_seqlens, n_seqs));
+    CM3P_LAUNCH_CHECK();
+    return CM3P_OK;
+}
+
+int cm3p_geglu_fwd_dropout(const void* h, void* g, int64_t T, int I, int S, const int* cu_seqlens, int n_seqs, int layer, int thr,
+                           uint64_t seed, void* stream) {
+    const int site = cm3p_drop::kSiteMlp;
+    CM3P_REQUIRE(h && g && T >= 0 && I > 0 && I % 8 == 0 && cm3p_aligned16(h) && cm3p_aligned16(g));
+    CM3P_DROP_REQUIRE();
+    if (T == 0) return CM3P_OK;
+    geglu_drop_fwd_kernel<<<ew_grid(T * (I / 8)), 256, 0, static_cast<hipStream_t>(stream)>>>(
+        (const uint16_t*)h, (uint16_t*)g, T, I, make_drop(layer, site, thr, seed, S, cu_seqlens, n_seqs));
+    CM3P_LAUNCH_CHECK();
+    return CM3P_OK;
+}
+
+int cm3p_geglu_bwd_dropout(const void* dg, const void* h, void* dh, int64_t T, int I, int S, const int* cu_seqlens, int n_seqs, int layer,
+                           int thr, uint64_t seed, void* stream) {
+    const int site = cm3p_drop::kSiteMlp;
+    CM3P_REQUIRE(dg && h && dh && T >= 0 && I > 0 && I % 8 == 0 && cm3p_aligned16(dg) && cm3p_aligned16(h) && cm3p_aligned16(dh));
+    CM3P_DROP_REQUIRE();
+    if (T == 0) return CM3P_OK;
+    geglu_drop_bwd_kernel<<<ew_grid(T * (I / 8)), 256, 0, static_cast<hipStream_t>(stream)>>>(
+        (const uint16_t*)dg, (const uint16_t*)h, (uint16_t*)dh, T, I, make_drop(layer, site, thr, seed, S, cu_seqlens, n_seqs));
+    CM3P_LAUNCH_CHECK();
+    return CM3P_OK;
+}
+
+int cm3p_dropout_keep(uint8_t* keep, int n2, int n1, int n0, int layer, int site, int thr, uint64_t seed, void* stream) {
+    CM3P_REQUIRE(keep && n2 > 0 && n1 > 0 && n0 > 0 && thr >= 0 && thr <= 65536 && layer >= 0 && site >= 0 && site <= 3);
+    const int64_t items = (int64_t)n2 * n1 * ((n0 + 7) / 8);
+    dropout_keep_kernel<<<ew_grid(items), 256, 0, static_cast<hipStream_t>(stream)>>>(keep, n2, n1, n0, seed,
+                                                                                       cm3p_drop::site_word(layer, (uint32_t)site), (uint32_t)thr);
+    CM3P_LAUNCH_CHECK();
+    return CM3P_OK;
+}
+
+int cm3p_philox4x32_10_host(const uint32_t* ctr, const uint32_t* key, uint32_t* out, int64_t n) {
+    CM3P_REQUIRE(ctr && key && out && n >= 0);
+    for (int64_t i = 0; i < n; ++i) {
+        const cm3p_drop::U32x4 r = cm3p_drop::philox4x32_10(ctr[4 * i], ctr[4 * i + 1], ctr[4 * i + 2], ctr[4 * i + 3], key[2 * i], key[2 * i + 1]);
+        for (int j = 0; j < 4; ++j) out[4 * i + j] = r.w[j];
+    }
+    return CM3P_OK;
+}
+#undef CM3P_DROP_REQUIRE
 
 int cm3p_gelu_fwd(const void* x, void* y, int64_t n, void* stream) {
     CM3P_REQUIRE(x && y && n >= 0 && n % 8 == 0);

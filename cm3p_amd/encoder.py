@@ -15,6 +15,9 @@ TF:models/modernbert/modeling_modernbert.py:262-333,434-478:
 
 Numerics: the residual stream, LayerNorm statistics, softmax and all accumulations are fp32; GEMM operands and saved
 activations are bf16 (what HF Trainer's bf16 autocast gives the reference's nn.Linear calls).
+
+Dropout (training mode, p > 0): embedding output, attention probabilities (inside the attention kernels), attention output before
+the residual add, and gelu(h[:I]) * h[I:] before Wo - the masks follow csrc/dropout_rng.h from one seed per stack forward.
 """
 from __future__ import annotations
 
@@ -43,8 +46,9 @@ def _check_supported(cfg):
         if getattr(cfg, flag, False):
             problems.append(f"{flag}=True is not supported (the reference configs never set it)")
     for p in ("attention_dropout", "embedding_dropout", "mlp_dropout"):
-        if getattr(cfg, p, 0.0) != 0.0:
-            problems.append(f"{p} must be 0.0")
+        v = getattr(cfg, p, 0.0) or 0.0
+        if not 0.0 <= float(v) <= 1.0:  # nn.Dropout's own rule
+            raise ValueError(f"{p} has to be between 0 and 1, but got {v}")
     if cfg.intermediate_size % 8 or H % 8:
         problems.append("hidden_size and intermediate_size must be multiples of 8")
     if problems:
@@ -147,7 +151,7 @@ class _Geometry:
     """Static description of one forward call of the stack (no tensors that need grad)."""
 
     __slots__ = ("B", "S", "H", "I", "nh", "L", "eps", "windows", "key_mask", "rope", "per_batch_pos", "save", "cu", "max_s", "checkpoint",
-                 "handoff", "attn_out", "wcast", "hd")
+                 "handoff", "attn_out", "wcast", "hd", "drop")
 
 
 def _hand_upstream(geo: _Geometry, gx32: Tensor, gx16: Optional[Tensor]) -> None:
@@ -177,6 +181,8 @@ def _layer_forward(geo: _Geometry, i: int, x: Tensor, wb, want_stats: bool):
     B, S, nh = geo.B, geo.S, geo.nh
     scale = geo.hd ** -0.5
     cos, sin = geo.rope[i]
+    # attention dropout (probabilities and out_drop, TF:...modeling_modernbert.py:292,300): (thr, seed, layer), or None
+    ad = (geo.drop.attn, geo.drop.seed, i) if geo.drop is not None and geo.drop.attn else None
     if i == 0:
         xn, mean_a, rstd_a = K.cast_bf16(x), None, None
     else:
@@ -186,24 +192,30 @@ def _layer_forward(geo: _Geometry, i: int, x: Tensor, wb, want_stats: bool):
         # reference's order), attention on the generic kernels (csrc/attention_generic.hip); padded execution only
         qkv = K.linear_fwd(xn, Wqkv_b)
         K.rope_apply_generic_(qkv, cos, sin, B, S, nh, geo.hd, geo.per_batch_pos)
-        o, lse = K.attn_fwd_generic(qkv, geo.key_mask, B, S, nh, geo.hd, geo.windows[i], scale)
+        o, lse = K.attn_fwd_generic(qkv, geo.key_mask, B, S, nh, geo.hd, geo.windows[i], scale, drop=ad)
     # projection + RoPE in one kernel; the q third also takes the softmax's scale * log2(e) before its one bf16 rounding, so the
     # attention kernels exponentiate the MFMA's scores as they come (prescaled=True everywhere below)
     elif geo.cu is not None:  # unpadded batch: packed rows, per-token rotary tables
         qkv = K.qkv_linear_rope(xn, Wqkv_b, cos, sin, S, geo.per_batch_pos, q_scale=K.SOFTMAX_Q_SCALE)
-        o, lse = K.attn_fwd_varlen(qkv, geo.cu, B, geo.max_s, nh, geo.windows[i], scale, prescaled=True)
+        o, lse = K.attn_fwd_varlen(qkv, geo.cu, B, geo.max_s, nh, geo.windows[i], scale, prescaled=True, drop=ad)
     else:
         qkv = K.qkv_linear_rope(xn, Wqkv_b, cos, sin, S, geo.per_batch_pos, q_scale=K.SOFTMAX_Q_SCALE)
-        o, lse = K.attn_fwd(qkv, geo.key_mask, B, S, nh, geo.windows[i], scale, prescaled=True)
+        o, lse = K.attn_fwd(qkv, geo.key_mask, B, S, nh, geo.windows[i], scale, prescaled=True, drop=ad)
         if geo.attn_out is not None and len(geo.attn_out) == i:  # output_attentions (not again when a checkpointed layer is recomputed)
             geo.attn_out.append(K.attn_probs(qkv, lse, geo.key_mask, B, S, nh, geo.windows[i], scale, prescaled=True))
-    x_mid = K.linear_fwd(o, Wo_b, resid=x)
+    if ad is not None:  # out_drop: Wo writes fp32 t, then x_mid = x + Z o t
+        x_mid = K.dropout_f32(K.linear_fwd_f32(o, Wo_b), ad[0], ad[1], i, K.SITE_ATTN_OUT, geo.S, geo.cu, resid=x)
+    else:
+        x_mid = K.linear_fwd(o, Wo_b, resid=x)
     _, xn2, mean_m, rstd_m = K.layernorm_fwd(x_mid, w_mn, geo.eps, False, True, want_stats)
     if len(wb) > 6 and wb[6] is not None:  # forward-only call: Wi and GeGLU in one kernel, h and g never exist (bit-identical a)
         h, g = None, K.gemm_geglu(xn2, wb[6])
     else:
         h = K.linear_fwd(xn2, Wi_b)
-        g = K.geglu_fwd(h)
+        if geo.drop is not None and geo.drop.mlp:  # g o Z: what Wo and its weight gradient read (TF:...modeling_modernbert.py:91)
+            g = K.geglu_fwd_dropout(h, geo.drop.mlp, geo.drop.seed, i, geo.S, geo.cu)
+        else:
+            g = K.geglu_fwd(h)
     x_out = K.linear_fwd(g, Wo2_b, resid=x_mid)
     return x_out, (x, xn, mean_a, rstd_a, qkv, o, lse, x_mid, xn2, mean_m, rstd_m, h, g)
 
@@ -221,7 +233,7 @@ class _EncoderLayerFn(torch.autograd.Function):
         w_an = None if i == 0 else _f32(next(it))
         Wqkv, Wo, w_mn, Wi, Wo2 = next(it), next(it), _f32(next(it)), next(it), next(it)
         # forward-only and a shape of the ring kernel: the Wi GEMM stores gelu(h) * g itself (CM3P_GEGLU_FUSED=0: the two-kernel path)
-        fuse_geglu = (not geo.save) and Wi.dim() == 2 and K.gemm_geglu_supported(x.shape[0], Wi.shape[0] // 2, Wi.shape[1]) \
+        fuse_geglu = (not geo.save) and not (geo.drop is not None and geo.drop.mlp) and Wi.dim() == 2 and K.gemm_geglu_supported(x.shape[0], Wi.shape[0] // 2, Wi.shape[1]) \
             and os.environ.get("CM3P_GEGLU_FUSED", "1") != "0"
         # (training: the casts of every layer were made in one launch at the top of the stack, _run_stack)
         pre = geo.wcast if geo.save and geo.wcast is not None else {}
@@ -260,25 +272,31 @@ class _EncoderLayerFn(torch.autograd.Function):
         # ---- MLP branch: x_out = x_mid + g Wo2^T
         dg = K.linear_dgrad(gx16, Wo2_b, Wo2_t)
         dWo2 = K.linear_wgrad(gx16, g) if n_o2 else None
-        dh = K.geglu_bwd(dg, h)
+        if geo.drop is not None and geo.drop.mlp:
+            dh = K.geglu_bwd_dropout(dg, h, geo.drop.mlp, geo.drop.seed, i, geo.S, geo.cu)
+        else:
+            dh = K.geglu_bwd(dg, h)
         del dg, g
         dxn2 = K.linear_dgrad(dh, Wi_b, Wi_t)
         dWi = K.linear_wgrad(dh, xn2) if n_i else None
         del dh, h, xn2
         gx32, gx16, dw_mn = K.layernorm_bwd(dxn2, x_mid, w_mn, mean_m, rstd_m, gx32, True)
         del dxn2, x_mid
-        # ---- attention branch: x_mid = x + o Wo^T
-        do = K.linear_dgrad(gx16, Wo_b, Wo_t)
-        dWo = K.linear_wgrad(gx16, o) if n_o else None
+        # ---- attention branch: x_mid = x + o Wo^T  (with attention dropout: x + Z o (o Wo^T))
+        ad = (geo.drop.attn, geo.drop.seed, i) if geo.drop is not None and geo.drop.attn else None
+        gt16 = gx16 if ad is None else K.dropout_f32(gx32, ad[0], ad[1], i, K.SITE_ATTN_OUT, geo.S, geo.cu, bf16_only=True)
+        do = K.linear_dgrad(gt16, Wo_b, Wo_t)
+        dWo = K.linear_wgrad(gt16, o) if n_o else None
+        del gt16
         # attention backward; the inverse rotary rotation of dq / dk is applied in its epilogue
         if geo.hd != 64:
-            dqkv = K.attn_bwd_generic(qkv, o, do, lse, geo.key_mask, B, S, nh, geo.hd, geo.windows[i], scale)
+            dqkv = K.attn_bwd_generic(qkv, o, do, lse, geo.key_mask, B, S, nh, geo.hd, geo.windows[i], scale, drop=ad)
             K.rope_apply_generic_(dqkv, geo.rope[i][0], geo.rope[i][1], B, S, nh, geo.hd, geo.per_batch_pos, inverse=True)
         elif geo.cu is not None:
-            dqkv = K.attn_bwd_varlen(qkv, o, do, lse, geo.cu, B, geo.max_s, nh, geo.windows[i], scale, geo.rope[i], prescaled=True)
+            dqkv = K.attn_bwd_varlen(qkv, o, do, lse, geo.cu, B, geo.max_s, nh, geo.windows[i], scale, geo.rope[i], prescaled=True, drop=ad)
         else:
             dqkv = K.attn_bwd(qkv, o, do, lse, geo.key_mask, B, S, nh, geo.windows[i], scale, geo.rope[i], geo.per_batch_pos,
-                              prescaled=True)
+                              prescaled=True, drop=ad)
         del do, o, qkv
         dWqkv = K.linear_wgrad(dqkv, xn) if n_qkv else None
         if i == 0:
@@ -347,6 +365,30 @@ class _EmbedLNFn(torch.autograd.Function):
         return None, d_table, dw.to(wd), None, None, None, d_audio
 
 
+class _DropPlan:
+    """The dropout of one stack forward in training mode: one seed (regenerates every mask in the backward and in a checkpointed
+    recompute) and the thresholds round(p * 65536) of the live sites (0: site off)."""
+
+    __slots__ = ("seed", "embedding", "attn", "mlp")
+
+    def __init__(self, seed: int, embedding: int, attn: int, mlp: int):
+        self.seed, self.embedding, self.attn, self.mlp = seed, embedding, attn, mlp
+
+
+class _EmbedDropFn(torch.autograd.Function):
+    """ModernBertEmbeddings.drop (TF:...modeling_modernbert.py:70) on [rows, H] fp32: x o Z; backward dy o Z (same mask)."""
+
+    @staticmethod
+    def forward(ctx, x: Tensor, plan: _DropPlan, S: int, cu: Optional[Tensor]):
+        ctx.args = (plan.embedding, plan.seed, S, cu)
+        return K.dropout_f32(x.contiguous(), plan.embedding, plan.seed, 0, K.SITE_EMBED, S, cu)
+
+    @staticmethod
+    def backward(ctx, dy: Tensor):
+        thr, seed, S, cu = ctx.args
+        return K.dropout_f32(dy.float().contiguous(), thr, seed, 0, K.SITE_EMBED, S, cu), None, None, None
+
+
 class _PadRowsFn(torch.autograd.Function):
     """Packed rows -> padded [rows, H] with zeros at the padding positions (ref:cm3p/modeling_cm3p.py:106-134 _pad_cm3p_output);
     backward gathers the rows back."""
@@ -413,6 +455,27 @@ class CM3PEncoder(nn.Module):
             invalidate_weight_cache()  # HF Trainer flips the mode around every evaluation: copies never cross a train/eval boundary
         return super().train(mode)
 
+    def _dropout_plan(self) -> Optional[_DropPlan]:
+        """-> the dropout of this call, or None: eval mode or every p = 0 (then the launch sequence is exactly the dropout-free one).
+        The seed comes from torch's default CPU generator (torch.manual_seed / transformers' set_seed make runs reproducible): a
+        host draw, no device sync."""
+        cfg = self.config
+        p_emb, p_attn, p_mlp = (float(getattr(cfg, n, 0.0) or 0.0) for n in ("embedding_dropout", "attention_dropout", "mlp_dropout"))
+        if not self.training or (p_emb == 0.0 and p_attn == 0.0 and p_mlp == 0.0):
+            return None
+        _check_supported(cfg)  # (the fields are read per call: a value set after construction is held to the same rules)
+        if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
+            raise NotImplementedError("dropout in training mode inside a CUDA-graph capture: the host-drawn seed would be frozen into the graph")
+        seed = int(torch.randint(-(2 ** 63), 2 ** 63 - 1, (), dtype=torch.int64)) & (2 ** 64 - 1)
+        thr = [K.dropout_threshold(p) if p > 0.0 else 0 for p in (p_emb, p_attn, p_mlp)]
+        return _DropPlan(seed, *thr)
+
+    @staticmethod
+    def _embed_dropout(x0: Tensor, plan: Optional[_DropPlan], S: int, cu: Optional[Tensor]) -> Tensor:
+        if plan is None or not plan.embedding:
+            return x0
+        return _EmbedDropFn.apply(x0, plan, S, cu)
+
     def get_input_embeddings(self):
         return self.embeddings.tok_embeddings
 
@@ -459,10 +522,13 @@ class CM3PEncoder(nn.Module):
             if output_attentions:
                 raise NotImplementedError("output_attentions needs head_dim 64")
             unpad = False
+        plan = self._dropout_plan()  # (before any launch: a refused graph capture has captured nothing)
+        if output_attentions and plan is not None and plan.attn:
+            raise NotImplementedError("output_attentions with attention dropout in training mode (the kernels return undropped probabilities)")
         if cu_seqlens is not None:
             if output_attentions:
                 raise NotImplementedError("output_attentions with unpadded inputs: attention probabilities are (B, nh, S, S) tensors of a padded batch")
-            return self._forward_prepacked(input_ids, position_ids, audio_slot, audio_rows, cu_seqlens, max_seqlen, output_hidden_states)
+            return self._forward_prepacked(input_ids, position_ids, audio_slot, audio_rows, cu_seqlens, max_seqlen, output_hidden_states, plan)
         if output_attentions:
             unpad = False  # the probabilities are laid out per padded (batch, head, query, key)
         if input_ids is not None and input_ids.dtype != torch.int64:
@@ -498,7 +564,8 @@ class CM3PEncoder(nn.Module):
         else:
             x0 = _LayerNormFn.apply(inputs_embeds.reshape(B * S, H), self.embeddings.norm.weight, cfg.norm_eps)
 
-        y, hiddens, attns = self._run_stack(x0, B, S, attention_mask, position_ids, packed, output_hidden_states, dev, output_attentions)
+        x0 = self._embed_dropout(x0, plan, S, packed[1] if packed is not None else None)
+        y, hiddens, attns = self._run_stack(x0, B, S, attention_mask, position_ids, packed, output_hidden_states, dev, output_attentions, plan)
         if hiddens is not None:
             if packed is not None:
                 hiddens = [K.scatter_rows(h[:n_valid].contiguous(), idx, B * S) for h in hiddens]
@@ -511,8 +578,9 @@ class CM3PEncoder(nn.Module):
         return (y, hiddens) if output_hidden_states else y
 
     def _run_stack(self, x0: Tensor, B: int, S: int, attention_mask, position_ids, packed, output_hidden_states: bool, dev,
-                   output_attentions: bool = False):
-        """The L encoder layers + final norm on [rows, H]; `packed` = (idx, cu, max_s, n_valid, n_rows, pos) for unpadded execution."""
+                   output_attentions: bool = False, plan: Optional[_DropPlan] = None):
+        """The L encoder layers + final norm on [rows, H]; `packed` = (idx, cu, max_s, n_valid, n_rows, pos) for unpadded execution;
+        `plan`: the call's dropout (None: none)."""
         cfg = self.config
         H = cfg.hidden_size
         geo = _Geometry()
@@ -523,6 +591,7 @@ class CM3PEncoder(nn.Module):
         geo.key_mask = None
         geo.cu = None
         geo.checkpoint = bool(self.gradient_checkpointing and self.training)
+        geo.drop = plan
         geo.max_s = S
         if packed is not None:
             idx, cu, max_s, n_valid, n_rows, pos = packed
@@ -573,7 +642,7 @@ class CM3PEncoder(nn.Module):
         return y, hiddens, attns
 
     def _forward_prepacked(self, input_ids: Tensor, position_ids: Optional[Tensor], audio_slot, audio_rows, cu_seqlens: Tensor,
-                           max_seqlen: Optional[int], output_hidden_states: bool):
+                           max_seqlen: Optional[int], output_hidden_states: bool, plan: Optional[_DropPlan] = None):
         """Caller-supplied unpadded inputs (ref:cm3p/modeling_cm3p.py:911-931 when `indices` / `cu_seqlens` / `max_seqlen` are given;
         the layout of _unpad_cm3p_input, :65-104): input_ids (total,), cu_seqlens (batch + 1,) -> last_hidden_state (total, H),
         NOT re-padded (the reference's encoder leaves caller-packed rows packed as well)."""
@@ -614,7 +683,8 @@ class CM3PEncoder(nn.Module):
         x0 = _EmbedLNFn.apply(ids, self.embeddings.tok_embeddings.weight, self.embeddings.norm.weight, cfg.norm_eps,
                               -1 if pad is None else pad, None if slot_p is None else slot_p.contiguous(), audio_rows)
         packed = (None, cu, max(max_s, n_rows - total), total, n_rows, pos.contiguous())
-        y, hiddens, _ = self._run_stack(x0, cu.numel() - 1, max_s, None, None, packed, output_hidden_states, dev)
+        x0 = self._embed_dropout(x0, plan, max_s, cu)
+        y, hiddens, _ = self._run_stack(x0, cu.numel() - 1, max_s, None, None, packed, output_hidden_states, dev, plan=plan)
         if n_rows != total:
             y = y[:total]
             if hiddens is not None:

@@ -4,6 +4,7 @@ No autograd here and no torch compute ops: everything numerical happens inside l
 """
 from __future__ import annotations
 
+import math
 import os
 from typing import Optional
 
@@ -191,6 +192,12 @@ def linear_fwd(x: Tensor, w: Tensor, resid: Optional[Tensor] = None) -> Tensor:
     return gemm(x, w, T, N, K, True, True, EPI_F32_RESID if resid is not None else EPI_BF16, resid)
 
 
+def linear_fwd_f32(x: Tensor, w: Tensor) -> Tensor:
+    """x [T,K] bf16, w [N,K] bf16 -> x w^T as fp32 (the attention output projection when out_drop follows it)."""
+    T, K = x.shape
+    return gemm(x, w, T, w.shape[0], K, True, True, EPI_F32, None)
+
+
 SOFTMAX_Q_SCALE = 64 ** -0.5 * 1.4426950408889634  # scale * log2(e) for head_dim 64: what q_prescaled attention expects in q
 
 
@@ -307,11 +314,19 @@ def _attn_fwd_name(window: int, prescaled: bool, masked: bool, S: int, nh: int) 
     return "attn_fwd_kernel<1, %s, " + ("true>" if window >= 0 else "false>")
 
 
-def attn_fwd(qkv: Tensor, key_mask: Optional[Tensor], B: int, S: int, nh: int, window: int, scale: float, prescaled: bool = False):
-    """prescaled: the q third already carries scale * log2(e) (qkv_linear_rope(..., q_scale=SOFTMAX_Q_SCALE))."""
+def attn_fwd(qkv: Tensor, key_mask: Optional[Tensor], B: int, S: int, nh: int, window: int, scale: float, prescaled: bool = False,
+             drop: Optional[tuple] = None):
+    """prescaled: the q third already carries scale * log2(e) (qkv_linear_rope(..., q_scale=SOFTMAX_Q_SCALE)).
+    drop = (thr, seed, layer): attention-probability dropout (the band kernels at every window)."""
     out = torch.empty((B * S, nh * 64), dtype=torch.bfloat16, device=qkv.device)
     lse = torch.empty((B, nh, S), dtype=torch.float32, device=qkv.device)
     keys = S if window < 0 else min(S, 2 * window + 1)
+    if drop is not None:
+        thr, seed, layer = drop
+        call("cm3p_attn_fwd_dropout", ptr(qkv), ptr(out), ptr(lse, torch.float32), ptr(key_mask, torch.uint8), B, S, nh, window, scale, int(prescaled),
+             layer, thr, seed, stream(), tag=_attn_tag("attn_fwd_kernel<1, %s, " + ("true" if window >= 0 else "false") + ", DropCfg>", window, prescaled),
+             work=4.0 * B * nh * S * keys * 64)
+        return out, lse
     call("cm3p_attn_fwd", ptr(qkv), ptr(out), ptr(lse, torch.float32), ptr(key_mask, torch.uint8), B, S, nh, window, scale, int(prescaled), stream(),
          tag=_attn_tag(_attn_fwd_name(window, prescaled, key_mask is not None, S, nh), window, prescaled), work=4.0 * B * nh * S * keys * 64)
     return out, lse
@@ -327,18 +342,30 @@ def rope_apply_generic_(qkv: Tensor, cos: Tensor, sin: Tensor, B: int, S: int, n
     return qkv
 
 
-def attn_fwd_generic(qkv: Tensor, key_mask: Optional[Tensor], B: int, S: int, nh: int, hd: int, window: int, scale: float):
+def attn_fwd_generic(qkv: Tensor, key_mask: Optional[Tensor], B: int, S: int, nh: int, hd: int, window: int, scale: float,
+                     drop: Optional[tuple] = None):
+    """drop = (thr, seed, layer): attention-probability dropout (the rule of attn_fwd's)."""
     out = torch.empty((B * S, nh * hd), dtype=torch.bfloat16, device=qkv.device)
     lse = torch.empty((B, nh, S), dtype=torch.float32, device=qkv.device)
+    if drop is not None:
+        thr, seed, layer = drop
+        call("cm3p_attn_fwd_generic_dropout", ptr(qkv, torch.bfloat16), ptr(out), ptr(lse, torch.float32), ptr(key_mask, torch.uint8), B, S, nh, hd,
+             window, scale, layer, thr, seed, stream())
+        return out, lse
     call("cm3p_attn_fwd_generic", ptr(qkv, torch.bfloat16), ptr(out), ptr(lse, torch.float32), ptr(key_mask, torch.uint8), B, S, nh, hd, window, scale, stream())
     return out, lse
 
 
 def attn_bwd_generic(qkv: Tensor, out: Tensor, dout: Tensor, lse: Tensor, key_mask: Optional[Tensor], B: int, S: int, nh: int, hd: int,
-                     window: int, scale: float) -> Tensor:
+                     window: int, scale: float, drop: Optional[tuple] = None) -> Tensor:
     """-> dqkv with the q / k thirds still in the ROTATED frame (rope_apply_generic_(..., inverse=True) finishes them)."""
     dqkv = torch.empty_like(qkv)
     delta = torch.empty_like(lse)
+    if drop is not None:
+        thr, seed, layer = drop
+        call("cm3p_attn_bwd_generic_dropout", ptr(qkv, torch.bfloat16), ptr(out, torch.bfloat16), ptr(dout, torch.bfloat16), ptr(lse, torch.float32),
+             ptr(delta), ptr(dqkv), ptr(key_mask, torch.uint8), B, S, nh, hd, window, scale, layer, thr, seed, stream())
+        return dqkv
     call("cm3p_attn_bwd_generic", ptr(qkv, torch.bfloat16), ptr(out, torch.bfloat16), ptr(dout, torch.bfloat16), ptr(lse, torch.float32), ptr(delta), ptr(dqkv),
          ptr(key_mask, torch.uint8), B, S, nh, hd, window, scale, stream())
     return dqkv
@@ -411,12 +438,23 @@ def _attn_bwd_fused(qkv, out, dout, lse, key_mask, cu, B, S, total, nh, scale, r
 
 
 def attn_bwd(qkv: Tensor, out: Tensor, dout: Tensor, lse: Tensor, key_mask: Optional[Tensor], B: int, S: int, nh: int,
-             window: int, scale: float, rope: Optional[tuple] = None, per_batch: bool = False, prescaled: bool = False) -> Tensor:
+             window: int, scale: float, rope: Optional[tuple] = None, per_batch: bool = False, prescaled: bool = False,
+             drop: Optional[tuple] = None) -> Tensor:
     """rope = (cos, sin): also applies the inverse rotary rotation to dq / dk (backward of the fused Wqkv+RoPE GEMM).
     Global layers (window < 0) run the five-product kernel of csrc/attention_bwd_fused.hip; sliding-window layers the band kernels
     of csrc/attention.hip, issued as two C calls so that each has its own profiler tag (one rocprof row per tag).  `work` is the
     algorithmic count of SURVEY.md section 8(d) (backward = 2 x forward = four matmuls: dQ is the dq kernel's, dP / dV / dK the
     dkv kernel's); the scores each kernel recomputes are not credited."""
+    if drop is not None:
+        thr, seed, layer = drop
+        dqkv = torch.empty_like(qkv)
+        delta = torch.empty_like(lse)
+        cos, sin = rope if rope is not None else (None, None)
+        for stage, name in ((ATTN_BWD_DQ, "attn_bwd_dq_drop_kernel<%s>"), (ATTN_BWD_DKV, "attn_bwd_dkv_drop_kernel<%s>")):
+            call("cm3p_attn_bwd_dropout", ptr(qkv), ptr(out), ptr(dout), ptr(lse, torch.float32), ptr(delta), ptr(dqkv), ptr(key_mask, torch.uint8), B, S,
+                 nh, window, scale, ptr(cos, torch.float32), ptr(sin, torch.float32), S if per_batch else 0, stage, int(prescaled), layer, thr, seed,
+                 stream(), tag=_attn_tag(name, window, prescaled))
+        return dqkv
     if window < 0:
         return _attn_bwd_fused(qkv, out, dout, lse, key_mask, None, B, S, 0, nh, scale, rope, per_batch, prescaled)
     dqkv = torch.empty_like(qkv)
@@ -430,19 +468,36 @@ def attn_bwd(qkv: Tensor, out: Tensor, dout: Tensor, lse: Tensor, key_mask: Opti
     return dqkv
 
 
-def attn_fwd_varlen(qkv: Tensor, cu: Tensor, B: int, max_s: int, nh: int, window: int, scale: float, prescaled: bool = False):
+def attn_fwd_varlen(qkv: Tensor, cu: Tensor, B: int, max_s: int, nh: int, window: int, scale: float, prescaled: bool = False,
+                    drop: Optional[tuple] = None):
     """Packed sequences: qkv [total, 3, nh, 64], cu int32 [B+1] -> out [total, nh*64], lse [nh, total]."""
     total = qkv.shape[0]
     out = torch.empty((total, nh * 64), dtype=torch.bfloat16, device=qkv.device)
     lse = torch.empty((nh, total), dtype=torch.float32, device=qkv.device)
+    if drop is not None:
+        thr, seed, layer = drop
+        call("cm3p_attn_fwd_dropout_varlen", ptr(qkv), ptr(out), ptr(lse, torch.float32), ptr(cu, torch.int32), B, max_s, total, nh, window, scale,
+             int(prescaled), layer, thr, seed, stream(),
+             tag=_attn_tag("attn_fwd_kernel<1, %s, " + ("true" if window >= 0 else "false") + ", DropCfg>", window, prescaled, True))
+        return out, lse
     call("cm3p_attn_fwd_varlen", ptr(qkv), ptr(out), ptr(lse, torch.float32), ptr(cu, torch.int32), B, max_s, total, nh, window, scale, int(prescaled), stream(),
          tag=_attn_tag(_attn_fwd_name(window, prescaled, False, max_s, nh), window, prescaled, True))
     return out, lse
 
 
 def attn_bwd_varlen(qkv: Tensor, out: Tensor, dout: Tensor, lse: Tensor, cu: Tensor, B: int, max_s: int, nh: int, window: int,
-                    scale: float, rope: Optional[tuple] = None, prescaled: bool = False) -> Tensor:
+                    scale: float, rope: Optional[tuple] = None, prescaled: bool = False, drop: Optional[tuple] = None) -> Tensor:
     """rope = (cos, sin) per packed token [total, 32]: also applies the inverse rotation to dq / dk."""
+    if drop is not None:
+        thr, seed, layer = drop
+        dqkv = torch.empty_like(qkv)
+        delta = torch.empty_like(lse)
+        cos, sin = rope if rope is not None else (None, None)
+        for stage, name in ((ATTN_BWD_DQ, "attn_bwd_dq_drop_kernel<%s>"), (ATTN_BWD_DKV, "attn_bwd_dkv_drop_kernel<%s>")):
+            call("cm3p_attn_bwd_dropout_varlen", ptr(qkv), ptr(out), ptr(dout), ptr(lse, torch.float32), ptr(delta), ptr(dqkv), ptr(cu, torch.int32), B,
+                 max_s, qkv.shape[0], nh, window, scale, ptr(cos, torch.float32), ptr(sin, torch.float32), stage, int(prescaled), layer, thr, seed,
+                 stream(), tag=_attn_tag(name, window, prescaled, True))
+        return dqkv
     if window < 0:
         return _attn_bwd_fused(qkv, out, dout, lse, None, cu, B, max_s, qkv.shape[0], nh, scale, rope, False, prescaled)
     dqkv = torch.empty_like(qkv)
@@ -504,6 +559,69 @@ def geglu_bwd(dg: Tensor, h: Tensor) -> Tensor:
     dh = torch.empty_like(h)
     call("cm3p_geglu_bwd", ptr(dg), ptr(h), ptr(dh), h.shape[0], h.shape[1] // 2, stream(), work=10.0 * h.shape[0] * (h.shape[1] // 2))
     return dh
+
+
+# ------------------------------------------------------------------------------------------------ dropout (csrc/dropout_rng.h)
+SITE_EMBED, SITE_ATTN_PROBS, SITE_ATTN_OUT, SITE_MLP = 0, 1, 2, 3
+
+
+def dropout_threshold(p: float) -> int:
+    """thr = round(p * 65536) of the RNG contract: an element is kept iff its 16-bit draw is >= thr."""
+    return int(math.floor(float(p) * 65536.0 + 0.5))
+
+
+def dropout_scale(thr: int) -> float:
+    """The survivors' factor 65536 / (65536 - thr) as the kernels hold it (fp32); 0 when nothing survives."""
+    return 0.0 if thr >= 65536 else float(torch.tensor(65536.0) / torch.tensor(float(65536 - thr)))
+
+
+def _drop_rows(S: int, cu: Optional[Tensor]):
+    """Row layout arguments of the element sites: padded rows of S positions, or the packed batch of cu_seqlens."""
+    return (S, None, 0) if cu is None else (S, ptr(cu, torch.int32), cu.numel() - 1)
+
+
+def dropout_f32(x: Tensor, thr: int, seed: int, layer: int, site: int, S: int, cu: Optional[Tensor] = None, resid: Optional[Tensor] = None,
+                bf16_only: bool = False) -> Tensor:
+    """[resid +] x o Z on [rows, H] fp32 (also the backward: dy o Z); bf16_only: the bf16 result alone (a GEMM operand)."""
+    rows, H = x.shape
+    y = torch.empty(x.shape, dtype=torch.bfloat16 if bf16_only else torch.float32, device=x.device)
+    call("cm3p_dropout_f32", ptr(x, torch.float32), ptr(resid, torch.float32), None if bf16_only else ptr(y), ptr(y) if bf16_only else None, rows, H,
+         *_drop_rows(S, cu), layer, site, thr, seed, stream())
+    return y
+
+
+def geglu_fwd_dropout(h: Tensor, thr: int, seed: int, layer: int, S: int, cu: Optional[Tensor] = None) -> Tensor:
+    T, I2 = h.shape
+    g = torch.empty((T, I2 // 2), dtype=torch.bfloat16, device=h.device)
+    call("cm3p_geglu_fwd_dropout", ptr(h, torch.bfloat16), ptr(g), T, I2 // 2, *_drop_rows(S, cu), layer, thr, seed, stream())
+    return g
+
+
+def geglu_bwd_dropout(dg: Tensor, h: Tensor, thr: int, seed: int, layer: int, S: int, cu: Optional[Tensor] = None) -> Tensor:
+    dh = torch.empty_like(h)
+    call("cm3p_geglu_bwd_dropout", ptr(dg, torch.bfloat16), ptr(h, torch.bfloat16), ptr(dh), h.shape[0], h.shape[1] // 2, *_drop_rows(S, cu),
+         layer, thr, seed, stream())
+    return dh
+
+
+def dropout_keep(n2: int, n1: int, n0: int, layer: int, site: int, thr: int, seed: int, device) -> Tensor:
+    """The contract's keep mask (uint8 [n2, n1, n0]) of one (layer, site): element sites (sequences, positions, features)."""
+    keep = torch.empty((n2, n1, n0), dtype=torch.uint8, device=device)
+    call("cm3p_dropout_keep", ptr(keep), n2, n1, n0, layer, site, thr, seed, stream())
+    return keep
+
+
+def philox4x32_10_host(ctr, key):
+    """Philox4x32-10 on the host (no GPU): ctr uint32 [n, 4], key uint32 [n, 2] (numpy) -> uint32 [n, 4]."""
+    import numpy as np
+
+    c = np.ascontiguousarray(ctr, dtype=np.uint32).reshape(-1, 4)
+    k = np.ascontiguousarray(key, dtype=np.uint32).reshape(-1, 2)
+    if c.shape[0] != k.shape[0]:
+        raise ValueError("one key per counter")
+    out = np.empty_like(c)
+    _lib._check(query("cm3p_philox4x32_10_host", c.ctypes.data, k.ctypes.data, out.ctypes.data, c.shape[0]), "cm3p_philox4x32_10_host")
+    return out
 
 
 def gelu_fwd(x: Tensor) -> Tensor:

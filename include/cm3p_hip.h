@@ -31,7 +31,7 @@ extern "C" {
 #define CM3P_BF16 1
 
 /* ABI version of this header; cm3p_abi_version() must return it. */
-#define CM3P_ABI_VERSION 16
+#define CM3P_ABI_VERSION 17
 int cm3p_abi_version(void);
 
 /* ---------------------------------------------------------------------------------------------------------------
@@ -244,6 +244,14 @@ int cm3p_attn_fwd_generic(const void* qkv, void* out, float* lse, const uint8_t*
                           float scale, void* stream);
 int cm3p_attn_bwd_generic(const void* qkv, const void* out, const void* dout, const float* lse, float* delta, void* dqkv,
                           const uint8_t* key_mask, int B, int S, int nh, int head_dim, int window, float scale, void* stream);
+/* Attention-probability dropout on the generic kernels (TF:models/modernbert/modeling_modernbert.py:181 eager, :292 sdpa dropout_p): the
+ * rule and the decisions of cm3p_attn_fwd_dropout / cm3p_attn_bwd_dropout (dropout contract below, site 1), arguments as the two entries
+ * above plus layer, thr, seed. */
+int cm3p_attn_fwd_generic_dropout(const void* qkv, void* out, float* lse, const uint8_t* key_mask, int B, int S, int nh, int head_dim,
+                                  int window, float scale, int layer, int thr, uint64_t seed, void* stream);
+int cm3p_attn_bwd_generic_dropout(const void* qkv, const void* out, const void* dout, const float* lse, float* delta, void* dqkv,
+                                  const uint8_t* key_mask, int B, int S, int nh, int head_dim, int window, float scale, int layer, int thr,
+                                  uint64_t seed, void* stream);
 int cm3p_rope_apply_generic(void* qkv, const float* cos_tab, const float* sin_tab, int B, int S, int nh, int head_dim, int64_t pos_batch_stride,
                             int inverse, void* stream);
 
@@ -275,6 +283,24 @@ int cm3p_attn_bwd_fused(const void* qkv, const void* out, const void* dout, cons
                         const float* sin_tab, int64_t pos_batch_stride, int stages, int q_prescaled, void* workspace,
                         int64_t workspace_bytes, void* stream);
 
+/* Attention-probability dropout (softmax(...) -> nn.functional.dropout at TF:models/modernbert/modeling_modernbert.py:181 eager,
+ * :292 sdpa dropout_p; site 1 of the dropout contract below, cm3p_amd/csrc/dropout_rng.h: counter (key >> 3, query, b * nh + h,
+ * 4 * layer + 1)).  Arguments as cm3p_attn_fwd / cm3p_attn_bwd / their _varlen twins plus layer, thr, seed.  Every window runs the band
+ * kernels (global layers at window -1); out = (P o Z) V, lse unchanged; the backward regenerates Z: dV = (P o Z)^T dO,
+ * dS = P o (Z o dP - delta) with delta = rowsum(dO o O). */
+int cm3p_attn_fwd_dropout(const void* qkv, void* out, float* lse, const uint8_t* key_mask, int B, int S, int nh, int window, float scale,
+                          int q_prescaled, int layer, int thr, uint64_t seed, void* stream);
+int cm3p_attn_bwd_dropout(const void* qkv, const void* out, const void* dout, const float* lse, float* delta, void* dqkv,
+                          const uint8_t* key_mask, int B, int S, int nh, int window, float scale, const float* cos_tab,
+                          const float* sin_tab, int64_t pos_batch_stride, int stages, int q_prescaled, int layer, int thr, uint64_t seed,
+                          void* stream);
+int cm3p_attn_fwd_dropout_varlen(const void* qkv, void* out, float* lse, const int* cu_seqlens, int B, int max_seqlen, int64_t total, int nh,
+                                 int window, float scale, int q_prescaled, int layer, int thr, uint64_t seed, void* stream);
+int cm3p_attn_bwd_dropout_varlen(const void* qkv, const void* out, const void* dout, const float* lse, float* delta, void* dqkv,
+                                 const int* cu_seqlens, int B, int max_seqlen, int64_t total, int nh, int window, float scale,
+                                 const float* cos_tab, const float* sin_tab, int stages, int q_prescaled, int layer, int thr, uint64_t seed,
+                                 void* stream);
+
 /* ---------------------------------------------------------------------------------------------------------------
  * GeGLU: g = gelu_erf(h[:, :I]) * h[:, I:]   (ModernBertMLP.forward, TF:...modeling_modernbert.py:89-91).
  * h: [T, 2I] bf16, g: [T, I] bf16; I % 8 == 0.  Backward: dh from dg and h.
@@ -291,6 +317,33 @@ int cm3p_geglu_fwd(const void* h, void* g, int64_t T, int I, void* stream);
  * anything else is CM3P_ERR_INVALID and the caller keeps the two-kernel path. */
 int cm3p_gemm_geglu(const void* x, const void* w_interleaved, void* a, int64_t T, int64_t I, int64_t K, void* stream);
 int cm3p_geglu_bwd(const void* dg, const void* h, void* dh, int64_t T, int I, void* stream);
+/* ---------------------------------------------------------------------------------------------------------------
+ * Dropout (nn.Dropout in training mode): keep with probability 1 - p, scale the survivors by 1 / (1 - p).  Every decision follows the
+ * contract of cm3p_amd/csrc/dropout_rng.h: Philox4x32-10 keyed by the 64-bit `seed`, counter (feature >> 3, position s in its
+ * sequence, sequence b, 4 * layer + site), 8 decisions per call, kept iff the 16-bit draw >= thr; thr = round(p * 65536) in
+ * [0, 65536], scale 65536 / (65536 - thr) (0 when thr = 65536).  Sites: 0 embedding (layer 0), 1 attention probabilities,
+ * 2 attention output, 3 MLP.
+ * Row layout of the element sites: cu_seqlens NULL -> padded rows of S positions (b = row / S); else cu_seqlens [n_seqs + 1] of a
+ * packed batch (b = the sequence holding the row, s = row - cu_seqlens[b]), so packed and padded rows of one token decide alike.
+ *
+ * y = resid + x o Z on [rows, H] fp32, H % 8 == 0, resid may be NULL; y_f32 (may alias x) and/or the bf16 twin y_bf16.
+ * Replaces ModernBertEmbeddings.drop (TF:models/modernbert/modeling_modernbert.py:70, site 0) and the residual add after
+ * ModernBertAttention.out_drop (TF:...modeling_modernbert.py:260,300,331, site 2: x_mid = x + Z o (attn Wo^T)); the backward
+ * (dx = dy o Z) is the same call without resid. */
+int cm3p_dropout_f32(const float* x, const float* resid, float* y_f32, void* y_bf16, int64_t rows, int H, int S, const int* cu_seqlens,
+                     int n_seqs, int layer, int site, int thr, uint64_t seed, void* stream);
+/* GeGLU followed by ModernBertMLP.drop (TF:...modeling_modernbert.py:86,91): g = bf16((gelu_erf(h[:, :I]) * h[:, I:]) o Z), site 3;
+ * the backward takes dg o Z into the GeGLU derivative.  Shapes as cm3p_geglu_fwd / cm3p_geglu_bwd, rows as cm3p_dropout_f32. */
+int cm3p_geglu_fwd_dropout(const void* h, void* g, int64_t T, int I, int S, const int* cu_seqlens, int n_seqs, int layer, int thr,
+                           uint64_t seed, void* stream);
+int cm3p_geglu_bwd_dropout(const void* dg, const void* h, void* dh, int64_t T, int I, int S, const int* cu_seqlens, int n_seqs, int layer,
+                           int thr, uint64_t seed, void* stream);
+/* Materialiser of the contract: keep[i2, i1, i0] = 1 / 0 (uint8) for counters c2 = i2, c1 = i1, element i0 of one (layer, site).
+ * Element sites: (n2, n1, n0) = (sequences, positions, features); attention probabilities: (B * nh, queries, keys). */
+int cm3p_dropout_keep(uint8_t* keep, int n2, int n1, int n0, int layer, int site, int thr, uint64_t seed, void* stream);
+/* Host-only (no GPU needed): Philox4x32-10 of n counters ctr [n, 4] under keys key [n, 2] -> out [n, 4], host pointers. */
+int cm3p_philox4x32_10_host(const uint32_t* ctr, const uint32_t* key, uint32_t* out, int64_t n);
+
 /* y = gelu_erf(x) elementwise on bf16, and dx = dy * gelu'(x)  (nn.functional.gelu at ref:cm3p/modeling_cm3p.py:478,501-502). */
 int cm3p_gelu_fwd(const void* x, void* y, int64_t n, void* stream);
 int cm3p_gelu_bwd(const void* dy, const void* x, void* dx, int64_t n, void* stream);
