@@ -1005,6 +1005,24 @@ class _PointwiseLossFn(torch.autograd.Function):
         return K.scale_by(ctx.dx, g.reshape(1).contiguous()), None, None
 
 
+class _MaskedCrossEntropyFn(torch.autograd.Function):
+    """CrossEntropyLoss() of the single-label classifier (ref:cm3p/modeling_cm3p.py:1214-1216): rows labelled -100 (the default
+    ignore_index) get no loss and no gradient, and the mean is over the labelled rows only.  A batch without a labelled row gives
+    loss 0 and a zero gradient (torch returns NaN there; the masked-LM loss makes the same choice, inv_valid_count's max(n, 1))."""
+
+    @staticmethod
+    def forward(ctx, logits: Tensor, target: Tensor):
+        x = logits.detach().contiguous()
+        inv = K.inv_valid_count(target, -100)
+        loss_rows, dx = K.cross_entropy_masked(x, x.shape[1], target, -100, 1.0, inv, True)
+        ctx.dx = dx
+        return K.scale_by(K.sum_f32(loss_rows, 1.0), inv).reshape(())
+
+    @staticmethod
+    def backward(ctx, g: Tensor):
+        return K.scale_by(ctx.dx, g.reshape(1).contiguous()), None
+
+
 @dataclass
 class BeatmapClassifierOutput(ModelOutput):
     loss: Optional[torch.FloatTensor] = None
@@ -1053,9 +1071,7 @@ class CM3PForBeatmapClassification(CM3PPreTrainedModel):
             if self.config.problem_type == "regression":
                 loss = _PointwiseLossFn.apply(logits.reshape(-1), labels.reshape(-1), 0)
             elif self.config.problem_type == "single_label_classification":
-                n = logits.shape[0]
-                spec = [(0, n, self.num_labels, self.num_labels, 1, None, labels.reshape(-1).to(torch.int64).contiguous(), 1.0)]
-                loss = _CrossEntropySumFn.apply(spec, logits)
+                loss = _MaskedCrossEntropyFn.apply(logits, labels.reshape(-1).to(torch.int64).contiguous())
             else:
                 loss = _PointwiseLossFn.apply(logits.reshape(-1), labels.reshape(-1), 1)
         return BeatmapClassifierOutput(loss=loss, logits=logits, hidden_states=out.hidden_states, attentions=out.attentions)

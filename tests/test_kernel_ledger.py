@@ -1,0 +1,146 @@
+"""Which test checks each C-ABI entry point against a reference.  Every function include/cm3p_hip.h declares is either in LEDGER,
+with the test functions that compare its results with a reference restatement (node ids without parameters), or in EXEMPT with the
+reason it has none (host-side size queries, ablation and audit hooks).  A new entry point cannot land without one or the other.
+No GPU needed: the tests named here are found by parsing their files."""
+import ast
+import os
+import re
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+HEADER = os.path.join(ROOT, "include", "cm3p_hip.h")
+
+KG = "tests/test_kernels_gpu.py::"
+CH = "tests/test_conv_head_kernels_gpu.py::"
+DR = "tests/test_dropout_gpu.py::"
+MU = "tests/test_muon_gpu.py::"
+MG = "tests/test_model_gpu.py::"
+
+LEDGER = {
+    "cm3p_layernorm_fwd": [KG + "test_layernorm_fwd_bwd", CH + "test_layernorm_with_many_rows_per_wave"],
+    "cm3p_layernorm_bwd": [KG + "test_layernorm_fwd_bwd", CH + "test_layernorm_with_many_rows_per_wave"],
+    "cm3p_embed_ln_fwd": [KG + "test_embed_ln_with_audio_override"],
+    "cm3p_embed_ln_bwd": [KG + "test_embed_ln_with_audio_override"],
+    "cm3p_embed_ln_bwd_sorted": [KG + "test_embed_ln_with_audio_override", KG + "test_embedding_backward_in_id_order_is_reproducible_and_matches_autograd"],
+    "cm3p_token_order": [KG + "test_token_order_is_the_stable_sort_of_the_ids"],
+    "cm3p_audio_slots": [KG + "test_embed_ln_with_audio_override"],
+    "cm3p_gemm_bf16": [KG + "test_gemm_forward_layout", KG + "test_gemm_dgrad_layout", KG + "test_gemm_wgrad_layout",
+                       KG + "test_gemm256_forward_and_dgrad_layout", KG + "test_gemm256_wgrad_layout", KG + "test_gemm_bias_epilogue"],
+    "cm3p_gemm8p_set_grid": [KG + "test_ring_gemm_with_more_workgroups_than_cus_is_the_same_gemm"],
+    "cm3p_gemm8p_get_grid": [KG + "test_ring_gemm_with_more_workgroups_than_cus_is_the_same_gemm"],
+    "cm3p_qkv_gemm_rope": [KG + "test_fused_qkv_rope_gemm_and_inverse_in_attention_backward"],
+    "cm3p_cast_f32_bf16": [CH + "test_cast_f32_bf16_is_rne"],
+    "cm3p_cast_f32_bf16_t": [KG + "test_cast_with_transpose"],
+    "cm3p_cast_f32_bf16_t_multi": [KG + "test_cast_with_transpose_of_many_matrices_in_one_launch"],
+    "cm3p_add_f32": [CH + "test_add_f32_is_the_fp32_add_then_rne", CH + "test_add_f32_with_no_elements"],
+    "cm3p_rope_table": [KG + "test_rope_matches_reference_formula"],
+    "cm3p_rope_apply": [KG + "test_rope_matches_reference_formula"],
+    "cm3p_attn_fwd": [KG + "test_attention_global_nopad", KG + "test_attention_random_shapes", KG + "test_attention_sliding_window"],
+    "cm3p_attn_probs": [MG + "test_output_attentions_matches_the_reference_eager_probabilities"],
+    "cm3p_attn_bwd": [KG + "test_attention_global_backward_both_implementations", KG + "test_attention_random_shapes"],
+    "cm3p_attn_fwd_generic": [KG + "test_generic_attention_matches_fp32_reference"],
+    "cm3p_attn_bwd_generic": [KG + "test_generic_attention_matches_fp32_reference"],
+    "cm3p_attn_fwd_generic_dropout": [DR + "test_generic_attention_dropout_matches_fp32_restatement"],
+    "cm3p_attn_bwd_generic_dropout": [DR + "test_generic_attention_dropout_matches_fp32_restatement"],
+    "cm3p_rope_apply_generic": [KG + "test_generic_rope_is_the_reference_rotation_and_its_transpose"],
+    "cm3p_attn_bwd_fused": [KG + "test_attention_global_backward_both_implementations"],
+    "cm3p_attn_fwd_dropout": [DR + "test_attention_dropout_matches_fp32_restatement"],
+    "cm3p_attn_bwd_dropout": [DR + "test_attention_dropout_matches_fp32_restatement"],
+    "cm3p_attn_fwd_dropout_varlen": [DR + "test_attention_dropout_varlen_equals_padded"],
+    "cm3p_attn_bwd_dropout_varlen": [DR + "test_attention_dropout_varlen_equals_padded"],
+    "cm3p_geglu_fwd": [KG + "test_geglu_and_gelu"],
+    "cm3p_gemm_geglu": [KG + "test_wi_gemm_with_geglu_in_its_store_phase_equals_the_two_kernels"],
+    "cm3p_geglu_bwd": [KG + "test_geglu_and_gelu"],
+    "cm3p_dropout_f32": [DR + "test_dropout_f32_matches_the_mask_and_packed_equals_padded"],
+    "cm3p_geglu_fwd_dropout": [DR + "test_geglu_dropout_forward_and_backward"],
+    "cm3p_geglu_bwd_dropout": [DR + "test_geglu_dropout_forward_and_backward"],
+    "cm3p_dropout_keep": [DR + "test_materialiser_equals_the_restatement"],
+    "cm3p_philox4x32_10_host": ["tests/test_dropout_host.py::test_philox_known_answers", "tests/test_dropout_host.py::test_philox_matches_python_restatement"],
+    "cm3p_gelu_fwd": [KG + "test_gelu_on_every_finite_bf16_input_against_float64"],
+    "cm3p_gelu_bwd": [KG + "test_gelu_on_every_finite_bf16_input_against_float64"],
+    "cm3p_im2col_k3": [CH + "test_im2col_is_the_padded_gather_bit_for_bit", CH + "test_conv_front_end_refuses_what_it_cannot_do"],
+    "cm3p_col2im_k3": [CH + "test_col2im_is_the_ordered_sum_and_the_adjoint_of_im2col", CH + "test_conv_gelu_stages_against_float64"],
+    "cm3p_bias_gelu_fwd": [CH + "test_bias_gelu_forward_against_float64", CH + "test_conv_gelu_stages_against_float64"],
+    "cm3p_bias_gelu_bwd": [CH + "test_bias_gelu_backward_against_float64"],
+    "cm3p_pool_fwd": [KG + "test_pooling"],
+    "cm3p_pool_bwd": [KG + "test_pooling"],
+    "cm3p_gemm_f32": [CH + "test_gemm_f32_all_stride_forms", KG + "test_head_kernels"],
+    "cm3p_l2norm_fwd": [KG + "test_head_kernels"],
+    "cm3p_l2norm_bwd": [KG + "test_head_kernels"],
+    "cm3p_cross_entropy": [CH + "test_cross_entropy_with_the_specs_of_the_contrastive_loss", KG + "test_head_kernels"],
+    "cm3p_scale_exp": [CH + "test_scale_exp_dot_and_sum_against_float64"],
+    "cm3p_scale_by": [KG + "test_masked_lm_loss_kernels", CH + "test_cross_entropy_masked_against_float64"],
+    "cm3p_dot_f32": [CH + "test_scale_exp_dot_and_sum_against_float64"],
+    "cm3p_sum_f32": [CH + "test_scale_exp_dot_and_sum_against_float64", KG + "test_masked_lm_loss_kernels"],
+    "cm3p_cross_entropy_masked": [CH + "test_cross_entropy_masked_against_float64", CH + "test_single_label_classifier_ignores_minus_100_rows"],
+    "cm3p_inv_valid_count": [KG + "test_masked_lm_loss_kernels"],
+    "cm3p_ce_masked_stats": [KG + "test_masked_lm_loss_kernels"],
+    "cm3p_ce_masked_dlogits_bf16": [KG + "test_masked_lm_loss_kernels"],
+    "cm3p_add_bias_f32": [CH + "test_add_bias_is_the_fp32_add_bit_for_bit"],
+    "cm3p_colsum_f32": [CH + "test_colsum_against_float64"],
+    "cm3p_pointwise_loss": [CH + "test_pointwise_loss_against_float64"],
+    "cm3p_first_zero_index": [KG + "test_head_kernels"],
+    "cm3p_attn_fwd_varlen": [KG + "test_attention_varlen_equals_padded_on_valid_rows"],
+    "cm3p_attn_bwd_varlen": [KG + "test_attention_varlen_equals_padded_on_valid_rows"],
+    "cm3p_gather_rows_f32": [KG + "test_gather_scatter_rows"],
+    "cm3p_scatter_rows_f32": [KG + "test_gather_scatter_rows"],
+    "cm3p_gemm_bf16_batched": [MU + "test_batched_gemm_axpby"],
+    "cm3p_muon_partials": [MU + "test_steps_match_the_reference_fixture", MU + "test_model_sized_group_against_the_oracle"],
+    "cm3p_muon_momentum": [MU + "test_steps_match_the_reference_fixture", MU + "test_model_sized_group_against_the_oracle"],
+    "cm3p_muon_normalize": [MU + "test_steps_match_the_reference_fixture", MU + "test_model_sized_group_against_the_oracle"],
+    "cm3p_muon_apply": [MU + "test_steps_match_the_reference_fixture", MU + "test_model_sized_group_against_the_oracle"],
+    "cm3p_adamw_multi": [MU + "test_steps_match_the_reference_fixture"],
+}
+
+EXEMPT = {
+    "cm3p_abi_version": "host query: the header's version number (tests/test_cabi.py compares it with the binding)",
+    "cm3p_layernorm_bwd_blocks": "host query: workspace rows of cm3p_layernorm_bwd",
+    "cm3p_embed_ln_bwd_sorted_chunk": "host query: the id-order backward's chunk size",
+    "cm3p_token_order_workspace_ints": "host query: workspace size of cm3p_token_order",
+    "cm3p_gemm_wgrad_splits": "host query: split-K factor the wrapper picks",
+    "cm3p_build_ablation_flags": "ablation hook: tests/test_cabi.py and _lib.load() require 0 from a product library",
+    "cm3p_debug_set_dma_audit": "audit hook of the debug twin (tests/test_dma_audit_gpu.py)",
+    "cm3p_attn_fwd_impl": "host query: which forward kernel a shape takes",
+    "cm3p_attn_generic_supported": "host query: head dims the generic kernels take",
+    "cm3p_attn_bwd_fused_workspace_bytes": "host query: workspace size of cm3p_attn_bwd_fused",
+    "cm3p_attn_bwd_fused_slab_group": "host query: slab grouping of cm3p_attn_bwd_fused",
+    "cm3p_bias_gelu_bwd_blocks": "host query: partial rows of cm3p_bias_gelu_bwd",
+    "cm3p_pool_chunks": "host query: workspace size of cm3p_pool_fwd",
+    "cm3p_ce_masked_dlogits_blocks": "host query: partial rows of cm3p_ce_masked_dlogits_bf16",
+    "cm3p_colsum_blocks": "host query: partial rows of cm3p_colsum_f32",
+}
+
+
+def _declared():
+    """The same parse as tests/test_cabi.py::_declared."""
+    text = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
+    return set(re.findall(r"\b(?:int|int64_t)\s+(cm3p_[a-z0-9_]+)\s*\(", text))
+
+
+def _test_functions(relpath):
+    tree = ast.parse(open(os.path.join(ROOT, relpath)).read())
+    return {n.name for n in tree.body if isinstance(n, ast.FunctionDef) and n.name.startswith("test_")}
+
+
+def test_every_declared_entry_point_is_in_the_ledger_or_exempt():
+    declared = _declared()
+    covered = set(LEDGER) | set(EXEMPT)
+    assert not declared - covered, f"entry points with neither a test nor an exemption: {sorted(declared - covered)}"
+    assert not covered - declared, f"ledger names no longer in the header: {sorted(covered - declared)}"
+
+
+def test_ledger_and_exempt_are_disjoint_and_nonempty():
+    assert not set(LEDGER) & set(EXEMPT), sorted(set(LEDGER) & set(EXEMPT))
+    assert all(LEDGER.values()) and all(r.strip() for r in EXEMPT.values())
+
+
+def test_every_named_test_exists():
+    cache = {}
+    missing = []
+    for name, ids in LEDGER.items():
+        for node in ids:
+            path, func = node.split("::")
+            if path not in cache:
+                cache[path] = _test_functions(path) if os.path.exists(os.path.join(ROOT, path)) else set()
+            if func not in cache[path]:
+                missing.append((name, node))
+    assert not missing, missing

@@ -1,4 +1,5 @@
-"""Per-kernel parity tests: every C-ABI entry point against a torch fp32 CPU restatement of the same op.
+"""Per-kernel parity tests: C-ABI entry points against a torch fp32 CPU restatement of the same op (tests/test_kernel_ledger.py maps
+every entry point to the tests that check it).
 
 Run on the GPU box: python -m pytest tests -m gpu.  bf16 inputs are rounded first and handed to both sides, so the
 tolerances below only cover accumulation order and the final rounding of the output dtype (stated per test).
