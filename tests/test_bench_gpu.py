@@ -13,7 +13,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_bench_prints_one_json_line_with_the_contract_keys():
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--batch", "2"],
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--batch", "2", "--full"],
                        capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [l for l in p.stdout.splitlines() if l.strip()]
@@ -32,6 +32,24 @@ def test_bench_prints_one_json_line_with_the_contract_keys():
     assert abs(r["frac"] - r["achieved"] / r["peak"]) < 1e-9 and ("traffic" in r)
     c = d["cpu_baseline"]
     assert c["kind"] in ("port", "reference") and c["cores"] >= 1 and c["value"] > 0 and isinstance(c["sample"], str) and c["unit"] == "pairs/s"
+
+
+def test_bench_plain_run_prints_the_headline_line_only():
+    """Without --full the run sets up, warms up, times its steps and prints the same contract keys - and nothing that needs a run of
+    its own (per-kernel profile, optimizer step, C4 leg, CPU baseline)."""
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--batch", "2"],
+                       capture_output=True, text=True, timeout=900, cwd=ROOT)
+    assert p.returncode == 0, p.stderr[-2000:]
+    lines = [l for l in p.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1, lines
+    d = json.loads(lines[0])
+    for k, t in (("metric", str), ("value", float), ("unit", str), ("n_gpus", int), ("steps", int), ("warmup", int), ("ms_per_step", float),
+                 ("higher_is_better", bool), ("scaling", str), ("dtype", str), ("data", str), ("config", dict)):
+        assert isinstance(d[k], t), (k, d.get(k))
+    assert d["n_gpus"] == 1 and d["steps"] == 2 and d["warmup"] == 1 and d["higher_is_better"] is True and d["dtype"] == "bf16"
+    assert d["value"] > 0 and abs(d["value"] - 2 * 1e3 / d["ms_per_step"]) <= 1e-6 * d["value"]
+    for k in ("roofline", "kernel_breakdown_ms_per_step", "hbm_kernels", "optimizer_step", "secondary", "cpu_baseline", "comm", "replicas"):
+        assert k not in d, k
 
 
 def test_bench_dumps_the_last_timed_step_the_same_on_every_run(tmp_path):
@@ -66,7 +84,7 @@ def test_bench_two_ranks_share_the_card_over_gloo():
     env = dict(os.environ, CM3P_BENCH_BACKEND="gloo", MASTER_ADDR="127.0.0.1")
     p = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                         "--master-port", "29541", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "2",
-                        "--no-optimizer", "--diagnose"], capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
+                        "--no-optimizer", "--diagnose", "--full"], capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [l for l in p.stdout.splitlines() if l.strip().startswith("{")]
     assert len(lines) == 1, lines
@@ -115,7 +133,7 @@ def test_bench_prints_the_judged_line_when_a_diagnostic_never_returns():
     """The deadline around the N > 1 diagnostics: with it at 0 s rank 0 prints the judged line - complete before any diagnostic
     collective started - and leaves; the line carries everything the contract names and says why `comm` is short."""
     p = _torchrun(2, dict(CM3P_BENCH_BACKEND="gloo", CM3P_BENCH_DIAG_DEADLINE_S="0", CM3P_BENCH_PG_TIMEOUT_S="60"),
-                  "--steps", "1", "--warmup", "1", "--batch", "2", "--no-optimizer", port="29551")
+                  "--steps", "1", "--warmup", "1", "--batch", "2", "--no-optimizer", "--full", port="29551")
     lines = [l for l in p.stdout.splitlines() if l.strip().startswith("{")]
     assert len(lines) == 1, (lines, p.stderr[-2000:])
     d = json.loads(lines[0])
@@ -145,7 +163,7 @@ def test_bench_two_ranks_over_rccl_when_the_box_has_two_gpus():
 
     if torch.cuda.device_count() < 2:
         pytest.skip("needs two GPUs")
-    p = _torchrun(2, {}, "--steps", "2", "--warmup", "1", "--batch", "4", "--no-optimizer", port="29547")
+    p = _torchrun(2, {}, "--steps", "2", "--warmup", "1", "--batch", "4", "--no-optimizer", "--full", port="29547")
     assert p.returncode == 0, p.stderr[-3000:]
     d = json.loads([l for l in p.stdout.splitlines() if l.strip().startswith("{")][0])
     assert d["n_gpus"] == 2 and d["config"]["global_batch"] == 8 and d["replicas"]["identical_on_all_ranks"] is True

@@ -6,7 +6,7 @@ R=$(pwd)
 O=$R/gpurun_out/small_$WL
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O -o out -- python3 $R/bench.py --workload $WL --steps 5 --warmup 2 --no-cpu-baseline --no-optimizer --no-secondary > $O/log 2>&1
+timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O -o out -- python3 $R/bench.py --workload $WL --steps 5 --warmup 2 --no-cpu-baseline --no-optimizer --no-secondary --full > $O/log 2>&1
 cd $R
 python3 - <<PY
 import csv, re
