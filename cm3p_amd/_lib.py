@@ -13,8 +13,8 @@ from ctypes import c_float, c_int, c_int64, c_uint64, c_void_p
 import torch
 
 F32, BF16 = 0, 1
-EPI_BF16, EPI_F32, EPI_F32_RESID, EPI_F32_BIAS = 0, 1, 2, 5
-ABI_VERSION = 17
+EPI_BF16, EPI_F32, EPI_F32_RESID, EPI_F32_BIAS, EPI_BF16_RESID = 0, 1, 2, 5, 7
+ABI_VERSION = 18
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("CM3P_HIP_LIB") or os.path.join(_HERE, "csrc", "libcm3p_hip.so")  # env override: kernel experiments
@@ -78,7 +78,7 @@ SIGNATURES = {
     "cm3p_bias_gelu_bwd_blocks": [_L],
     "cm3p_bias_gelu_bwd": [_P, _I, _P, _P, _P, _P, _P, _L, _I, _P],
     "cm3p_pool_chunks": [_I],
-    "cm3p_pool_fwd": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P],
+    "cm3p_pool_fwd": [_P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _P],
     "cm3p_pool_bwd": [_P, _P, _P, _P, _I, _I, _I, _I, _P],
     "cm3p_gemm_f32": [_P, _P, _P, _I, _I, _I, _L, _L, _L, _L, _L, _F, _I, _P],
     "cm3p_l2norm_fwd": [_P, _P, _P, _I, _I, _P],

@@ -68,7 +68,9 @@ class _ProjectorFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, h: Tensor, W1: Tensor, W2: Tensor):
-        hb = K.cast_bf16(h.detach().contiguous())
+        hb = h.detach().contiguous()
+        if hb.dtype != torch.bfloat16:  # (rows of the bf16 residual stream are the GEMM operand as they are)
+            hb = K.cast_bf16(hb)
         W1b, W2b = _bf16_weight(W1), _bf16_weight(W2)
         z1 = K.linear_fwd(hb, W1b)
         a1 = K.gelu_fwd(z1)

@@ -21,6 +21,7 @@ typedef __attribute__((ext_vector_type(16))) float f32x16;
 #define CM3P_EPI_BF16_AXPBY 4  // internal: bf16 output = alpha * acc + beta * Rb (cm3p_gemm_bf16_batched)
 // 5 = CM3P_EPI_F32_BIAS (public, include/cm3p_hip.h)
 #define CM3P_EPI_BF16_GEGLU 6  // internal (cm3p_gemm_geglu): every 64 output columns are [32 h | 32 g]; stores gelu_erf(h) * g, 32 columns
+// 7 = CM3P_EPI_BF16_RESID (public, include/cm3p_hip.h)
 
 // Strided-batch offsets (elements) and the AXPBY epilogue operands of the 128 x 128 GEMM kernel.
 struct BatchArgs {
@@ -242,6 +243,8 @@ __device__ __forceinline__ uint32_t pack_bf16x2(float lo, float hi) {
 }
 __device__ __forceinline__ float bf16lo(uint32_t w) { return __builtin_bit_cast(float, w << 16); }
 __device__ __forceinline__ float bf16hi(uint32_t w) { return __builtin_bit_cast(float, w & 0xffff0000u); }
+// bf16 + bf16 of two packed pairs, added in fp32 and rounded once (torch's bf16 add): the CM3P_EPI_BF16_RESID epilogues
+__device__ __forceinline__ uint32_t add_bf16x2(uint32_t a, uint32_t b) { return pack_bf16x2(bf16lo(a) + bf16lo(b), bf16hi(a) + bf16hi(b)); }
 
 // Rotary tables for epilogue fusion: cos/sin are [n_pos, 32] fp32; a token row m uses table row (per_batch ? m : m % S);
 // only the first `ncols` output columns (the q and k thirds of a packed qkv row) are rotated.

@@ -448,8 +448,20 @@ __global__ __launch_bounds__(256) void gelu_bwd_kernel(const uint16_t* __restric
 // ---- pooling ------------------------------------------------------------------------------------------------
 constexpr int kPoolChunk = 128;
 
-// partial[b, c, :] = sum over the 128 rows of chunk c of h[b, s, :] * m[b, s]
-__global__ __launch_bounds__(256) void pool_partial_kernel(const float* __restrict__ h, const int64_t* __restrict__ mask,
+// four consecutive elements of an fp32 or bf16 row, widened to fp32 (the bf16 residual stream of forward-only calls)
+template <typename T>
+__device__ __forceinline__ f32x4 load4_f32(const T* p);
+template <>
+__device__ __forceinline__ f32x4 load4_f32<float>(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
+template <>
+__device__ __forceinline__ f32x4 load4_f32<uint16_t>(const uint16_t* p) {
+    const uint2 w = *reinterpret_cast<const uint2*>(p);
+    return f32x4{bf16lo(w.x), bf16hi(w.x), bf16lo(w.y), bf16hi(w.y)};
+}
+
+// partial[b, c, :] = sum over the 128 rows of chunk c of h[b, s, :] * m[b, s]  (fp32 accumulation whatever the row dtype)
+template <typename T>
+__global__ __launch_bounds__(256) void pool_partial_kernel(const T* __restrict__ h, const int64_t* __restrict__ mask,
                                                            float* __restrict__ partial, int S, int H, int nchunks) {
     const int b = blockIdx.x / nchunks, c = blockIdx.x % nchunks;
     const int s0 = c * kPoolChunk, s1 = min(S, s0 + kPoolChunk);
@@ -457,7 +469,7 @@ __global__ __launch_bounds__(256) void pool_partial_kernel(const float* __restri
         f32x4 acc = {0.f, 0.f, 0.f, 0.f};
         for (int s = s0; s < s1; ++s) {
             const float m = mask ? (float)mask[(int64_t)b * S + s] : 1.0f;
-            acc += *reinterpret_cast<const f32x4*>(h + ((int64_t)b * S + s) * H + col) * m;
+            acc += load4_f32(h + ((int64_t)b * S + s) * H + col) * m;
         }
         *reinterpret_cast<f32x4*>(partial + ((int64_t)b * nchunks + c) * H + col) = acc;
     }
@@ -487,9 +499,13 @@ __global__ __launch_bounds__(256) void pool_final_kernel(const float* __restrict
     }
 }
 
-__global__ __launch_bounds__(256) void pool_cls_kernel(const float* __restrict__ h, float* __restrict__ pooled, int S, int H) {
+__device__ __forceinline__ float to_f32(float x) { return x; }
+__device__ __forceinline__ float to_f32(uint16_t x) { return bf16_bits_to_f32(x); }
+
+template <typename T>
+__global__ __launch_bounds__(256) void pool_cls_kernel(const T* __restrict__ h, float* __restrict__ pooled, int S, int H) {
     const int b = blockIdx.x;
-    for (int col = threadIdx.x; col < H; col += 256) pooled[(int64_t)b * H + col] = h[(int64_t)b * S * H + col];
+    for (int col = threadIdx.x; col < H; col += 256) pooled[(int64_t)b * H + col] = to_f32(h[(int64_t)b * S * H + col]);
 }
 
 __global__ __launch_bounds__(256) void pool_bwd_kernel(const float* __restrict__ dpooled, const int64_t* __restrict__ mask,
@@ -698,16 +714,20 @@ int cm3p_gelu_bwd(const void* dy, const void* x, void* dx, int64_t n, void* stre
 
 int cm3p_pool_chunks(int S) { return (S + kPoolChunk - 1) / kPoolChunk; }
 
-int cm3p_pool_fwd(const float* h, const int64_t* mask, float* pooled, float* partial, float* count, int Bn, int S, int H,
+int cm3p_pool_fwd(const void* h, int h_dtype, const int64_t* mask, float* pooled, float* partial, float* count, int Bn, int S, int H,
                   int cls, void* stream) {
-    CM3P_REQUIRE(h && pooled && Bn > 0 && S > 0 && H > 0 && H % 4 == 0);
+    CM3P_REQUIRE(h && pooled && Bn > 0 && S > 0 && H > 0 && H % 4 == 0 && (h_dtype == CM3P_F32 || h_dtype == CM3P_BF16));
+    CM3P_REQUIRE(cls || h_dtype == CM3P_F32 || reinterpret_cast<uintptr_t>(h) % 8 == 0);  // (bf16 rows: 8-byte loads of 4 columns)
     hipStream_t s = static_cast<hipStream_t>(stream);
+    const bool bf = h_dtype == CM3P_BF16;
     if (cls) {
-        pool_cls_kernel<<<Bn, 256, 0, s>>>(h, pooled, S, H);
+        if (bf) pool_cls_kernel<<<Bn, 256, 0, s>>>(static_cast<const uint16_t*>(h), pooled, S, H);
+        else pool_cls_kernel<<<Bn, 256, 0, s>>>(static_cast<const float*>(h), pooled, S, H);
     } else {
         CM3P_REQUIRE(partial);
         const int nch = cm3p_pool_chunks(S);
-        pool_partial_kernel<<<Bn * nch, 256, 0, s>>>(h, mask, partial, S, H, nch);
+        if (bf) pool_partial_kernel<<<Bn * nch, 256, 0, s>>>(static_cast<const uint16_t*>(h), mask, partial, S, H, nch);
+        else pool_partial_kernel<<<Bn * nch, 256, 0, s>>>(static_cast<const float*>(h), mask, partial, S, H, nch);
         CM3P_LAUNCH_CHECK();
         pool_final_kernel<<<Bn, 256, 0, s>>>(partial, mask, pooled, count, S, H, nch);
     }

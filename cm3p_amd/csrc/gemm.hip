@@ -190,6 +190,11 @@ __global__ __launch_bounds__(256, 2) void gemm_bf16_kernel(const uint16_t* A, co
             if constexpr (EPI == CM3P_EPI_BF16 || EPI == CM3P_EPI_BF16_ROPE) {
                 uint16_t* C = static_cast<uint16_t*>(Cv);
                 *reinterpret_cast<uint2*>(C + m * ldc + n) = uint2{pack_bf16x2(v.x, v.y), pack_bf16x2(v.z, v.w)};
+            } else if constexpr (EPI == CM3P_EPI_BF16_RESID) {
+                // C = bf16(bf16(acc) + Rb), Rb bf16 with C's layout (may alias C): a bf16 projection, then torch's bf16 add
+                uint16_t* C = static_cast<uint16_t*>(Cv);
+                const uint2 r = *reinterpret_cast<const uint2*>(reinterpret_cast<const uint16_t*>(R) + m * ldc + n);
+                *reinterpret_cast<uint2*>(C + m * ldc + n) = uint2{add_bf16x2(pack_bf16x2(v.x, v.y), r.x), add_bf16x2(pack_bf16x2(v.z, v.w), r.y)};
             } else if constexpr (EPI == CM3P_EPI_BF16_AXPBY) {
                 // C = bf16(alpha * acc + beta * Rb), Rb bf16 with C's layout (the Newton-Schulz polynomial steps)
                 uint16_t* C = static_cast<uint16_t*>(Cv) + (int64_t)blockIdx.y * bt.c_stride;
@@ -237,6 +242,9 @@ int launch(const void* A, const void* B, void* C, const float* R, int64_t M, int
             break;
         case CM3P_EPI_F32_RESID:
             gemm_bf16_kernel<A_KC, B_KC, CM3P_EPI_F32_RESID><<<grid, 256, lds, s>>>(a, b, C, R, M, N, K, lda, ldb, ldc, tiles_n, kchunk, c_split_stride, rope, bt);
+            break;
+        case CM3P_EPI_BF16_RESID:
+            gemm_bf16_kernel<A_KC, B_KC, CM3P_EPI_BF16_RESID><<<grid, 256, lds, s>>>(a, b, C, R, M, N, K, lda, ldb, ldc, tiles_n, kchunk, c_split_stride, rope, bt);
             break;
         case CM3P_EPI_BF16_ROPE:
             if constexpr (A_KC && B_KC) {
@@ -369,13 +377,15 @@ int cm3p_qkv_gemm_rope(const void* x, const void* Wqkv, void* qkv, int64_t M, in
 int cm3p_gemm_bf16(const void* A, const void* B, void* C, const float* R, int64_t M, int64_t N, int64_t K, int64_t lda,
                    int64_t ldb, int64_t ldc, int a_kc, int b_kc, int epilogue, int split_k, float* workspace, void* stream) {
     CM3P_REQUIRE(A && B && C && M > 0 && N > 0 && K > 0);
-    CM3P_REQUIRE((epilogue >= CM3P_EPI_BF16 && epilogue <= CM3P_EPI_F32_RESID) || (epilogue == CM3P_EPI_F32_BIAS && a_kc && b_kc));
+    CM3P_REQUIRE((epilogue >= CM3P_EPI_BF16 && epilogue <= CM3P_EPI_F32_RESID) || (epilogue == CM3P_EPI_F32_BIAS && a_kc && b_kc) ||
+                 epilogue == CM3P_EPI_BF16_RESID);
     CM3P_REQUIRE(cm3p_aligned16(A) && cm3p_aligned16(B) && cm3p_aligned16(C));
     CM3P_REQUIRE(lda % 8 == 0 && ldb % 8 == 0 && ldc % 4 == 0 && N % 4 == 0);
     CM3P_REQUIRE(a_kc ? (K % 8 == 0 && lda >= K) : (M % 8 == 0 && lda >= M));
     CM3P_REQUIRE(b_kc ? (K % 8 == 0 && ldb >= K) : (N % 8 == 0 && ldb >= N));
     CM3P_REQUIRE(ldc >= N && (epilogue != CM3P_EPI_BF16 || ldc % 8 == 0 || ldc % 4 == 0));
-    CM3P_REQUIRE((epilogue != CM3P_EPI_F32_RESID && epilogue != CM3P_EPI_F32_BIAS) || (R && cm3p_aligned16(R)));
+    CM3P_REQUIRE((epilogue != CM3P_EPI_F32_RESID && epilogue != CM3P_EPI_F32_BIAS && epilogue != CM3P_EPI_BF16_RESID) || (R && cm3p_aligned16(R)));
+    CM3P_REQUIRE(epilogue != CM3P_EPI_BF16_RESID || (N % 8 == 0 && ldc % 8 == 0));  // (16-byte bf16 row chunks in the 256 x 256 kernels)
     CM3P_REQUIRE(split_k >= 1 && (split_k == 1 || (epilogue == CM3P_EPI_F32 && workspace && cm3p_aligned16(workspace) && ldc == N)));
     hipStream_t s = static_cast<hipStream_t>(stream);
     int64_t kchunk = K;

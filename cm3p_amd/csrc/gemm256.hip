@@ -265,7 +265,7 @@ __global__ __launch_bounds__(kThreads, kWN == 4 ? 2 : 1) void gemm256_kernel(con
         // (a lane owns 4 consecutive n of one m; storing that directly issues 32 partial-line stores per lane and is
         //  store-issue bound.)  `stage` now holds the next item's first k-tile (if any); the other 64 KiB are free.
         char* ebuf = smem + (stage ^ 1) * kStage;
-        if constexpr (EPI == CM3P_EPI_BF16 || EPI == CM3P_EPI_BF16_ROPE) {
+        if constexpr (EPI == CM3P_EPI_BF16 || EPI == CM3P_EPI_BF16_ROPE || EPI == CM3P_EPI_BF16_RESID) {
             constexpr int kRow = TN * 2 + 16;  // padded row pitch (bytes): 16 rows of one column land on different banks
             uint16_t* C = static_cast<uint16_t*>(Cv);
 #pragma unroll
@@ -323,7 +323,14 @@ __global__ __launch_bounds__(kThreads, kWN == 4 ? 2 : 1) void gemm256_kernel(con
                     for (int u = 0; u < kItems; ++u) {
                         const int id = tid + kThreads * u, r = id >> 5, ch = id & 31;
                         const int64_t m = m0 + pass * 64 + r, n = n0 + ch * 8;
-                        if (m < M && n < N) *reinterpret_cast<uint4*>(C + m * ldc + n) = *reinterpret_cast<const uint4*>(ebuf + r * kRow + ch * 16);
+                        if (m < M && n < N) {
+                            uint4 x = *reinterpret_cast<const uint4*>(ebuf + r * kRow + ch * 16);
+                            if constexpr (EPI == CM3P_EPI_BF16_RESID) {  // C = bf16(bf16(acc) + Rb), Rb bf16 with C's layout (may alias C)
+                                const uint4 rb = *reinterpret_cast<const uint4*>(reinterpret_cast<const uint16_t*>(R) + m * ldc + n);
+                                x = uint4{add_bf16x2(x.x, rb.x), add_bf16x2(x.y, rb.y), add_bf16x2(x.z, rb.z), add_bf16x2(x.w, rb.w)};
+                            }
+                            *reinterpret_cast<uint4*>(C + m * ldc + n) = x;
+                        }
                     }
                 }
                 lds_barrier();
@@ -418,6 +425,7 @@ int launch256(const uint16_t* a, const uint16_t* b, void* C, const float* R, int
         case CM3P_EPI_BF16: CM3P_G256(CM3P_EPI_BF16) break;
         case CM3P_EPI_F32: CM3P_G256(CM3P_EPI_F32) break;
         case CM3P_EPI_F32_RESID: CM3P_G256(CM3P_EPI_F32_RESID) break;
+        case CM3P_EPI_BF16_RESID: CM3P_G256(CM3P_EPI_BF16_RESID) break;
         case CM3P_EPI_BF16_ROPE:
             if constexpr (A_KC && B_KC) {
                 CM3P_G256(CM3P_EPI_BF16_ROPE)

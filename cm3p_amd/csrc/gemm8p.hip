@@ -370,9 +370,11 @@ __global__ __launch_bounds__(512, 2) void gemm8p_kernel(const uint16_t* __restri
             for (int i = 0; i < 8; ++i)
 #pragma unroll
                 for (int j = 0; j < 4; ++j) asm volatile("" ::"v"(acc[i][j]));
-        } else if constexpr (EPI == CM3P_EPI_BF16 || EPI == CM3P_EPI_BF16_ROPE) {
+        } else if constexpr (EPI == CM3P_EPI_BF16 || EPI == CM3P_EPI_BF16_ROPE || EPI == CM3P_EPI_BF16_RESID) {
             char* Cb = reinterpret_cast<char*>(static_cast<uint16_t*>(Cv) + mw * ldc + nw);
             const uint32_t ldcb = (uint32_t)ldc * 2;
+            // CM3P_EPI_BF16_RESID: R bf16 with C's layout (may alias C; every element is read before the lane that owns it stores)
+            const char* Rb = reinterpret_cast<const char*>(reinterpret_cast<const uint16_t*>(R) + mw * ldc + nw);
             const bool rotate = (EPI == CM3P_EPI_BF16_ROPE) && nw < rope.ncols;  // a wave's 64 columns are one head
             const float qs = (EPI == CM3P_EPI_BF16_ROPE && nw < rope.q_cols) ? rope.q_scale : 1.f;
             uint32_t prow0 = 0;
@@ -407,6 +409,16 @@ __global__ __launch_bounds__(512, 2) void gemm8p_kernel(const uint16_t* __restri
 #pragma unroll
             for (int i4 = 0; i4 < 8; ++i4) {
                 char* eb = ebuf + (i4 & 1) * 2048;
+                // residual rows of this step, requested before the staging round trip (the rows and chunks the lane stores below)
+                u32x4 res0, res1;
+                if constexpr (EPI == CM3P_EPI_BF16_RESID) {
+                    const int r0 = lane >> 3, r1 = 8 + (lane >> 3), ch = lane & 7;
+                    const bool col_ok = FULL || nw + ch * 8 < N;
+                    res0 = (FULL || (col_ok && mw + i4 * 16 + r0 < M)) ? __builtin_bit_cast(u32x4, gload16<(CM3P_NT & 64) != 0>(Rb + (uint32_t)(i4 * 16 + r0) * ldcb + ch * 16))
+                                                                       : u32x4{0u, 0u, 0u, 0u};
+                    res1 = (FULL || (col_ok && mw + i4 * 16 + r1 < M)) ? __builtin_bit_cast(u32x4, gload16<(CM3P_NT & 64) != 0>(Rb + (uint32_t)(i4 * 16 + r1) * ldcb + ch * 16))
+                                                                       : u32x4{0u, 0u, 0u, 0u};
+                }
 #pragma unroll
                 for (int j4 = 0; j4 < 4; ++j4) {
                     const f32x4 a = acc[i4][j4];
@@ -446,9 +458,16 @@ __global__ __launch_bounds__(512, 2) void gemm8p_kernel(const uint16_t* __restri
                 }
                 {
                     const int r0 = lane >> 3, r1 = 8 + (lane >> 3), ch = lane & 7;
-                    const u32x4 x0 = *reinterpret_cast<const u32x4*>(eb + r0 * 128 + ((ch ^ (r0 & 7)) << 4));
-                    const u32x4 x1 = *reinterpret_cast<const u32x4*>(eb + r1 * 128 + ((ch ^ (r1 & 7)) << 4));
+                    u32x4 x0 = *reinterpret_cast<const u32x4*>(eb + r0 * 128 + ((ch ^ (r0 & 7)) << 4));
+                    u32x4 x1 = *reinterpret_cast<const u32x4*>(eb + r1 * 128 + ((ch ^ (r1 & 7)) << 4));
                     G8P_LANE_XCHG_FENCE();
+                    if constexpr (EPI == CM3P_EPI_BF16_RESID) {
+#pragma unroll
+                        for (int t = 0; t < 4; ++t) {
+                            x0[t] = add_bf16x2(x0[t], res0[t]);
+                            x1[t] = add_bf16x2(x1[t], res1[t]);
+                        }
+                    }
                     const bool col_ok = FULL || nw + ch * 8 < N;
                     if (FULL || (col_ok && mw + i4 * 16 + r0 < M)) G8P_GLOBAL(gstore16<(CM3P_NT & 1) != 0>(Cb + (uint32_t)(i4 * 16 + r0) * ldcb + ch * 16, x0));
                     if (FULL || (col_ok && mw + i4 * 16 + r1 < M)) G8P_GLOBAL(gstore16<(CM3P_NT & 1) != 0>(Cb + (uint32_t)(i4 * 16 + r1) * ldcb + ch * 16, x1));
@@ -648,6 +667,7 @@ int launch8p(const uint16_t* a, const uint16_t* b, void* C, const float* R, int6
         case CM3P_EPI_BF16: CM3P_G8P(CM3P_EPI_BF16) break;
         case CM3P_EPI_F32: CM3P_G8P(CM3P_EPI_F32) break;
         case CM3P_EPI_F32_RESID: CM3P_G8P(CM3P_EPI_F32_RESID) break;
+        case CM3P_EPI_BF16_RESID: CM3P_G8P(CM3P_EPI_BF16_RESID) break;
         case CM3P_EPI_BF16_ROPE:
             if constexpr (A_KC && B_KC) {
                 CM3P_G8P(CM3P_EPI_BF16_ROPE)

@@ -18,6 +18,11 @@ activations are bf16 (what HF Trainer's bf16 autocast gives the reference's nn.L
 
 Dropout (training mode, p > 0): embedding output, attention probabilities (inside the attention kernels), attention output before
 the residual add, and gelu(h[:I]) * h[I:] before Wo - the masks follow csrc/dropout_rng.h from one seed per stack forward.
+
+bf16 residual stream (opt-in, `CM3PEncoder.residual_dtype = torch.bfloat16`): a forward-only call (nothing recorded for a backward,
+no dropout plan) keeps the stream in bf16 the way a bf16 ModernBERT does (TF:...modeling_modernbert.py:68-70,331-332,476): every
+LayerNorm reads and writes bf16, `x + o Wo^T` and `x + g Wo^T` are bf16 adds of the bf16-rounded projection (CM3P_EPI_BF16_RESID),
+last_hidden_state and hidden_states are bf16.  Every other call runs the fp32 stream whatever the switch says.
 """
 from __future__ import annotations
 
@@ -151,7 +156,7 @@ class _Geometry:
     """Static description of one forward call of the stack (no tensors that need grad)."""
 
     __slots__ = ("B", "S", "H", "I", "nh", "L", "eps", "windows", "key_mask", "rope", "per_batch_pos", "save", "cu", "max_s", "checkpoint",
-                 "handoff", "attn_out", "wcast", "hd", "drop")
+                 "handoff", "attn_out", "wcast", "hd", "drop", "bf16")
 
 
 def _hand_upstream(geo: _Geometry, gx32: Tensor, gx16: Optional[Tensor]) -> None:
@@ -183,8 +188,8 @@ def _layer_forward(geo: _Geometry, i: int, x: Tensor, wb, want_stats: bool):
     cos, sin = geo.rope[i]
     # attention dropout (probabilities and out_drop, TF:...modeling_modernbert.py:292,300): (thr, seed, layer), or None
     ad = (geo.drop.attn, geo.drop.seed, i) if geo.drop is not None and geo.drop.attn else None
-    if i == 0:
-        xn, mean_a, rstd_a = K.cast_bf16(x), None, None
+    if i == 0:  # (bf16 stream: the embedding output is layer 0's GEMM operand as it is)
+        xn, mean_a, rstd_a = (x if x.dtype == torch.bfloat16 else K.cast_bf16(x)), None, None
     else:
         _, xn, mean_a, rstd_a = K.layernorm_fwd(x, w_an, geo.eps, False, True, want_stats)
     if geo.hd != 64:
@@ -221,7 +226,8 @@ def _layer_forward(geo: _Geometry, i: int, x: Tensor, wb, want_stats: bool):
 
 
 class _EncoderLayerFn(torch.autograd.Function):
-    """One ModernBERT encoder layer (TF:...modeling_modernbert.py:318-333): x [T,H] fp32 + its weights -> x_out [T,H] fp32.
+    """One ModernBERT encoder layer (TF:...modeling_modernbert.py:318-333): x [T,H] fp32 + its weights -> x_out [T,H] fp32
+    (bf16 -> bf16 on the bf16 residual stream of a forward-only call: the residual GEMMs take x's dtype).
 
     One autograd node per layer, so a layer's weight gradients reach their parameters (and a DistributedDataParallel
     bucket's all-reduce starts) while the layers below are still in backward.  The fp32 residual-stream gradient travels
@@ -317,12 +323,14 @@ class _EncoderLayerFn(torch.autograd.Function):
 
 
 class _FinalNormFn(torch.autograd.Function):
-    """final_norm of the stack (TF:...modeling_modernbert.py:472): x [T,H] fp32 -> LayerNorm(x) fp32; its backward starts the
-    chain of bf16 gradient twins."""
+    """final_norm of the stack (TF:...modeling_modernbert.py:472): x [T,H] fp32 -> LayerNorm(x) fp32 (bf16 -> bf16 on the bf16
+    residual stream); its backward starts the chain of bf16 gradient twins."""
 
     @staticmethod
     def forward(ctx, geo: _Geometry, x: Tensor, norm_w: Tensor):
         w = _f32(norm_w.detach())
+        if geo.bf16:
+            return K.layernorm_fwd(x, w, geo.eps, False, True, False)[1]
         y, _, mean, rstd = K.layernorm_fwd(x, w, geo.eps, True, False, geo.save)
         if geo.save:
             ctx.geo, ctx.pack, ctx.wdtype = geo, (x, w, mean, rstd), norm_w.dtype
@@ -339,14 +347,17 @@ class _FinalNormFn(torch.autograd.Function):
 
 class _EmbedLNFn(torch.autograd.Function):
     """LayerNorm(tok_embeddings[ids]) with optional audio rows scattered over the placeholder tokens
-    (TF:...modeling_modernbert.py:64-71, ref:cm3p/modeling_cm3p.py:592,603-605)."""
+    (TF:...modeling_modernbert.py:64-71, ref:cm3p/modeling_cm3p.py:592,603-605).  bf16: the bf16 output alone (the bf16 residual
+    stream of a forward-only call; no fp32 rows are written)."""
 
     @staticmethod
     def forward(ctx, ids: Tensor, table: Tensor, norm_w: Tensor, eps: float, padding_idx: int, slot: Optional[Tensor],
-                audio_rows: Optional[Tensor]):
+                audio_rows: Optional[Tensor], bf16: bool = False):
         w = _f32(norm_w.detach())
         tab = table.detach()
         ar = audio_rows.detach().contiguous() if audio_rows is not None else None
+        if bf16:
+            return K.embed_ln_fwd(ids, tab, w, eps, slot, ar, want_bf16=True, want_f32=False)[1]
         y, _, mean, rstd = K.embed_ln_fwd(ids, tab, w, eps, slot, ar)
         ctx.pack = (ids, tab, w, mean, rstd, slot, ar, padding_idx)
         ctx.dtypes = (table.dtype, norm_w.dtype, audio_rows.dtype if audio_rows is not None else None)
@@ -362,7 +373,7 @@ class _EmbedLNFn(torch.autograd.Function):
             d_table = d_table.to(td)
         if d_audio is not None and d_audio.dtype != ad:
             d_audio = d_audio.to(ad)
-        return None, d_table, dw.to(wd), None, None, None, d_audio
+        return None, d_table, dw.to(wd), None, None, None, d_audio, None
 
 
 class _DropPlan:
@@ -407,12 +418,15 @@ class _PadRowsFn(torch.autograd.Function):
 
 
 class _LayerNormFn(torch.autograd.Function):
-    """Plain LayerNorm of given rows (the `inputs_embeds` entry of ModernBertEmbeddings, TF:...modeling_modernbert.py:67-68)."""
+    """Plain LayerNorm of given rows (the `inputs_embeds` entry of ModernBertEmbeddings, TF:...modeling_modernbert.py:67-68).
+    bf16: the bf16 output alone (the bf16 residual stream of a forward-only call)."""
 
     @staticmethod
-    def forward(ctx, x: Tensor, norm_w: Tensor, eps: float):
+    def forward(ctx, x: Tensor, norm_w: Tensor, eps: float, bf16: bool = False):
         w = _f32(norm_w.detach())
         xd = x.detach().contiguous()
+        if bf16:
+            return K.layernorm_fwd(xd, w, eps, False, True, False)[1]
         y, _, mean, rstd = K.layernorm_fwd(xd, w, eps, True, False)
         ctx.pack = (xd, w, mean, rstd)
         ctx.dtypes = (x.dtype, norm_w.dtype)
@@ -423,7 +437,7 @@ class _LayerNormFn(torch.autograd.Function):
         xd, w, mean, rstd = ctx.pack
         x32 = xd if xd.dtype == torch.float32 else xd.float()
         dx, _, dw = K.layernorm_bwd(dy.contiguous(), x32, w, mean, rstd, None, False, inplace=False)
-        return (dx if ctx.dtypes[0] == torch.float32 else dx.to(ctx.dtypes[0])), dw.to(ctx.dtypes[1]), None
+        return (dx if ctx.dtypes[0] == torch.float32 else dx.to(ctx.dtypes[0])), dw.to(ctx.dtypes[1]), None, None
 
 
 class CM3PEncoder(nn.Module):
@@ -437,6 +451,7 @@ class CM3PEncoder(nn.Module):
         self.layers = nn.ModuleList([CM3PEncoderLayerParams(config, i) for i in range(config.num_hidden_layers)])
         self.final_norm = nn.LayerNorm(config.hidden_size, eps=config.norm_eps, bias=False)
         self.gradient_checkpointing = False  # set by PreTrainedModel.gradient_checkpointing_enable()
+        self.residual_dtype = None  # None / torch.float32: fp32 residual stream; torch.bfloat16: bf16 on forward-only calls
         self._inv_freq_cache = {}
         # init roles (TF:...modeling_modernbert.py:372-386): 'in'/'embedding' std = initializer_range,
         # 'out' std = initializer_range / sqrt(2 L); consumed by CM3PPreTrainedModel._init_weights
@@ -449,6 +464,30 @@ class CM3PEncoder(nn.Module):
             layer.attn.Wo._cm3p_init = (std_out, cutoff)
             layer.mlp.Wi._cm3p_init = (std_in, cutoff)
             layer.mlp.Wo._cm3p_init = (std_out, cutoff)
+
+    @property
+    def residual_dtype(self) -> Optional[torch.dtype]:
+        """dtype of the residual stream on forward-only calls: None or torch.float32 (the default) keep it fp32; torch.bfloat16 runs
+        it in bf16 as a bf16 model of the reference does under no_grad (every LayerNorm reads and writes bf16, the residual adds are
+        bf16 adds of the bf16-rounded projections, last_hidden_state and hidden_states are bf16).  Applies only to calls that record
+        nothing for a backward and have no dropout plan; training steps, calls with grad enabled on trainable parameters or inputs,
+        and train-mode calls with dropout p > 0 run the fp32 stream bit for bit as with None.  Not part of the state dict or config."""
+        return self._residual_dtype
+
+    @residual_dtype.setter
+    def residual_dtype(self, dtype) -> None:
+        if dtype is not None and dtype not in (torch.float32, torch.bfloat16):
+            raise ValueError(f"residual_dtype must be None, torch.float32 or torch.bfloat16, got {dtype!r}")
+        self._residual_dtype = dtype
+
+    def _bf16_stream(self, plan: Optional[_DropPlan], *inputs: Optional[Tensor]) -> bool:
+        """Whether this call runs the bf16 residual stream: the switch is set, there is no dropout plan and nothing will be recorded
+        for a backward (the rule _run_stack applies to geo.save, decided before the embedding runs)."""
+        if self._residual_dtype is not torch.bfloat16 or plan is not None:
+            return False
+        if not torch.is_grad_enabled():
+            return True
+        return not any(t is not None and t.requires_grad for t in inputs) and not any(p.requires_grad for p in self.parameters())
 
     def train(self, mode: bool = True):
         if mode != self.training:
@@ -504,7 +543,7 @@ class CM3PEncoder(nn.Module):
                 audio_slot: Optional[Tensor] = None, audio_rows: Optional[Tensor] = None, unpad: bool = False,
                 output_hidden_states: bool = False, cu_seqlens: Optional[Tensor] = None, max_seqlen: Optional[int] = None,
                 output_attentions: bool = False):
-        """-> last_hidden_state (B, S, H) fp32 [, tuple of L+1 detached hidden states (the stack's input and every layer's output,
+        """-> last_hidden_state (B, S, H) fp32 (bf16 on the bf16 residual stream, see residual_dtype) [, tuple of L+1 detached hidden states (the stack's input and every layer's output,
         TF:...modeling_modernbert.py:457-470) when output_hidden_states].  Exactly one of input_ids / inputs_embeds.
         output_attentions: -> (last_hidden_state, hidden states or None, tuple of L attention-probability tensors (B, nh, S, S) fp32,
         detached): what the reference returns as `attentions` (TF runs its eager attention for such a call); padded execution only.
@@ -525,10 +564,11 @@ class CM3PEncoder(nn.Module):
         plan = self._dropout_plan()  # (before any launch: a refused graph capture has captured nothing)
         if output_attentions and plan is not None and plan.attn:
             raise NotImplementedError("output_attentions with attention dropout in training mode (the kernels return undropped probabilities)")
+        bf16 = self._bf16_stream(plan, inputs_embeds, audio_rows)
         if cu_seqlens is not None:
             if output_attentions:
                 raise NotImplementedError("output_attentions with unpadded inputs: attention probabilities are (B, nh, S, S) tensors of a padded batch")
-            return self._forward_prepacked(input_ids, position_ids, audio_slot, audio_rows, cu_seqlens, max_seqlen, output_hidden_states, plan)
+            return self._forward_prepacked(input_ids, position_ids, audio_slot, audio_rows, cu_seqlens, max_seqlen, output_hidden_states, plan, bf16)
         if output_attentions:
             unpad = False  # the probabilities are laid out per padded (batch, head, query, key)
         if input_ids is not None and input_ids.dtype != torch.int64:
@@ -556,16 +596,16 @@ class CM3PEncoder(nn.Module):
                     slot_p = torch.cat((slot_p, slot_p.new_full((n_rows - n_valid,), -1)))
             pad = self.embeddings.tok_embeddings.padding_idx
             x0 = _EmbedLNFn.apply(ids, self.embeddings.tok_embeddings.weight, self.embeddings.norm.weight, cfg.norm_eps,
-                                  -1 if pad is None else pad, None if slot_p is None else slot_p.contiguous(), audio_rows)
+                                  -1 if pad is None else pad, None if slot_p is None else slot_p.contiguous(), audio_rows, bf16)
         elif input_ids is not None:
             pad = self.embeddings.tok_embeddings.padding_idx
             x0 = _EmbedLNFn.apply(input_ids.contiguous().view(-1), self.embeddings.tok_embeddings.weight,
-                                  self.embeddings.norm.weight, cfg.norm_eps, -1 if pad is None else pad, audio_slot, audio_rows)
+                                  self.embeddings.norm.weight, cfg.norm_eps, -1 if pad is None else pad, audio_slot, audio_rows, bf16)
         else:
-            x0 = _LayerNormFn.apply(inputs_embeds.reshape(B * S, H), self.embeddings.norm.weight, cfg.norm_eps)
+            x0 = _LayerNormFn.apply(inputs_embeds.reshape(B * S, H), self.embeddings.norm.weight, cfg.norm_eps, bf16)
 
         x0 = self._embed_dropout(x0, plan, S, packed[1] if packed is not None else None)
-        y, hiddens, attns = self._run_stack(x0, B, S, attention_mask, position_ids, packed, output_hidden_states, dev, output_attentions, plan)
+        y, hiddens, attns = self._run_stack(x0, B, S, attention_mask, position_ids, packed, output_hidden_states, dev, output_attentions, plan, bf16)
         if hiddens is not None:
             if packed is not None:
                 hiddens = [K.scatter_rows(h[:n_valid].contiguous(), idx, B * S) for h in hiddens]
@@ -578,9 +618,9 @@ class CM3PEncoder(nn.Module):
         return (y, hiddens) if output_hidden_states else y
 
     def _run_stack(self, x0: Tensor, B: int, S: int, attention_mask, position_ids, packed, output_hidden_states: bool, dev,
-                   output_attentions: bool = False, plan: Optional[_DropPlan] = None):
+                   output_attentions: bool = False, plan: Optional[_DropPlan] = None, bf16: bool = False):
         """The L encoder layers + final norm on [rows, H]; `packed` = (idx, cu, max_s, n_valid, n_rows, pos) for unpadded execution;
-        `plan`: the call's dropout (None: none)."""
+        `plan`: the call's dropout (None: none); `bf16`: x0 is bf16 and the stream stays bf16 (forward-only calls, _bf16_stream)."""
         cfg = self.config
         H = cfg.hidden_size
         geo = _Geometry()
@@ -618,6 +658,9 @@ class CM3PEncoder(nn.Module):
         weights = self._stack_weights()
         geo.save = torch.is_grad_enabled() and (x0.requires_grad or self.final_norm.weight.requires_grad
                                                 or any(w.requires_grad for ws in weights for w in ws))
+        if bf16 and geo.save:  # (_bf16_stream applies the same rule before the embedding ran)
+            raise RuntimeError("cm3p_amd: bf16 residual stream on a call that records a backward")
+        geo.bf16 = bf16
         if geo.save and _eval_weights:
             invalidate_weight_cache()  # a backward will follow, so an optimizer will: no copy made before this step may outlive it
         geo.wcast = None
@@ -642,7 +685,7 @@ class CM3PEncoder(nn.Module):
         return y, hiddens, attns
 
     def _forward_prepacked(self, input_ids: Tensor, position_ids: Optional[Tensor], audio_slot, audio_rows, cu_seqlens: Tensor,
-                           max_seqlen: Optional[int], output_hidden_states: bool, plan: Optional[_DropPlan] = None):
+                           max_seqlen: Optional[int], output_hidden_states: bool, plan: Optional[_DropPlan] = None, bf16: bool = False):
         """Caller-supplied unpadded inputs (ref:cm3p/modeling_cm3p.py:911-931 when `indices` / `cu_seqlens` / `max_seqlen` are given;
         the layout of _unpad_cm3p_input, :65-104): input_ids (total,), cu_seqlens (batch + 1,) -> last_hidden_state (total, H),
         NOT re-padded (the reference's encoder leaves caller-packed rows packed as well)."""
@@ -681,10 +724,10 @@ class CM3PEncoder(nn.Module):
                 slot_p = torch.cat((slot_p, slot_p.new_full((n_rows - total,), -1)))
         pad = self.embeddings.tok_embeddings.padding_idx
         x0 = _EmbedLNFn.apply(ids, self.embeddings.tok_embeddings.weight, self.embeddings.norm.weight, cfg.norm_eps,
-                              -1 if pad is None else pad, None if slot_p is None else slot_p.contiguous(), audio_rows)
+                              -1 if pad is None else pad, None if slot_p is None else slot_p.contiguous(), audio_rows, bf16)
         packed = (None, cu, max(max_s, n_rows - total), total, n_rows, pos.contiguous())
         x0 = self._embed_dropout(x0, plan, max_s, cu)
-        y, hiddens, _ = self._run_stack(x0, cu.numel() - 1, max_s, None, None, packed, output_hidden_states, dev, plan=plan)
+        y, hiddens, _ = self._run_stack(x0, cu.numel() - 1, max_s, None, None, packed, output_hidden_states, dev, plan=plan, bf16=bf16)
         if n_rows != total:
             y = y[:total]
             if hiddens is not None:

@@ -11,7 +11,7 @@ from typing import Optional
 import torch
 
 from . import _lib
-from ._lib import BF16, EPI_BF16, EPI_F32, EPI_F32_RESID, F32, call, dt, ptr, query, stream
+from ._lib import BF16, EPI_BF16, EPI_BF16_RESID, EPI_F32, EPI_F32_RESID, F32, call, dt, ptr, query, stream
 
 Tensor = torch.Tensor
 
@@ -53,10 +53,13 @@ def layernorm_bwd(dy: Tensor, x: Tensor, weight: Tensor, mean: Tensor, rstd: Ten
 
 
 def embed_ln_fwd(ids: Tensor, table: Tensor, weight: Tensor, eps: float, slot: Optional[Tensor] = None,
-                 override: Optional[Tensor] = None, want_bf16: bool = False):
+                 override: Optional[Tensor] = None, want_bf16: bool = False, want_f32: bool = True):
+    """-> (y_f32|None, y_bf16|None, mean, rstd); at least one of want_f32 / want_bf16 (bf16 alone: the bf16 residual stream)."""
     T = ids.numel()
     H = table.shape[1]
-    y32 = _empty((T, H), torch.float32, table)
+    if not (want_f32 or want_bf16):
+        raise ValueError("embed_ln_fwd: no output requested")
+    y32 = _empty((T, H), torch.float32, table) if want_f32 else None
     y16 = _empty((T, H), torch.bfloat16, table) if want_bf16 else None
     mean = _empty((T,), torch.float32, table)
     rstd = _empty((T,), torch.float32, table)
@@ -178,7 +181,7 @@ def gemm(a: Tensor, b: Tensor, M: int, N: int, K: int, a_kc: bool, b_kc: bool, e
     """C[m,n] = sum_k A(m,k) B(n,k) (+resid).  a/b bf16, row-major 2-D; see include/cm3p_hip.h for the layouts."""
     lda, ldb = a.shape[1], b.shape[1]
     if out is None:
-        out = _empty((M, N), torch.bfloat16 if epilogue == EPI_BF16 else torch.float32, a)
+        out = _empty((M, N), torch.bfloat16 if epilogue in (EPI_BF16, EPI_BF16_RESID) else torch.float32, a)
     ws = _empty((split_k, M, N), torch.float32, a) if split_k > 1 else None
     call("cm3p_gemm_bf16", ptr(a), ptr(b), ptr(out), ptr(resid), M, N, K, lda, ldb, N, int(a_kc), int(b_kc), epilogue, split_k,
          ptr(ws), stream(), tag=_gemm_tag(M, N, K, a_kc, b_kc, epilogue, split_k), work=2.0 * M * N * K)
@@ -186,10 +189,13 @@ def gemm(a: Tensor, b: Tensor, M: int, N: int, K: int, a_kc: bool, b_kc: bool, e
 
 
 def linear_fwd(x: Tensor, w: Tensor, resid: Optional[Tensor] = None) -> Tensor:
-    """x [T,K] bf16, w [N,K] bf16 -> x w^T as bf16, or fp32 resid + x w^T."""
+    """x [T,K] bf16, w [N,K] bf16 -> x w^T as bf16, or resid + x w^T: fp32 for an fp32 resid, bf16(resid + bf16(x w^T)) for a
+    bf16 one (the bf16 residual stream of forward-only calls, CM3P_EPI_BF16_RESID)."""
     T, K = x.shape
     N = w.shape[0]
-    return gemm(x, w, T, N, K, True, True, EPI_F32_RESID if resid is not None else EPI_BF16, resid)
+    if resid is None:
+        return gemm(x, w, T, N, K, True, True, EPI_BF16)
+    return gemm(x, w, T, N, K, True, True, EPI_BF16_RESID if resid.dtype == torch.bfloat16 else EPI_F32_RESID, resid)
 
 
 def linear_fwd_f32(x: Tensor, w: Tensor) -> Tensor:
@@ -509,18 +515,25 @@ def attn_bwd_varlen(qkv: Tensor, out: Tensor, dout: Tensor, lse: Tensor, cu: Ten
     return dqkv
 
 
+def _rows_as_f32(src: Tensor) -> Tensor:
+    """bf16 rows [n, H] (H even) as fp32 rows [n, H / 2] of the same bits: the row copies below move them unchanged."""
+    return src.view(torch.float32) if src.dtype == torch.bfloat16 else src
+
+
 def gather_rows(src: Tensor, idx: Tensor) -> Tensor:
-    """src [R, H] fp32, idx int64 [n] -> [n, H] (the row selection of _unpad_cm3p_input)."""
-    out = torch.empty((idx.numel(), src.shape[1]), dtype=torch.float32, device=src.device)
-    call("cm3p_gather_rows_f32", ptr(src), ptr(idx, torch.int64), ptr(out), idx.numel(), src.shape[1], stream())
-    return out
+    """src [R, H] fp32 or bf16, idx int64 [n] -> [n, H] of src's dtype (the row selection of _unpad_cm3p_input)."""
+    s32 = _rows_as_f32(src)
+    out = torch.empty((idx.numel(), s32.shape[1]), dtype=torch.float32, device=src.device)
+    call("cm3p_gather_rows_f32", ptr(s32), ptr(idx, torch.int64), ptr(out), idx.numel(), s32.shape[1], stream())
+    return out.view(src.dtype)
 
 
 def scatter_rows(src: Tensor, idx: Tensor, rows: int) -> Tensor:
-    """src [n, H] fp32 -> [rows, H] with row idx[i] = src[i] and zeros elsewhere (_pad_cm3p_output)."""
-    out = torch.zeros((rows, src.shape[1]), dtype=torch.float32, device=src.device)
-    call("cm3p_scatter_rows_f32", ptr(src), ptr(idx, torch.int64), ptr(out), idx.numel(), src.shape[1], stream())
-    return out
+    """src [n, H] fp32 or bf16 -> [rows, H] of src's dtype with row idx[i] = src[i] and zeros elsewhere (_pad_cm3p_output)."""
+    s32 = _rows_as_f32(src)
+    out = torch.zeros((rows, s32.shape[1]), dtype=torch.float32, device=src.device)
+    call("cm3p_scatter_rows_f32", ptr(s32), ptr(idx, torch.int64), ptr(out), idx.numel(), s32.shape[1], stream())
+    return out.view(src.dtype)
 
 
 # ------------------------------------------------------------------------------------------------ MLP pieces
@@ -669,11 +682,12 @@ def bias_gelu_bwd(da: Tensor, z: Tensor, bias: Tensor):
 
 # ------------------------------------------------------------------------------------------------ pooling
 def pool_fwd(h: Tensor, mask: Optional[Tensor], Bn: int, S: int, cls: bool):
+    """h [Bn, S, H] fp32 or bf16 (fp32 accumulation either way) -> (pooled [Bn, H] fp32, count [Bn] fp32)."""
     H = h.shape[-1]
     pooled = torch.empty((Bn, H), dtype=torch.float32, device=h.device)
     count = torch.empty((Bn,), dtype=torch.float32, device=h.device)
     part = None if cls else torch.empty((Bn, query("cm3p_pool_chunks", S), H), dtype=torch.float32, device=h.device)
-    call("cm3p_pool_fwd", ptr(h), ptr(mask, torch.int64), ptr(pooled), ptr(part), ptr(count), Bn, S, H, int(cls), stream())
+    call("cm3p_pool_fwd", ptr(h), dt(h), ptr(mask, torch.int64), ptr(pooled), ptr(part), ptr(count), Bn, S, H, int(cls), stream())
     return pooled, count
 
 

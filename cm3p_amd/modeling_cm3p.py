@@ -211,7 +211,9 @@ def _mlm_head_forward(h: Tensor, Wd: Tensor, bd: Optional[Tensor], norm_w: Tenso
     T, H = h.shape
     V = Wdec.shape[0]
     Vp = (V + 63) // 64 * 64
-    hb = K.cast_bf16(h.detach().contiguous())
+    hb = h.detach().contiguous()
+    if hb.dtype != torch.bfloat16:  # (rows of the bf16 residual stream are the GEMM operand as they are)
+        hb = K.cast_bf16(hb)
     Wd_b = _bf16_weight(Wd)
     Wdec_b = _bf16_weight(Wdec)
     if Vp != V:
@@ -339,6 +341,18 @@ class CM3PPreTrainedModel(PreTrainedModel):
     _supports_flash_attn = True
     _supports_sdpa = True
     _supports_flex_attn = False
+
+    def set_residual_dtype(self, dtype: Optional[torch.dtype]):
+        """Set `residual_dtype` on every encoder this model owns (beatmap, metadata and audio towers): torch.bfloat16 runs the
+        residual stream of forward-only calls in bf16, the reference's inference recipe (a bf16 model called under no_grad);
+        None / torch.float32 keep the fp32 stream.  Training steps and dropout calls always run fp32 (CM3PEncoder.residual_dtype).
+        Returns the model; the state dict and the config are unchanged."""
+        from .encoder import CM3PEncoder
+
+        encoders = [m for m in self.modules() if isinstance(m, CM3PEncoder)]
+        for enc in encoders:
+            enc.residual_dtype = dtype  # (the setter validates; a bad dtype raises before anything is changed: all share one rule)
+        return self
 
     def _check_and_adjust_attn_implementation(self, attn_implementation, *args, **kwargs):
         # Attention always runs in the HIP flash kernels; the configured string ("sdpa", "flash_attention_2", "eager", as
@@ -532,6 +546,8 @@ class CM3PBeatmapTransformer(nn.Module):
                     raise NotImplementedError("Pooling with unpadded input is not implemented yet.")
                 first = cu_seqlens[:-1].to(device=h.device, dtype=torch.int64).contiguous()
                 pooled = _TakeRowsFn.apply(h, first)
+                if pooled.dtype != torch.float32:  # bf16 residual stream: the pooled rows widened exactly, as _PoolFn returns them
+                    pooled = pooled.float()
             return CM3PBeatmapModelOutput(last_hidden_state=h, pooler_output=pooled, hidden_states=hiddens, attentions=None,
                                           audio_model_output=audio_out)
         if inputs_embeds is not None:

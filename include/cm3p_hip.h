@@ -31,7 +31,7 @@ extern "C" {
 #define CM3P_BF16 1
 
 /* ABI version of this header; cm3p_abi_version() must return it. */
-#define CM3P_ABI_VERSION 17
+#define CM3P_ABI_VERSION 18
 int cm3p_abi_version(void);
 
 /* ---------------------------------------------------------------------------------------------------------------
@@ -105,13 +105,17 @@ int cm3p_audio_slots(const int64_t* ids, int64_t T, int64_t audio_token_id, int3
  *   b_kc likewise for B over (n, k).
  *   epilogue: CM3P_EPI_BF16 (C bf16), CM3P_EPI_F32 (C fp32), CM3P_EPI_F32_RESID (C fp32 = R + acc; R fp32 [M, ldc], may
  *   alias C), CM3P_EPI_F32_BIAS (C fp32 = acc + R[n]; R fp32 [N]: nn.Linear's bias added while the tile is stored - the
- *   decoder of the MLM head, ref:cm3p/modeling_cm3p.py:767,991; forward orientation a_kc = b_kc = 1 only).
+ *   decoder of the MLM head, ref:cm3p/modeling_cm3p.py:767,991; forward orientation a_kc = b_kc = 1 only),
+ *   CM3P_EPI_BF16_RESID (C bf16 = bf16(float(bf16(acc)) + float(R)); R bf16 [M, ldc], may alias C: the bf16 residual add
+ *   `hidden_states + Wo(x)` of a bf16 model, TF:...modeling_modernbert.py:331-332 - bit for bit a CM3P_EPI_BF16 GEMM followed by
+ *   torch's bf16 add; N and ldc multiples of 8, split_k = 1; R is read through the `const float*` parameter as bf16).
  *   Constraints: contiguous extents and leading dimensions are multiples of 8 elements.
  */
 #define CM3P_EPI_BF16 0
 #define CM3P_EPI_F32 1
 #define CM3P_EPI_F32_RESID 2
 #define CM3P_EPI_F32_BIAS 5
+#define CM3P_EPI_BF16_RESID 7
 /* split_k > 1 (CM3P_EPI_F32 only, ldc == N): the contraction is cut into split_k ranges whose fp32 partial tiles go to
  * `workspace` (split_k * M * N floats) and are then summed in a fixed order - used for dW, whose contraction runs over
  * all tokens while its output is only a few hundred tiles. */
@@ -369,11 +373,12 @@ int cm3p_bias_gelu_bwd(const void* da, int da_dtype, const float* z, const float
 /* ---------------------------------------------------------------------------------------------------------------
  * Pooling of the last hidden state (ref:cm3p/modeling_cm3p.py:385-396, 631-642).
  *   cls != 0: pooled[b] = h[b, 0];  else pooled[b] = sum_s h[b,s]*m[b,s] / max(sum_s m[b,s], 1e-9)  (m all ones if NULL).
- * h: [Bn, S, H] fp32, mask: [Bn, S] int64 or NULL, pooled: [Bn, H] fp32.  partial: fp32 workspace
- * [Bn, cm3p_pool_chunks(S), H]; count: [Bn] fp32, sum of the mask row (saved for the backward pass).
+ * h: [Bn, S, H] of h_dtype (CM3P_F32, or CM3P_BF16: the bf16 residual stream of a forward-only call; accumulated in fp32 in
+ * the same order, so bf16 rows pool to the bits of their fp32 upcast), mask: [Bn, S] int64 or NULL, pooled: [Bn, H] fp32.
+ * partial: fp32 workspace [Bn, cm3p_pool_chunks(S), H]; count: [Bn] fp32, sum of the mask row (saved for the backward pass).
  */
 int cm3p_pool_chunks(int S);
-int cm3p_pool_fwd(const float* h, const int64_t* mask, float* pooled, float* partial, float* count, int Bn, int S, int H,
+int cm3p_pool_fwd(const void* h, int h_dtype, const int64_t* mask, float* pooled, float* partial, float* count, int Bn, int S, int H,
                   int cls, void* stream);
 int cm3p_pool_bwd(const float* dpooled, const int64_t* mask, const float* count, float* dh, int Bn, int S, int H, int cls,
                   void* stream);

@@ -8,6 +8,10 @@ the judged number comes from bench.py):
               a (B, V, 256) metadata batch through the metadata tower + logits + loss
 
     python tools/bench_eval.py [extract] [variations] [--batch 32] [--variations 1000] [--var-batch 8] [--iters 5]
+                               [--residual {fp32,bf16,both}]
+
+--residual: the residual stream of the encoders (model.set_residual_dtype): fp32 (the default), bf16, or both - the two modes timed in
+the same process, alternating (--rounds pairs of --iters calls each), with ms per call of each mode and the bf16 / fp32 ratio.
 """
 import argparse
 import json
@@ -34,6 +38,32 @@ def timed(fn, iters):
     return e0.elapsed_time(e1) / iters
 
 
+def timed_modes(model, fn, modes, iters, rounds):
+    """-> {mode: ms per call}: with two modes, `rounds` alternating blocks of `iters` calls each (median over the blocks)."""
+    ms = {m: [] for m in modes}
+    for _ in range(rounds if len(modes) > 1 else 1):
+        for m in modes:
+            model.set_residual_dtype(RESID[m])
+            ms[m].append(timed(fn, iters))
+    model.set_residual_dtype(None)
+    return {m: sorted(v)[len(v) // 2] for m, v in ms.items()}
+
+
+def mode_fields(model, fn, modes, ms, top):
+    """ms per mode, the bf16 / fp32 ratio, and each mode's per-kernel split."""
+    out = {"residual": "+".join(modes), "ms": ms[modes[0]] if len(modes) == 1 else {m: round(ms[m], 3) for m in modes}}
+    if len(modes) > 1:
+        out["ratio_bf16_over_fp32"] = round(ms["bf16"] / ms["fp32"], 4)
+    for m in modes:
+        model.set_residual_dtype(RESID[m])
+        out["kernels_ms" if len(modes) == 1 else f"kernels_ms_{m}"] = breakdown(fn, top)
+    model.set_residual_dtype(None)
+    return out
+
+
+RESID = {"fp32": None, "bf16": torch.bfloat16}
+
+
 def breakdown(fn, top=8):
     _lib.profile_begin()
     fn()
@@ -48,6 +78,8 @@ def main():
     ap.add_argument("--variations", type=int, default=1000)
     ap.add_argument("--var-batch", type=int, default=8)
     ap.add_argument("--iters", type=int, default=5)
+    ap.add_argument("--residual", choices=["fp32", "bf16", "both"], default="fp32")
+    ap.add_argument("--rounds", type=int, default=5, help="--residual both: alternating blocks per mode")
     ap.add_argument("--meta-valid", type=float, default=1.0,
                     help="variations: valid length of a metadata row ~ U{1..meta_valid * L} (right-padded); below 1 the run is repeated with "
                          "unpadded execution (model.unpad_inputs = True)")
@@ -57,6 +89,7 @@ def main():
     torch.manual_seed(0)
     model = CM3PModel(cfg).to(dev).eval()
     S, L = 4096, 256
+    modes = ["fp32", "bf16"] if args.residual == "both" else [args.residual]
     if "extract" in args.what:
         b = {k: v.to(dev) for k, v in synthetic_batch(cfg, args.batch, S, L, seed=1234).items()}
 
@@ -64,10 +97,11 @@ def main():
             with torch.no_grad():
                 return model(input_ids=b["input_ids"], attention_mask=b["attention_mask"], return_loss=False).beatmap_embeds
 
-        ms = timed(run, args.iters)
+        mss = timed_modes(model, run, modes, args.iters, args.rounds)
+        ms = mss[modes[-1]]
         fl = tower_flops_fwd(cfg.beatmap_config, args.batch * S, S)
-        print(json.dumps({"path": "extract", "batch": args.batch, "seq": S, "ms": ms, "beatmaps_per_s": args.batch / ms * 1e3,
-                          "tokens_per_s": args.batch * S / ms * 1e3, "tflops": fl / ms / 1e9, "kernels_ms": breakdown(run)}))
+        print(json.dumps({"path": "extract", "batch": args.batch, "seq": S, "beatmaps_per_s": args.batch / ms * 1e3,
+                          "tokens_per_s": args.batch * S / ms * 1e3, "tflops": fl / ms / 1e9, **mode_fields(model, run, modes, mss, 8)}))
     if "variations" in args.what:
         B, V = args.var_batch, args.variations
         b = {k: v.to(dev) for k, v in synthetic_batch(cfg, B, S, L, seed=99).items()}
@@ -100,12 +134,13 @@ def main():
             print(json.dumps({"path": "variations, right-padded metadata", "valid_fraction": float(mmask.float().mean()), "ms_padded_execution": ms_pad,
                               "ms_unpadded_execution": ms_unp}))
             mmask = torch.ones(B, V, L, dtype=torch.int64, device=dev)
-        ms = timed(run_full, args.iters)
+        mss = timed_modes(model, run_full, modes, args.iters, args.rounds)
+        ms = mss[modes[-1]]
         fl_m = tower_flops_fwd(cfg.metadata_config, B * V * L, L)
         fl_b = tower_flops_fwd(cfg.beatmap_config, B * S, S)
-        print(json.dumps({"path": "variations", "batch": B, "variations": V, "metadata_seq": L, "ms": ms,
+        print(json.dumps({"path": "variations", "batch": B, "variations": V, "metadata_seq": L,
                           "metadata_sequences_per_s": B * V / ms * 1e3, "metadata_tokens_per_s": B * V * L / ms * 1e3,
-                          "tflops": (fl_m + fl_b) / ms / 1e9, "metadata_tower_tflop": fl_m / 1e12, "kernels_ms": breakdown(run_full, 10)}))
+                          "tflops": (fl_m + fl_b) / ms / 1e9, "metadata_tower_tflop": fl_m / 1e12, **mode_fields(model, run_full, modes, mss, 10)}))
         del bm
 
 
