@@ -524,6 +524,8 @@ def gather_rows(src: Tensor, idx: Tensor) -> Tensor:
     """src [R, H] fp32 or bf16, idx int64 [n] -> [n, H] of src's dtype (the row selection of _unpad_cm3p_input)."""
     s32 = _rows_as_f32(src)
     out = torch.empty((idx.numel(), s32.shape[1]), dtype=torch.float32, device=src.device)
+    if idx.numel() == 0:  # no row selected (every position masked): an empty tensor has no address to hand to the entry point
+        return out.view(src.dtype)
     call("cm3p_gather_rows_f32", ptr(s32), ptr(idx, torch.int64), ptr(out), idx.numel(), s32.shape[1], stream())
     return out.view(src.dtype)
 
@@ -532,6 +534,8 @@ def scatter_rows(src: Tensor, idx: Tensor, rows: int) -> Tensor:
     """src [n, H] fp32 or bf16 -> [rows, H] of src's dtype with row idx[i] = src[i] and zeros elsewhere (_pad_cm3p_output)."""
     s32 = _rows_as_f32(src)
     out = torch.zeros((rows, s32.shape[1]), dtype=torch.float32, device=src.device)
+    if idx.numel() == 0:  # nothing to place: all rows stay zero (see gather_rows)
+        return out.view(src.dtype)
     call("cm3p_scatter_rows_f32", ptr(s32), ptr(idx, torch.int64), ptr(out), idx.numel(), s32.shape[1], stream())
     return out.view(src.dtype)
 

@@ -14,15 +14,22 @@ CH = "tests/test_conv_head_kernels_gpu.py::"
 DR = "tests/test_dropout_gpu.py::"
 MU = "tests/test_muon_gpu.py::"
 MG = "tests/test_model_gpu.py::"
+RK = "tests/test_row_kernels_gpu.py::"
 
 LEDGER = {
-    "cm3p_layernorm_fwd": [KG + "test_layernorm_fwd_bwd", CH + "test_layernorm_with_many_rows_per_wave"],
-    "cm3p_layernorm_bwd": [KG + "test_layernorm_fwd_bwd", CH + "test_layernorm_with_many_rows_per_wave"],
-    "cm3p_embed_ln_fwd": [KG + "test_embed_ln_with_audio_override"],
-    "cm3p_embed_ln_bwd": [KG + "test_embed_ln_with_audio_override"],
-    "cm3p_embed_ln_bwd_sorted": [KG + "test_embed_ln_with_audio_override", KG + "test_embedding_backward_in_id_order_is_reproducible_and_matches_autograd"],
+    "cm3p_layernorm_fwd": [KG + "test_layernorm_fwd_bwd", CH + "test_layernorm_with_many_rows_per_wave",
+                           RK + "test_layernorm_forward_every_instance_and_output_form", RK + "test_layernorm_forward_on_rows_that_break_a_careless_variance"],
+    "cm3p_layernorm_bwd": [KG + "test_layernorm_fwd_bwd", CH + "test_layernorm_with_many_rows_per_wave",
+                           RK + "test_layernorm_backward_every_form"],
+    "cm3p_embed_ln_fwd": [KG + "test_embed_ln_with_audio_override",
+                          RK + "test_embed_ln_forward_is_layernorm_of_the_gathered_rows"],
+    "cm3p_embed_ln_bwd": [KG + "test_embed_ln_with_audio_override",
+                          RK + "test_embed_ln_backward_against_float64_autograd"],
+    "cm3p_embed_ln_bwd_sorted": [KG + "test_embed_ln_with_audio_override", KG + "test_embedding_backward_in_id_order_is_reproducible_and_matches_autograd",
+                                 RK + "test_embed_ln_backward_against_float64_autograd"],
     "cm3p_token_order": [KG + "test_token_order_is_the_stable_sort_of_the_ids"],
-    "cm3p_audio_slots": [KG + "test_embed_ln_with_audio_override"],
+    "cm3p_audio_slots": [KG + "test_embed_ln_with_audio_override",
+                         RK + "test_audio_slots_is_the_exclusive_cumsum"],
     "cm3p_gemm_bf16": [KG + "test_gemm_forward_layout", KG + "test_gemm_dgrad_layout", KG + "test_gemm_wgrad_layout",
                        KG + "test_gemm256_forward_and_dgrad_layout", KG + "test_gemm256_wgrad_layout", KG + "test_gemm_bias_epilogue"],
     "cm3p_gemm8p_set_grid": [KG + "test_ring_gemm_with_more_workgroups_than_cus_is_the_same_gemm"],
@@ -32,8 +39,10 @@ LEDGER = {
     "cm3p_cast_f32_bf16_t": [KG + "test_cast_with_transpose"],
     "cm3p_cast_f32_bf16_t_multi": [KG + "test_cast_with_transpose_of_many_matrices_in_one_launch"],
     "cm3p_add_f32": [CH + "test_add_f32_is_the_fp32_add_then_rne", CH + "test_add_f32_with_no_elements"],
-    "cm3p_rope_table": [KG + "test_rope_matches_reference_formula"],
-    "cm3p_rope_apply": [KG + "test_rope_matches_reference_formula"],
+    "cm3p_rope_table": [KG + "test_rope_matches_reference_formula",
+                        RK + "test_rope_table_is_cos_sin_of_the_fp32_product"],
+    "cm3p_rope_apply": [KG + "test_rope_matches_reference_formula",
+                        RK + "test_rope_apply_against_the_float64_rotation"],
     "cm3p_attn_fwd": [KG + "test_attention_global_nopad", KG + "test_attention_random_shapes", KG + "test_attention_sliding_window"],
     "cm3p_attn_probs": [MG + "test_output_attentions_matches_the_reference_eager_probabilities"],
     "cm3p_attn_bwd": [KG + "test_attention_global_backward_both_implementations", KG + "test_attention_random_shapes"],
@@ -41,28 +50,35 @@ LEDGER = {
     "cm3p_attn_bwd_generic": [KG + "test_generic_attention_matches_fp32_reference"],
     "cm3p_attn_fwd_generic_dropout": [DR + "test_generic_attention_dropout_matches_fp32_restatement"],
     "cm3p_attn_bwd_generic_dropout": [DR + "test_generic_attention_dropout_matches_fp32_restatement"],
-    "cm3p_rope_apply_generic": [KG + "test_generic_rope_is_the_reference_rotation_and_its_transpose"],
+    "cm3p_rope_apply_generic": [KG + "test_generic_rope_is_the_reference_rotation_and_its_transpose",
+                                RK + "test_rope_apply_against_the_float64_rotation"],
     "cm3p_attn_bwd_fused": [KG + "test_attention_global_backward_both_implementations"],
     "cm3p_attn_fwd_dropout": [DR + "test_attention_dropout_matches_fp32_restatement"],
     "cm3p_attn_bwd_dropout": [DR + "test_attention_dropout_matches_fp32_restatement"],
     "cm3p_attn_fwd_dropout_varlen": [DR + "test_attention_dropout_varlen_equals_padded"],
     "cm3p_attn_bwd_dropout_varlen": [DR + "test_attention_dropout_varlen_equals_padded"],
-    "cm3p_geglu_fwd": [KG + "test_geglu_and_gelu"],
+    "cm3p_geglu_fwd": [KG + "test_geglu_and_gelu",
+                       RK + "test_geglu_against_float64"],
     "cm3p_gemm_geglu": [KG + "test_wi_gemm_with_geglu_in_its_store_phase_equals_the_two_kernels"],
-    "cm3p_geglu_bwd": [KG + "test_geglu_and_gelu"],
+    "cm3p_geglu_bwd": [KG + "test_geglu_and_gelu",
+                       RK + "test_geglu_against_float64"],
     "cm3p_dropout_f32": [DR + "test_dropout_f32_matches_the_mask_and_packed_equals_padded"],
     "cm3p_geglu_fwd_dropout": [DR + "test_geglu_dropout_forward_and_backward"],
     "cm3p_geglu_bwd_dropout": [DR + "test_geglu_dropout_forward_and_backward"],
     "cm3p_dropout_keep": [DR + "test_materialiser_equals_the_restatement"],
     "cm3p_philox4x32_10_host": ["tests/test_dropout_host.py::test_philox_known_answers", "tests/test_dropout_host.py::test_philox_matches_python_restatement"],
-    "cm3p_gelu_fwd": [KG + "test_gelu_on_every_finite_bf16_input_against_float64"],
-    "cm3p_gelu_bwd": [KG + "test_gelu_on_every_finite_bf16_input_against_float64"],
+    "cm3p_gelu_fwd": [KG + "test_gelu_on_every_finite_bf16_input_against_float64",
+                      RK + "test_gelu_element_kernels_past_the_grid"],
+    "cm3p_gelu_bwd": [KG + "test_gelu_on_every_finite_bf16_input_against_float64",
+                      RK + "test_gelu_element_kernels_past_the_grid"],
     "cm3p_im2col_k3": [CH + "test_im2col_is_the_padded_gather_bit_for_bit", CH + "test_conv_front_end_refuses_what_it_cannot_do"],
     "cm3p_col2im_k3": [CH + "test_col2im_is_the_ordered_sum_and_the_adjoint_of_im2col", CH + "test_conv_gelu_stages_against_float64"],
     "cm3p_bias_gelu_fwd": [CH + "test_bias_gelu_forward_against_float64", CH + "test_conv_gelu_stages_against_float64"],
     "cm3p_bias_gelu_bwd": [CH + "test_bias_gelu_backward_against_float64"],
-    "cm3p_pool_fwd": [KG + "test_pooling"],
-    "cm3p_pool_bwd": [KG + "test_pooling"],
+    "cm3p_pool_fwd": [KG + "test_pooling",
+                      RK + "test_pooling_against_float64"],
+    "cm3p_pool_bwd": [KG + "test_pooling",
+                      RK + "test_pooling_against_float64"],
     "cm3p_gemm_f32": [CH + "test_gemm_f32_all_stride_forms", KG + "test_head_kernels"],
     "cm3p_l2norm_fwd": [KG + "test_head_kernels"],
     "cm3p_l2norm_bwd": [KG + "test_head_kernels"],
@@ -81,8 +97,10 @@ LEDGER = {
     "cm3p_first_zero_index": [KG + "test_head_kernels"],
     "cm3p_attn_fwd_varlen": [KG + "test_attention_varlen_equals_padded_on_valid_rows"],
     "cm3p_attn_bwd_varlen": [KG + "test_attention_varlen_equals_padded_on_valid_rows"],
-    "cm3p_gather_rows_f32": [KG + "test_gather_scatter_rows"],
-    "cm3p_scatter_rows_f32": [KG + "test_gather_scatter_rows"],
+    "cm3p_gather_rows_f32": [KG + "test_gather_scatter_rows",
+                             RK + "test_gather_and_scatter_rows_bit_for_bit"],
+    "cm3p_scatter_rows_f32": [KG + "test_gather_scatter_rows",
+                              RK + "test_gather_and_scatter_rows_bit_for_bit"],
     "cm3p_gemm_bf16_batched": [MU + "test_batched_gemm_axpby"],
     "cm3p_muon_partials": [MU + "test_steps_match_the_reference_fixture", MU + "test_model_sized_group_against_the_oracle"],
     "cm3p_muon_momentum": [MU + "test_steps_match_the_reference_fixture", MU + "test_model_sized_group_against_the_oracle"],

@@ -160,6 +160,7 @@ def test_layernorm_fwd_bwd(K, rows, H):
     _assert_close(y16, y.detach().to(torch.bfloat16), 1e-4, 8e-3, "ln y bf16")  # one bf16 ulp
     dx32, dx16, dw = K.layernorm_bwd(dy.to(DEV), x.to(DEV), w.to(DEV), mean, rstd, dres.to(DEV), True)
     _assert_close(dx32, xr.grad + dres, 5e-5, 1e-5, "ln dx")
+    assert torch.equal(dx16.cpu(), dx32.cpu().to(torch.bfloat16))  # the bf16 copy is the RNE rounding of the same call's dx_f32
     _assert_close(dw, wr.grad, 2e-4 * math.sqrt(rows), 1e-5, "ln dw")
     # bf16 dy path
     dy16 = _bf(dy)
