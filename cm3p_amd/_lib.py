@@ -13,8 +13,9 @@ from ctypes import c_float, c_int, c_int64, c_uint64, c_void_p
 import torch
 
 F32, BF16 = 0, 1
+ADD_A_BF16 = 16  # cm3p_add_f32: or-ed into b_dtype when the first operand (and the result) is bf16
 EPI_BF16, EPI_F32, EPI_F32_RESID, EPI_F32_BIAS, EPI_BF16_RESID = 0, 1, 2, 5, 7
-ABI_VERSION = 18
+ABI_VERSION = 19
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("CM3P_HIP_LIB") or os.path.join(_HERE, "csrc", "libcm3p_hip.so")  # env override: kernel experiments
@@ -27,11 +28,11 @@ SIGNATURES = {
     "cm3p_abi_version": [],
     "cm3p_layernorm_fwd": [_P, _I, _P, _P, _P, _P, _P, _L, _I, _F, _P],
     "cm3p_layernorm_bwd_blocks": [_L],
-    "cm3p_layernorm_bwd": [_P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _L, _I, _P],
+    "cm3p_layernorm_bwd": [_P, _I, _P, _I, _P, _P, _P, _P, _I, _P, _P, _P, _P, _L, _I, _P],
     "cm3p_embed_ln_fwd": [_P, _P, _I, _P, _P, _I, _P, _P, _P, _P, _P, _L, _I, _F, _L, _P],
-    "cm3p_embed_ln_bwd": [_P, _P, _P, _I, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _L, _I, _L, _L, _P],
+    "cm3p_embed_ln_bwd": [_P, _I, _P, _P, _I, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _L, _I, _L, _L, _P],
     "cm3p_embed_ln_bwd_sorted_chunk": [],
-    "cm3p_embed_ln_bwd_sorted": [_P, _P, _P, _P, _P, _I, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _L, _I, _L, _L, _P],
+    "cm3p_embed_ln_bwd_sorted": [_P, _I, _P, _P, _P, _P, _I, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _L, _I, _L, _L, _P],
     "cm3p_token_order_workspace_ints": [_L, _L],
     "cm3p_token_order": [_P, _L, _L, _P, _P, _P, _P],
     "cm3p_audio_slots": [_P, _L, _L, _P, _P, _P],
@@ -79,7 +80,7 @@ SIGNATURES = {
     "cm3p_bias_gelu_bwd": [_P, _I, _P, _P, _P, _P, _P, _L, _I, _P],
     "cm3p_pool_chunks": [_I],
     "cm3p_pool_fwd": [_P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _P],
-    "cm3p_pool_bwd": [_P, _P, _P, _P, _I, _I, _I, _I, _P],
+    "cm3p_pool_bwd": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
     "cm3p_gemm_f32": [_P, _P, _P, _I, _I, _I, _L, _L, _L, _L, _L, _F, _I, _P],
     "cm3p_l2norm_fwd": [_P, _P, _P, _I, _I, _P],
     "cm3p_l2norm_bwd": [_P, _P, _P, _P, _I, _I, _P],

@@ -9,7 +9,7 @@ from __future__ import annotations
 import torch
 
 from . import kernels as K
-from ._lib import EPI_F32
+from ._lib import EPI_BF16, EPI_F32
 from .encoder import _bf16_weight, _f32
 
 Tensor = torch.Tensor
@@ -77,6 +77,7 @@ class _ProjectorFn(torch.autograd.Function):
         R, D = a1.shape
         out = K.gemm(a1, W2b, R, W2b.shape[0], D, True, True, EPI_F32)
         ctx.pack = (hb, W1b, W2b, z1, a1, W1.dtype, W2.dtype)
+        ctx.hdtype = h.dtype
         return out
 
     @staticmethod
@@ -87,7 +88,8 @@ class _ProjectorFn(torch.autograd.Function):
         dW2 = K.linear_wgrad(dob, a1)
         dz1 = K.gelu_bwd(da1, z1)
         R, Kin = hb.shape
-        dh = K.gemm(dz1, W1b, R, Kin, dz1.shape[1], True, False, EPI_F32) if ctx.needs_input_grad[0] else None
+        # (rows of a bf16 residual stream take their gradient in bf16: the dgrad GEMM stores it)
+        dh = K.gemm(dz1, W1b, R, Kin, dz1.shape[1], True, False, EPI_BF16 if ctx.hdtype == torch.bfloat16 else EPI_F32) if ctx.needs_input_grad[0] else None
         dW1 = K.linear_wgrad(dz1, hb)
         return dh, dW1.to(d1), dW2.to(d2)
 

@@ -127,6 +127,23 @@ __global__ __launch_bounds__(256) void add_f32_kernel(const float* __restrict__ 
     }
 }
 
+// y = bf16(a + b) for a bf16 `a` (the residual-stream gradient of a bf16 training step at layer 0): the sum in fp32, one rounding.
+// y may alias a.
+template <bool B_BF16>
+__global__ __launch_bounds__(256) void add_bf16_kernel(const uint16_t* a, const void* __restrict__ b, uint16_t* y, int64_t n4) {
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) {
+        const uint2 wa = reinterpret_cast<const uint2*>(a)[i];
+        f32x4 v = f32x4{bf16lo(wa.x), bf16hi(wa.x), bf16lo(wa.y), bf16hi(wa.y)};
+        if constexpr (B_BF16) {
+            const uint2 w = reinterpret_cast<const uint2*>(b)[i];
+            v += f32x4{bf16lo(w.x), bf16hi(w.x), bf16lo(w.y), bf16hi(w.y)};
+        } else {
+            v += reinterpret_cast<const f32x4*>(b)[i];
+        }
+        reinterpret_cast<uint2*>(y)[i] = uint2{pack_bf16x2(v.x, v.y), pack_bf16x2(v.z, v.w)};
+    }
+}
+
 // ---- RoPE ---------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void rope_table_kernel(const int64_t* __restrict__ pos, const float* __restrict__ inv_freq,
                                                          float* __restrict__ cos_out, float* __restrict__ sin_out, int64_t n,
@@ -508,8 +525,9 @@ __global__ __launch_bounds__(256) void pool_cls_kernel(const T* __restrict__ h, 
     for (int col = threadIdx.x; col < H; col += 256) pooled[(int64_t)b * H + col] = to_f32(h[(int64_t)b * S * H + col]);
 }
 
+template <bool DH_BF16>
 __global__ __launch_bounds__(256) void pool_bwd_kernel(const float* __restrict__ dpooled, const int64_t* __restrict__ mask,
-                                                       const float* __restrict__ count, float* __restrict__ dh, int Bn, int S,
+                                                       const float* __restrict__ count, void* __restrict__ dh, int Bn, int S,
                                                        int H, int cls) {
     const int h4 = H / 4;
     const int64_t total = (int64_t)Bn * S * h4;
@@ -522,7 +540,11 @@ __global__ __launch_bounds__(256) void pool_bwd_kernel(const float* __restrict__
         else if (mask) scale = (float)mask[row] / fmaxf(count[b], 1e-9f);
         else scale = 1.0f / (float)S;
         const f32x4 g = *reinterpret_cast<const f32x4*>(dpooled + b * H + col);
-        *reinterpret_cast<f32x4*>(dh + row * H + col) = g * scale;
+        const f32x4 d = g * scale;
+        if constexpr (DH_BF16)  // (the bf16 residual stream of a training step: the gradient in the stream's dtype, one rounding)
+            *reinterpret_cast<uint2*>(static_cast<uint16_t*>(dh) + row * H + col) = uint2{pack_bf16x2(d.x, d.y), pack_bf16x2(d.z, d.w)};
+        else
+            *reinterpret_cast<f32x4*>(static_cast<float*>(dh) + row * H + col) = d;
     }
 }
 
@@ -570,12 +592,22 @@ int cm3p_cast_f32_bf16_t_multi(const int64_t* table, int n, int64_t total_blocks
     return CM3P_OK;
 }
 
-int cm3p_add_f32(const float* a, const void* b, int b_dtype, float* y_f32, void* y_bf16, int64_t n, void* stream) {
+int cm3p_add_f32(const void* a, const void* b, int b_dtype, float* y_f32, void* y_bf16, int64_t n, void* stream) {
     CM3P_REQUIRE(a && b && (y_f32 || y_bf16) && n >= 0 && n % 4 == 0);
+    CM3P_REQUIRE((b_dtype & ~(CM3P_ADD_A_BF16 | CM3P_BF16)) == 0);
+    if (b_dtype & CM3P_ADD_A_BF16) {  // bf16 first operand: the bf16 result alone
+        CM3P_REQUIRE(!y_f32 && y_bf16);
+        if (n == 0) return CM3P_OK;
+        hipStream_t s = static_cast<hipStream_t>(stream);
+        if (b_dtype & CM3P_BF16) add_bf16_kernel<true><<<ew_grid(n / 4), 256, 0, s>>>((const uint16_t*)a, b, (uint16_t*)y_bf16, n / 4);
+        else add_bf16_kernel<false><<<ew_grid(n / 4), 256, 0, s>>>((const uint16_t*)a, b, (uint16_t*)y_bf16, n / 4);
+        CM3P_LAUNCH_CHECK();
+        return CM3P_OK;
+    }
     if (n == 0) return CM3P_OK;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (b_dtype == CM3P_BF16) add_f32_kernel<true><<<ew_grid(n / 4), 256, 0, s>>>(a, b, y_f32, (uint16_t*)y_bf16, n / 4);
-    else add_f32_kernel<false><<<ew_grid(n / 4), 256, 0, s>>>(a, b, y_f32, (uint16_t*)y_bf16, n / 4);
+    if (b_dtype == CM3P_BF16) add_f32_kernel<true><<<ew_grid(n / 4), 256, 0, s>>>((const float*)a, b, y_f32, (uint16_t*)y_bf16, n / 4);
+    else add_f32_kernel<false><<<ew_grid(n / 4), 256, 0, s>>>((const float*)a, b, y_f32, (uint16_t*)y_bf16, n / 4);
     CM3P_LAUNCH_CHECK();
     return CM3P_OK;
 }
@@ -735,12 +767,15 @@ int cm3p_pool_fwd(const void* h, int h_dtype, const int64_t* mask, float* pooled
     return CM3P_OK;
 }
 
-int cm3p_pool_bwd(const float* dpooled, const int64_t* mask, const float* count, float* dh, int Bn, int S, int H, int cls,
+int cm3p_pool_bwd(const float* dpooled, const int64_t* mask, const float* count, void* dh, int dh_dtype, int Bn, int S, int H, int cls,
                   void* stream) {
     CM3P_REQUIRE(dpooled && dh && Bn > 0 && S > 0 && H > 0 && H % 4 == 0);
     CM3P_REQUIRE(cls || !mask || count);
-    pool_bwd_kernel<<<ew_grid((int64_t)Bn * S * (H / 4)), 256, 0, static_cast<hipStream_t>(stream)>>>(dpooled, mask, count, dh,
-                                                                                                      Bn, S, H, cls);
+    CM3P_REQUIRE(dh_dtype == CM3P_F32 || dh_dtype == CM3P_BF16);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int grid = ew_grid((int64_t)Bn * S * (H / 4));
+    if (dh_dtype == CM3P_BF16) pool_bwd_kernel<true><<<grid, 256, 0, s>>>(dpooled, mask, count, dh, Bn, S, H, cls);
+    else pool_bwd_kernel<false><<<grid, 256, 0, s>>>(dpooled, mask, count, dh, Bn, S, H, cls);
     CM3P_LAUNCH_CHECK();
     return CM3P_OK;
 }

@@ -168,6 +168,81 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const void* __restri
     }
 }
 
+// The same backward for the bf16 residual stream of a training step: x and / or the incoming residual gradient are bf16 rows, and with
+// dx32 == nullptr the only output is bf16(dres + LN'(dy)) - the sum is formed in fp32 and rounded ONCE (a bf16 torch model rounds LN'(dy)
+// and the sum separately).  8 bytes per element (dy, x, dres in, dx out) where the fp32 stream moves 16 and more.  Statistics, the row
+// reductions and the dw partial sums are fp32 in the order of the kernel above, so dw differs from it only through the rounded inputs.
+// dx16 may alias dres: every lane reads its four columns of a row before it writes them.
+// The body restates layernorm_bwd_kernel (whose instances keep their code, so that no bit of the fp32 stream can move): a fix to one
+// of the two kernels must be made in the other.  The stack launches <true, true, true, NC>; the other dtype forms serve the entry point.
+template <bool DY_BF16, bool X_BF16, bool RES_BF16, int NC>
+__global__ __launch_bounds__(256) void layernorm_bwd_s16_kernel(const void* __restrict__ dy, const void* __restrict__ x,
+                                                                const float* __restrict__ w, const float* __restrict__ mean_in,
+                                                                const float* __restrict__ rstd_in, const void* dres, float* dx32,
+                                                                uint16_t* dx16, float* __restrict__ dw_partial, int64_t rows, int H) {
+    extern __shared__ __attribute__((aligned(16))) float dw_lds[];  // [4][H]
+    const int lane = threadIdx.x & 63;
+    const int wid = threadIdx.x >> 6;
+    const int64_t wave = (int64_t)blockIdx.x * 4 + wid;
+    const int64_t nwaves = (int64_t)gridDim.x * 4;
+    RowRegs<NC> dw;
+#pragma unroll
+    for (int c = 0; c < NC; ++c) dw.v[c] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+    for (int64_t row = wave; row < rows; row += nwaves) {
+        RowRegs<NC> xr, gr, rr;
+        const void* xsrc = X_BF16 ? (const void*)(static_cast<const uint16_t*>(x) + row * H)
+                                  : (const void*)(static_cast<const float*>(x) + row * H);
+        load_row<X_BF16, NC>(xr, xsrc, H, lane);
+        const void* dsrc = DY_BF16 ? (const void*)(static_cast<const uint16_t*>(dy) + row * H)
+                                   : (const void*)(static_cast<const float*>(dy) + row * H);
+        load_row<DY_BF16, NC>(gr, dsrc, H, lane);
+        if (dres) {  // (requested with the row, as above)
+            const void* rsrc = RES_BF16 ? (const void*)(static_cast<const uint16_t*>(dres) + row * H)
+                                        : (const void*)(static_cast<const float*>(dres) + row * H);
+            load_row<RES_BF16, NC>(rr, rsrc, H, lane);
+        }
+        const float mean = mean_in[row], rstd = rstd_in[row];
+        float s1 = 0.f, s2 = 0.f;
+#pragma unroll
+        for (int c = 0; c < NC; ++c) {
+            const int col = c * 256 + lane * 4;
+            if (col < H) {
+                const f32x4 xhat = (xr.v[c] - mean) * rstd;
+                const f32x4 wv = *reinterpret_cast<const f32x4*>(w + col);
+                dw.v[c] += gr.v[c] * xhat;
+                const f32x4 g = gr.v[c] * wv;
+                xr.v[c] = xhat;
+                gr.v[c] = g;
+                s1 += (g.x + g.y) + (g.z + g.w);
+                const f32x4 gx = g * xhat;
+                s2 += (gx.x + gx.y) + (gx.z + gx.w);
+            }
+        }
+        s1 = wave_sum(s1) / (float)H;
+        s2 = wave_sum(s2) / (float)H;
+#pragma unroll
+        for (int c = 0; c < NC; ++c) {
+            const int col = c * 256 + lane * 4;
+            if (col < H) {
+                f32x4 d = (gr.v[c] - s1 - xr.v[c] * s2) * rstd;
+                if (dres) d += rr.v[c];
+                if (dx32) gstore16f<(CM3P_NT & 16) != 0>(dx32 + row * H + col, d);
+                if (dx16) gstore8<(CM3P_NT & 16) != 0>(dx16 + row * H + col, uint2{pack_bf16x2(d.x, d.y), pack_bf16x2(d.z, d.w)});
+            }
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < NC; ++c) {
+        const int col = c * 256 + lane * 4;
+        if (col < H) *reinterpret_cast<f32x4*>(dw_lds + wid * H + col) = dw.v[c];
+    }
+    __syncthreads();
+    for (int col = threadIdx.x; col < H; col += 256) {
+        dw_partial[(int64_t)blockIdx.x * H + col] = (dw_lds[col] + dw_lds[H + col]) + (dw_lds[2 * H + col] + dw_lds[3 * H + col]);
+    }
+}
+
 // out[col] = sum_b partial[b][col], fixed summation order.  Block = 32 columns x 32 row slices (1024 threads: the 24 workgroups
 // this launch has at H = 768 sit between two kernels of the backward chain, so its time is the depth of its dependent load rounds -
 // 4 rounds of 8 loads per thread at 1024 partial rows, 16 in the 8-slice form of r01-r03: 17.6 -> ~6 us per launch);
@@ -250,8 +325,8 @@ __global__ __launch_bounds__(256) void embed_ln_fwd_kernel(const int64_t* __rest
 // Backward of the gather + LayerNorm: LayerNorm backward on the re-gathered row, then the row gradient is
 // scattered: atomically added into d_table[ids[t]] (several tokens share a row) or stored to d_override[slot[t]]
 // (each audio row is used exactly once).
-template <bool TAB_BF16, bool OVR_BF16, int NC>
-__global__ __launch_bounds__(256) void embed_ln_bwd_kernel(const float* __restrict__ dy, const int64_t* __restrict__ ids,
+template <bool TAB_BF16, bool OVR_BF16, int NC, bool DY_BF16 = false>
+__global__ __launch_bounds__(256) void embed_ln_bwd_kernel(const void* __restrict__ dy, const int64_t* __restrict__ ids,
                                                            const void* __restrict__ table, const int32_t* __restrict__ slot,
                                                            const void* __restrict__ ovr, const float* __restrict__ w,
                                                            const float* __restrict__ mean_in, const float* __restrict__ rstd_in,
@@ -269,7 +344,8 @@ __global__ __launch_bounds__(256) void embed_ln_bwd_kernel(const float* __restri
     for (int64_t t = wave; t < T; t += nwaves) {
         RowRegs<NC> xr, gr;
         load_embed_row<TAB_BF16, OVR_BF16, NC>(xr, ids, table, slot, ovr, t, H, lane, vocab);
-        load_row<false, NC>(gr, dy + t * H, H, lane);
+        if constexpr (DY_BF16) load_row<true, NC>(gr, static_cast<const uint16_t*>(dy) + t * H, H, lane);  // (bf16 residual stream)
+        else load_row<false, NC>(gr, static_cast<const float*>(dy) + t * H, H, lane);
         const float mean = mean_in[t], rstd = rstd_in[t];
         float s1 = 0.f, s2 = 0.f;
 #pragma unroll
@@ -330,8 +406,8 @@ __global__ __launch_bounds__(256) void embed_ln_bwd_kernel(const float* __restri
 // is not), and tokens that share an id - most of a beatmap - no longer serialise on one row of d_table.
 constexpr int kEmbChunk = 64;
 
-template <bool TAB_BF16, bool OVR_BF16, int NC>
-__global__ __launch_bounds__(256) void embed_ln_bwd_sorted_kernel(const float* __restrict__ dy, const int64_t* __restrict__ ids,
+template <bool TAB_BF16, bool OVR_BF16, int NC, bool DY_BF16 = false>
+__global__ __launch_bounds__(256) void embed_ln_bwd_sorted_kernel(const void* __restrict__ dy, const int64_t* __restrict__ ids,
                                                                   const int64_t* __restrict__ order, const int32_t* __restrict__ run_of,
                                                                   const void* __restrict__ table, const int32_t* __restrict__ slot,
                                                                   const void* __restrict__ ovr, const float* __restrict__ w,
@@ -369,7 +445,8 @@ __global__ __launch_bounds__(256) void embed_ln_bwd_sorted_kernel(const float* _
         }
         RowRegs<NC> xr, gr;
         load_embed_row<TAB_BF16, OVR_BF16, NC>(xr, ids, table, slot, ovr, t, H, lane, vocab);
-        load_row<false, NC>(gr, dy + t * H, H, lane);
+        if constexpr (DY_BF16) load_row<true, NC>(gr, static_cast<const uint16_t*>(dy) + t * H, H, lane);  // (bf16 residual stream)
+        else load_row<false, NC>(gr, static_cast<const float*>(dy) + t * H, H, lane);
         const float mean = mean_in[t], rstd = rstd_in[t];
         float s1 = 0.f, s2 = 0.f;
 #pragma unroll
@@ -691,22 +768,43 @@ int cm3p_layernorm_fwd(const void* x, int x_dtype, const float* weight, float* y
 
 int cm3p_layernorm_bwd_blocks(int64_t rows) { return ln_bwd_grid(rows); }
 
-int cm3p_layernorm_bwd(const void* dy, int dy_dtype, const float* x, const float* weight, const float* mean, const float* rstd,
-                       const float* dres, float* dx_f32, void* dx_bf16, float* dw_partial, float* dw, int64_t rows, int H,
+int cm3p_layernorm_bwd(const void* dy, int dy_dtype, const void* x, int x_dtype, const float* weight, const float* mean, const float* rstd,
+                       const void* dres, int dres_dtype, float* dx_f32, void* dx_bf16, float* dw_partial, float* dw, int64_t rows, int H,
                        void* stream) {
     CM3P_REQUIRE(dy && x && weight && mean && rstd && dw_partial && dw && (dx_f32 || dx_bf16));
     CM3P_REQUIRE(rows > 0 && H > 0 && H % 4 == 0 && H <= 2048);
     CM3P_REQUIRE(dy_dtype == CM3P_F32 || dy_dtype == CM3P_BF16);
+    CM3P_REQUIRE(x_dtype == CM3P_F32 || x_dtype == CM3P_BF16);
+    CM3P_REQUIRE(!dres || dres_dtype == CM3P_F32 || dres_dtype == CM3P_BF16);
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int grid = ln_bwd_grid(rows);
     const size_t lds = (size_t)4 * H * sizeof(float);
+    const bool xb = x_dtype == CM3P_BF16, rb = dres && dres_dtype == CM3P_BF16;
+    if (!xb && !rb) {  // the fp32 residual stream: the instances it has always run
+        const float* x32 = static_cast<const float*>(x);
+        const float* r32 = static_cast<const float*>(dres);
 #define CM3P_LN_BWD(NC)                                                                                                      \
     if (dy_dtype == CM3P_BF16)                                                                                               \
-        layernorm_bwd_kernel<true, NC><<<grid, 256, lds, s>>>(dy, x, weight, mean, rstd, dres, dx_f32, (uint16_t*)dx_bf16, dw_partial, rows, H); \
+        layernorm_bwd_kernel<true, NC><<<grid, 256, lds, s>>>(dy, x32, weight, mean, rstd, r32, dx_f32, (uint16_t*)dx_bf16, dw_partial, rows, H); \
     else                                                                                                                     \
-        layernorm_bwd_kernel<false, NC><<<grid, 256, lds, s>>>(dy, x, weight, mean, rstd, dres, dx_f32, (uint16_t*)dx_bf16, dw_partial, rows, H);
-    CM3P_NC_SWITCH(H, CM3P_LN_BWD)
+        layernorm_bwd_kernel<false, NC><<<grid, 256, lds, s>>>(dy, x32, weight, mean, rstd, r32, dx_f32, (uint16_t*)dx_bf16, dw_partial, rows, H);
+        CM3P_NC_SWITCH(H, CM3P_LN_BWD)
 #undef CM3P_LN_BWD
+    } else {  // bf16 rows on the stream (x, the residual gradient, or both)
+        const bool db = dy_dtype == CM3P_BF16;
+#define CM3P_LN_BWD_NC(NC) \
+    layernorm_bwd_s16_kernel<DB_, XB_, RB_, NC><<<grid, 256, lds, s>>>(dy, x, weight, mean, rstd, dres, dx_f32, (uint16_t*)dx_bf16, dw_partial, rows, H);
+#define CM3P_LN_BWD_S16(DB, XB, RB)                   \
+    do {                                              \
+        constexpr bool DB_ = DB, XB_ = XB, RB_ = RB;  \
+        CM3P_NC_SWITCH(H, CM3P_LN_BWD_NC)             \
+    } while (0)
+        if (xb && rb) { if (db) CM3P_LN_BWD_S16(true, true, true); else CM3P_LN_BWD_S16(false, true, true); }
+        else if (xb) { if (db) CM3P_LN_BWD_S16(true, true, false); else CM3P_LN_BWD_S16(false, true, false); }
+        else { if (db) CM3P_LN_BWD_S16(true, false, true); else CM3P_LN_BWD_S16(false, false, true); }
+#undef CM3P_LN_BWD_S16
+#undef CM3P_LN_BWD_NC
+    }
     CM3P_LAUNCH_CHECK();
     colsum_kernel<<<(H + 31) / 32, 1024, 0, s>>>(dw_partial, dw, grid, H);
     CM3P_LAUNCH_CHECK();
@@ -739,19 +837,24 @@ int cm3p_embed_ln_fwd(const int64_t* ids, const void* table, int table_dtype, co
     return CM3P_OK;
 }
 
-int cm3p_embed_ln_bwd(const float* dy, const int64_t* ids, const void* table, int table_dtype, const int32_t* slot,
+int cm3p_embed_ln_bwd(const void* dy, int dy_dtype, const int64_t* ids, const void* table, int table_dtype, const int32_t* slot,
                       const void* override_rows, int override_dtype, const float* weight, const float* mean, const float* rstd,
                       float* d_table, float* d_override, float* dw_partial, float* dw, int64_t T, int H, int64_t padding_idx,
                       int64_t vocab, void* stream) {
     CM3P_REQUIRE(dy && ids && table && weight && mean && rstd && dw_partial && dw && T > 0 && H > 0 && H % 4 == 0 && H <= 2048);
     CM3P_REQUIRE((slot == nullptr) == (override_rows == nullptr));
+    CM3P_REQUIRE(dy_dtype == CM3P_F32 || dy_dtype == CM3P_BF16);
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int grid = ln_bwd_grid(T);
     const size_t lds = (size_t)4 * H * sizeof(float);
     const bool tb = table_dtype == CM3P_BF16, ob = override_dtype == CM3P_BF16;
-#define CM3P_EMB_BWD_NC(NC)                                                                                              \
-    embed_ln_bwd_kernel<TB_, OB_, NC><<<grid, 256, lds, s>>>(dy, ids, table, slot, override_rows, weight, mean, rstd, d_table, \
-                                                             d_override, dw_partial, T, H, padding_idx, vocab);
+#define CM3P_EMB_BWD_NC(NC)                                                                                                         \
+    if (dy_dtype == CM3P_BF16)                                                                                                      \
+        embed_ln_bwd_kernel<TB_, OB_, NC, true><<<grid, 256, lds, s>>>(dy, ids, table, slot, override_rows, weight, mean, rstd, d_table, \
+                                                                       d_override, dw_partial, T, H, padding_idx, vocab);          \
+    else                                                                                                                            \
+        embed_ln_bwd_kernel<TB_, OB_, NC><<<grid, 256, lds, s>>>(dy, ids, table, slot, override_rows, weight, mean, rstd, d_table,  \
+                                                                 d_override, dw_partial, T, H, padding_idx, vocab);
 #define CM3P_EMB_BWD(TB, OB)               \
     do {                                   \
         constexpr bool TB_ = TB, OB_ = OB; \
@@ -771,21 +874,26 @@ int cm3p_embed_ln_bwd(const float* dy, const int64_t* ids, const void* table, in
 
 int cm3p_embed_ln_bwd_sorted_chunk(void) { return kEmbChunk; }
 
-int cm3p_embed_ln_bwd_sorted(const float* dy, const int64_t* ids, const int64_t* order, const int32_t* run_of, const void* table,
+int cm3p_embed_ln_bwd_sorted(const void* dy, int dy_dtype, const int64_t* ids, const int64_t* order, const int32_t* run_of, const void* table,
                              int table_dtype, const int32_t* slot, const void* override_rows, int override_dtype, const float* weight,
                              const float* mean, const float* rstd, float* d_table, float* d_override, float* run_rows, int64_t* run_ids,
                              float* dw_partial, float* dw, int64_t T, int H, int64_t padding_idx, int64_t vocab, void* stream) {
     CM3P_REQUIRE(dy && ids && order && run_of && table && weight && mean && rstd && d_table && run_rows && run_ids && dw_partial && dw);
     CM3P_REQUIRE(T > 0 && H > 0 && H % 4 == 0 && H <= 2048 && vocab > 0);
     CM3P_REQUIRE((slot == nullptr) == (override_rows == nullptr));
+    CM3P_REQUIRE(dy_dtype == CM3P_F32 || dy_dtype == CM3P_BF16);
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int64_t chunks = (T + kEmbChunk - 1) / kEmbChunk;
     const int grid = (int)((chunks + 3) / 4);
     const size_t lds = (size_t)4 * H * sizeof(float);
     const bool tb = table_dtype == CM3P_BF16, ob = override_dtype == CM3P_BF16;
-#define CM3P_EMB_SORT_NC(NC)                                                                                                       \
-    embed_ln_bwd_sorted_kernel<TB_, OB_, NC><<<grid, 256, lds, s>>>(dy, ids, order, run_of, table, slot, override_rows, weight, mean, \
-                                                                    rstd, d_override, run_rows, run_ids, dw_partial, T, H, padding_idx, vocab);
+#define CM3P_EMB_SORT_NC(NC)                                                                                                              \
+    if (dy_dtype == CM3P_BF16)                                                                                                            \
+        embed_ln_bwd_sorted_kernel<TB_, OB_, NC, true><<<grid, 256, lds, s>>>(dy, ids, order, run_of, table, slot, override_rows, weight, mean, \
+                                                                              rstd, d_override, run_rows, run_ids, dw_partial, T, H, padding_idx, vocab); \
+    else                                                                                                                                  \
+        embed_ln_bwd_sorted_kernel<TB_, OB_, NC><<<grid, 256, lds, s>>>(dy, ids, order, run_of, table, slot, override_rows, weight, mean,  \
+                                                                        rstd, d_override, run_rows, run_ids, dw_partial, T, H, padding_idx, vocab);
 #define CM3P_EMB_SORT(TB, OB)               \
     do {                                    \
         constexpr bool TB_ = TB, OB_ = OB;  \

@@ -22,7 +22,16 @@ the residual add, and gelu(h[:I]) * h[I:] before Wo - the masks follow csrc/drop
 bf16 residual stream (opt-in, `CM3PEncoder.residual_dtype = torch.bfloat16`): a forward-only call (nothing recorded for a backward,
 no dropout plan) keeps the stream in bf16 the way a bf16 ModernBERT does (TF:...modeling_modernbert.py:68-70,331-332,476): every
 LayerNorm reads and writes bf16, `x + o Wo^T` and `x + g Wo^T` are bf16 adds of the bf16-rounded projection (CM3P_EPI_BF16_RESID),
-last_hidden_state and hidden_states are bf16.  Every other call runs the fp32 stream whatever the switch says.
+last_hidden_state and hidden_states are bf16.  Every other call runs the fp32 stream whatever that switch says.
+
+bf16 residual stream of a training step (opt-in, its own switch: `CM3PEncoder.train_residual_dtype = torch.bfloat16`, or
+`model.set_residual_dtype(torch.bfloat16, training=True)`): a call that records a backward and has no dropout plan runs the forward
+above (the same kernels; LayerNorm also writes its fp32 mean / rstd, and a layer keeps x and x_mid as bf16) and a backward whose
+residual-stream gradient is ONE bf16 tensor: LayerNorm backward reads dy, x and the incoming gradient g in bf16 and writes
+bf16(g + LN'(dy)), the sum formed in fp32 and rounded once (8 bytes per element where the fp32 stream moves 16 and more).
+Statistics, dw partial sums, softmax and GEMM accumulation stay fp32; weight gradients come out of the wgrad GEMMs in fp32 and are cast to
+the parameter's dtype as on the fp32 stream.  With a dropout plan (train mode, any p > 0) the fp32 stream runs: the dropout sites have
+no bf16 form.
 """
 from __future__ import annotations
 
@@ -160,7 +169,8 @@ class _Geometry:
 
 
 def _hand_upstream(geo: _Geometry, gx32: Tensor, gx16: Optional[Tensor]) -> None:
-    """A node's backward leaves the bf16 twin of the fp32 gradient it returns here; the node below (the next one the autograd
+    """(bf16 residual stream: the ONE bf16 gradient is handed up in both places, (g, g); _take_bf16_from_downstream reads the first.)
+    A node's backward leaves the bf16 twin of the fp32 gradient it returns here; the node below (the next one the autograd
     engine runs on this chain) picks it up instead of re-reading 4 bytes per element to cast it again."""
     geo.handoff = (gx32, gx16)
 
@@ -178,6 +188,19 @@ def _take_from_downstream(geo: _Geometry, dy: Tensor):
     if g.data_ptr() == dy.data_ptr():
         g = g.clone()
     return g, K.cast_bf16(g)
+
+
+def _take_bf16_from_downstream(geo: _Geometry, dy: Tensor) -> Tensor:
+    """bf16 residual stream: -> the ONE bf16 gradient tensor this node may update in place.  The rule of _take_from_downstream: `dy`
+    is used as it is only when it is exactly the tensor the node above handed up; anything else (the gradient that enters the stack
+    from pooling or a head, a sum autograd formed for two consumers, a hook) gets a private copy."""
+    h, geo.handoff = geo.handoff, None
+    if h is not None and h[0].data_ptr() == dy.data_ptr() and h[0].shape == dy.shape and dy.dtype == torch.bfloat16 and dy.is_contiguous():
+        return h[0]
+    g = dy.to(torch.bfloat16).contiguous()
+    if g.data_ptr() == dy.data_ptr():
+        g = g.clone()
+    return g
 
 
 def _layer_forward(geo: _Geometry, i: int, x: Tensor, wb, want_stats: bool):
@@ -227,7 +250,7 @@ def _layer_forward(geo: _Geometry, i: int, x: Tensor, wb, want_stats: bool):
 
 class _EncoderLayerFn(torch.autograd.Function):
     """One ModernBERT encoder layer (TF:...modeling_modernbert.py:318-333): x [T,H] fp32 + its weights -> x_out [T,H] fp32
-    (bf16 -> bf16 on the bf16 residual stream of a forward-only call: the residual GEMMs take x's dtype).
+    (bf16 -> bf16 on the bf16 residual stream: the residual GEMMs take x's dtype; its backward is _backward_bf16).
 
     One autograd node per layer, so a layer's weight gradients reach their parameters (and a DistributedDataParallel
     bucket's all-reduce starts) while the layers below are still in backward.  The fp32 residual-stream gradient travels
@@ -256,7 +279,69 @@ class _EncoderLayerFn(torch.autograd.Function):
         return x_out
 
     @staticmethod
+    def _backward_bf16(ctx, dy: Tensor):
+        """The backward on the bf16 residual stream (train_residual_dtype; never with a dropout plan): the launch sequence of
+        backward() below with ONE bf16 gradient tensor g where that one carries an fp32 tensor and its bf16 twin.  g is what the
+        dgrad / wgrad GEMMs read, and each LayerNorm backward replaces it by bf16(g + LN'(dy)) - fp32 sum, one rounding (torch's bf16
+        LayerNorm backward rounds LN'(dy) first and the sum again; the single rounding is the more accurate of the two)."""
+        geo, i = ctx.geo, ctx.i
+        B, S, nh = geo.B, geo.S, geo.nh
+        scale = geo.hd ** -0.5
+        need = ctx.needs_input_grad  # (geo, i, x, *weights)
+        need_w = list(need[3:])
+        if i == 0:
+            need_w.insert(0, False)  # (no attn_norm in layer 0)
+        n_an, n_qkv, n_o, n_mn, n_i, n_o2 = need_w
+        g = _take_bf16_from_downstream(geo, dy)
+        if geo.checkpoint:
+            _, acts = _layer_forward(geo, i, ctx.saved[0], ctx.wb, True)
+        else:
+            acts = ctx.saved
+        x, xn, mean_a, rstd_a, qkv, o, lse, x_mid, xn2, mean_m, rstd_m, h, ga = acts
+        del acts
+        w_an, Wqkv_b, Wo_b, w_mn, Wi_b, Wo2_b = ctx.wb[:6]
+        Wqkv_t, Wo_t, Wi_t, Wo2_t = ctx.wt
+        ctx.saved = ctx.wb = ctx.wt = None  # release activations as we go
+        # ---- MLP branch: x_out = x_mid + g Wo2^T
+        dg = K.linear_dgrad(g, Wo2_b, Wo2_t)
+        dWo2 = K.linear_wgrad(g, ga) if n_o2 else None
+        dh = K.geglu_bwd(dg, h)
+        del dg, ga
+        dxn2 = K.linear_dgrad(dh, Wi_b, Wi_t)
+        dWi = K.linear_wgrad(dh, xn2) if n_i else None
+        del dh, h, xn2
+        _, g, dw_mn = K.layernorm_bwd(dxn2, x_mid, w_mn, mean_m, rstd_m, g, False, bf16_only=True)
+        del dxn2, x_mid
+        # ---- attention branch: x_mid = x + o Wo^T
+        do = K.linear_dgrad(g, Wo_b, Wo_t)
+        dWo = K.linear_wgrad(g, o) if n_o else None
+        if geo.hd != 64:
+            dqkv = K.attn_bwd_generic(qkv, o, do, lse, geo.key_mask, B, S, nh, geo.hd, geo.windows[i], scale)
+            K.rope_apply_generic_(dqkv, geo.rope[i][0], geo.rope[i][1], B, S, nh, geo.hd, geo.per_batch_pos, inverse=True)
+        elif geo.cu is not None:
+            dqkv = K.attn_bwd_varlen(qkv, o, do, lse, geo.cu, B, geo.max_s, nh, geo.windows[i], scale, geo.rope[i], prescaled=True)
+        else:
+            dqkv = K.attn_bwd(qkv, o, do, lse, geo.key_mask, B, S, nh, geo.windows[i], scale, geo.rope[i], geo.per_batch_pos, prescaled=True)
+        del do, o, qkv
+        dWqkv = K.linear_wgrad(dqkv, xn) if n_qkv else None
+        dw_an = None
+        if i == 0:
+            if need[2]:  # layer 0 has no attn_norm: bf16(g + dxn) of two bf16 operands, one rounding
+                _, g = K.add_f32(g, K.linear_dgrad(dqkv, Wqkv_b, Wqkv_t))
+            _hand_upstream(geo, g, g)
+        elif need[2] or n_an:
+            dxn = K.linear_dgrad(dqkv, Wqkv_b, Wqkv_t)
+            _, g, dw_an = K.layernorm_bwd(dxn, x, w_an, mean_a, rstd_a, g, False, bf16_only=True)
+            _hand_upstream(geo, g, g)
+        # (else: everything below this layer is frozen: the chain ends here)
+        grads = [dWqkv, dWo, dw_mn, dWi, dWo2] if i == 0 else [dw_an, dWqkv, dWo, dw_mn, dWi, dWo2]
+        out = [(gw if gw.dtype == dt else gw.to(dt)) if (nd and gw is not None) else None for gw, dt, nd in zip(grads, ctx.wdtypes, need[3:])]
+        return (None, None, g if need[2] else None, *out)
+
+    @staticmethod
     def backward(ctx, dy: Tensor):
+        if ctx.geo.bf16:
+            return _EncoderLayerFn._backward_bf16(ctx, dy)
         geo, i = ctx.geo, ctx.i
         B, S, nh = geo.B, geo.S, geo.nh
         scale = geo.hd ** -0.5
@@ -330,7 +415,10 @@ class _FinalNormFn(torch.autograd.Function):
     def forward(ctx, geo: _Geometry, x: Tensor, norm_w: Tensor):
         w = _f32(norm_w.detach())
         if geo.bf16:
-            return K.layernorm_fwd(x, w, geo.eps, False, True, False)[1]
+            _, y, mean, rstd = K.layernorm_fwd(x, w, geo.eps, False, True, geo.save)
+            if geo.save:  # (a training step on the bf16 stream, train_residual_dtype)
+                ctx.geo, ctx.pack, ctx.wdtype = geo, (x, w, mean, rstd), norm_w.dtype
+            return y
         y, _, mean, rstd = K.layernorm_fwd(x, w, geo.eps, True, False, geo.save)
         if geo.save:
             ctx.geo, ctx.pack, ctx.wdtype = geo, (x, w, mean, rstd), norm_w.dtype
@@ -339,6 +427,11 @@ class _FinalNormFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy: Tensor):
         x, w, mean, rstd = ctx.pack
+        if ctx.geo.bf16:  # the chain's single bf16 gradient starts here: bf16(LN'(dy)), one rounding
+            _, g, dw = K.layernorm_bwd(dy.to(torch.bfloat16).contiguous(), x, w, mean, rstd, None, False, inplace=False, bf16_only=True)
+            ctx.pack = None
+            _hand_upstream(ctx.geo, g, g)
+            return None, g if ctx.needs_input_grad[1] else None, dw.to(ctx.wdtype) if ctx.needs_input_grad[2] else None
         gx32, gx16, dw = K.layernorm_bwd(dy.contiguous(), x, w, mean, rstd, None, True, inplace=False)
         ctx.pack = None
         _hand_upstream(ctx.geo, gx32, gx16)
@@ -348,7 +441,7 @@ class _FinalNormFn(torch.autograd.Function):
 class _EmbedLNFn(torch.autograd.Function):
     """LayerNorm(tok_embeddings[ids]) with optional audio rows scattered over the placeholder tokens
     (TF:...modeling_modernbert.py:64-71, ref:cm3p/modeling_cm3p.py:592,603-605).  bf16: the bf16 output alone (the bf16 residual
-    stream of a forward-only call; no fp32 rows are written)."""
+    stream; no fp32 rows are written).  The backward takes the stream's gradient in its dtype (fp32 or bf16); its results are fp32."""
 
     @staticmethod
     def forward(ctx, ids: Tensor, table: Tensor, norm_w: Tensor, eps: float, padding_idx: int, slot: Optional[Tensor],
@@ -356,9 +449,10 @@ class _EmbedLNFn(torch.autograd.Function):
         w = _f32(norm_w.detach())
         tab = table.detach()
         ar = audio_rows.detach().contiguous() if audio_rows is not None else None
-        if bf16:
-            return K.embed_ln_fwd(ids, tab, w, eps, slot, ar, want_bf16=True, want_f32=False)[1]
-        y, _, mean, rstd = K.embed_ln_fwd(ids, tab, w, eps, slot, ar)
+        if bf16:  # (the statistics are written either way; a training step on the bf16 stream keeps them for the backward)
+            _, y, mean, rstd = K.embed_ln_fwd(ids, tab, w, eps, slot, ar, want_bf16=True, want_f32=False)
+        else:
+            y, _, mean, rstd = K.embed_ln_fwd(ids, tab, w, eps, slot, ar)
         ctx.pack = (ids, tab, w, mean, rstd, slot, ar, padding_idx)
         ctx.dtypes = (table.dtype, norm_w.dtype, audio_rows.dtype if audio_rows is not None else None)
         return y
@@ -426,8 +520,10 @@ class _LayerNormFn(torch.autograd.Function):
         w = _f32(norm_w.detach())
         xd = x.detach().contiguous()
         if bf16:
-            return K.layernorm_fwd(xd, w, eps, False, True, False)[1]
-        y, _, mean, rstd = K.layernorm_fwd(xd, w, eps, True, False)
+            want = any(ctx.needs_input_grad[:2])  # (a training step on the bf16 stream: the statistics its backward reads)
+            _, y, mean, rstd = K.layernorm_fwd(xd, w, eps, False, True, want)
+        else:
+            y, _, mean, rstd = K.layernorm_fwd(xd, w, eps, True, False)
         ctx.pack = (xd, w, mean, rstd)
         ctx.dtypes = (x.dtype, norm_w.dtype)
         return y
@@ -452,6 +548,7 @@ class CM3PEncoder(nn.Module):
         self.final_norm = nn.LayerNorm(config.hidden_size, eps=config.norm_eps, bias=False)
         self.gradient_checkpointing = False  # set by PreTrainedModel.gradient_checkpointing_enable()
         self.residual_dtype = None  # None / torch.float32: fp32 residual stream; torch.bfloat16: bf16 on forward-only calls
+        self.train_residual_dtype = None  # the same choice for calls that record a backward (training steps)
         self._inv_freq_cache = {}
         # init roles (TF:...modeling_modernbert.py:372-386): 'in'/'embedding' std = initializer_range,
         # 'out' std = initializer_range / sqrt(2 L); consumed by CM3PPreTrainedModel._init_weights
@@ -470,8 +567,9 @@ class CM3PEncoder(nn.Module):
         """dtype of the residual stream on forward-only calls: None or torch.float32 (the default) keep it fp32; torch.bfloat16 runs
         it in bf16 as a bf16 model of the reference does under no_grad (every LayerNorm reads and writes bf16, the residual adds are
         bf16 adds of the bf16-rounded projections, last_hidden_state and hidden_states are bf16).  Applies only to calls that record
-        nothing for a backward and have no dropout plan; training steps, calls with grad enabled on trainable parameters or inputs,
-        and train-mode calls with dropout p > 0 run the fp32 stream bit for bit as with None.  Not part of the state dict or config."""
+        nothing for a backward and have no dropout plan; training steps and calls with grad enabled on trainable parameters or inputs
+        (those follow `train_residual_dtype`) and train-mode calls with dropout p > 0 run the fp32 stream bit for bit as with None.
+        Not part of the state dict or config."""
         return self._residual_dtype
 
     @residual_dtype.setter
@@ -480,14 +578,30 @@ class CM3PEncoder(nn.Module):
             raise ValueError(f"residual_dtype must be None, torch.float32 or torch.bfloat16, got {dtype!r}")
         self._residual_dtype = dtype
 
+    @property
+    def train_residual_dtype(self) -> Optional[torch.dtype]:
+        """dtype of the residual stream on calls that record a backward (training steps, fine-tuning with part of the tower frozen):
+        None or torch.float32 (the default) keep it fp32; torch.bfloat16 runs the forward of `residual_dtype` and a backward whose
+        residual-stream gradient is one bf16 tensor (see the module docstring).  Master weights keep their dtype (fp32 masters with a
+        bf16 stream is the expected use); weight gradients have the parameter's dtype.  Limitation: a call with a dropout plan (train
+        mode, any dropout p > 0) runs the fp32 stream bit for bit as with None - the dropout sites have no bf16 form.  Calls that
+        record nothing follow `residual_dtype`, not this attribute.  Not part of the state dict or config."""
+        return self._train_residual_dtype
+
+    @train_residual_dtype.setter
+    def train_residual_dtype(self, dtype) -> None:
+        if dtype is not None and dtype not in (torch.float32, torch.bfloat16):
+            raise ValueError(f"train_residual_dtype must be None, torch.float32 or torch.bfloat16, got {dtype!r}")
+        self._train_residual_dtype = dtype
+
     def _bf16_stream(self, plan: Optional[_DropPlan], *inputs: Optional[Tensor]) -> bool:
-        """Whether this call runs the bf16 residual stream: the switch is set, there is no dropout plan and nothing will be recorded
-        for a backward (the rule _run_stack applies to geo.save, decided before the embedding runs)."""
-        if self._residual_dtype is not torch.bfloat16 or plan is not None:
+        """Whether this call runs the bf16 residual stream: there is no dropout plan, and the switch of the call's kind is set -
+        `residual_dtype` when nothing will be recorded for a backward (the rule _run_stack applies to geo.save, decided before the
+        embedding runs), `train_residual_dtype` when something will."""
+        if plan is not None:
             return False
-        if not torch.is_grad_enabled():
-            return True
-        return not any(t is not None and t.requires_grad for t in inputs) and not any(p.requires_grad for p in self.parameters())
+        records = torch.is_grad_enabled() and (any(t is not None and t.requires_grad for t in inputs) or any(p.requires_grad for p in self.parameters()))
+        return (self._train_residual_dtype if records else self._residual_dtype) is torch.bfloat16
 
     def train(self, mode: bool = True):
         if mode != self.training:
@@ -620,7 +734,7 @@ class CM3PEncoder(nn.Module):
     def _run_stack(self, x0: Tensor, B: int, S: int, attention_mask, position_ids, packed, output_hidden_states: bool, dev,
                    output_attentions: bool = False, plan: Optional[_DropPlan] = None, bf16: bool = False):
         """The L encoder layers + final norm on [rows, H]; `packed` = (idx, cu, max_s, n_valid, n_rows, pos) for unpadded execution;
-        `plan`: the call's dropout (None: none); `bf16`: x0 is bf16 and the stream stays bf16 (forward-only calls, _bf16_stream)."""
+        `plan`: the call's dropout (None: none); `bf16`: x0 is bf16 and the stream stays bf16 (_bf16_stream)."""
         cfg = self.config
         H = cfg.hidden_size
         geo = _Geometry()
@@ -658,8 +772,9 @@ class CM3PEncoder(nn.Module):
         weights = self._stack_weights()
         geo.save = torch.is_grad_enabled() and (x0.requires_grad or self.final_norm.weight.requires_grad
                                                 or any(w.requires_grad for ws in weights for w in ws))
-        if bf16 and geo.save:  # (_bf16_stream applies the same rule before the embedding ran)
-            raise RuntimeError("cm3p_amd: bf16 residual stream on a call that records a backward")
+        if bf16 and geo.save and (self._train_residual_dtype is not torch.bfloat16 or plan is not None):
+            # (_bf16_stream applies the same rules before the embedding ran)
+            raise RuntimeError("cm3p_amd: bf16 residual stream on a call that records a backward without train_residual_dtype, or with dropout")
         geo.bf16 = bf16
         if geo.save and _eval_weights:
             invalidate_weight_cache()  # a backward will follow, so an optimizer will: no copy made before this step may outlive it

@@ -11,7 +11,7 @@ from typing import Optional
 import torch
 
 from . import _lib
-from ._lib import BF16, EPI_BF16, EPI_BF16_RESID, EPI_F32, EPI_F32_RESID, F32, call, dt, ptr, query, stream
+from ._lib import ADD_A_BF16, BF16, EPI_BF16, EPI_BF16_RESID, EPI_F32, EPI_F32_RESID, F32, call, dt, ptr, query, stream
 
 Tensor = torch.Tensor
 
@@ -38,17 +38,24 @@ def layernorm_fwd(x: Tensor, weight: Tensor, eps: float, want_f32: bool, want_bf
 
 
 def layernorm_bwd(dy: Tensor, x: Tensor, weight: Tensor, mean: Tensor, rstd: Tensor, dres: Optional[Tensor],
-                  want_bf16: bool, inplace: bool = True):
-    """-> (dx_f32 = dres + LN'(dy), dx_bf16|None, dw[H]).  With `inplace` dx_f32 overwrites dres."""
+                  want_bf16: bool, inplace: bool = True, bf16_only: bool = False):
+    """-> (dx_f32 = dres + LN'(dy), dx_bf16|None, dw[H]).  With `inplace` dx_f32 overwrites dres.  x and dres: fp32 or bf16 rows.
+    bf16_only (the bf16 residual stream of a training step): -> (None, bf16(dres + LN'(dy)), dw) - the sum is formed in fp32 and
+    rounded once, where a bf16 torch model rounds LN'(dy) and the sum separately; with `inplace` it overwrites a bf16 dres."""
     rows, H = x.shape
-    dx32 = dres if (inplace and dres is not None) else _empty((rows, H), torch.float32, x)
-    dx16 = _empty((rows, H), torch.bfloat16, x) if want_bf16 else None
+    if bf16_only:
+        dx32 = None
+        dx16 = dres if (inplace and dres is not None and dres.dtype == torch.bfloat16) else _empty((rows, H), torch.bfloat16, x)
+    else:
+        dx32 = dres if (inplace and dres is not None and dres.dtype == torch.float32) else _empty((rows, H), torch.float32, x)
+        dx16 = _empty((rows, H), torch.bfloat16, x) if want_bf16 else None
     nblk = query("cm3p_layernorm_bwd_blocks", rows)
     part = _empty((nblk, H), torch.float32, x)
     dw = _empty((H,), torch.float32, x)
-    call("cm3p_layernorm_bwd", ptr(dy), dt(dy), ptr(x), ptr(weight, torch.float32), ptr(mean, torch.float32), ptr(rstd, torch.float32), ptr(dres), ptr(dx32), ptr(dx16),
-         ptr(part), ptr(dw), rows, H, stream(),
-         work=float(rows) * H * (dy.element_size() + 4 + (4 if dres is not None else 0) + 4 + (2 if want_bf16 else 0)))
+    call("cm3p_layernorm_bwd", ptr(dy), dt(dy), ptr(x), dt(x), ptr(weight, torch.float32), ptr(mean, torch.float32), ptr(rstd, torch.float32), ptr(dres),
+         dt(dres) if dres is not None else F32, ptr(dx32), ptr(dx16), ptr(part), ptr(dw), rows, H, stream(),
+         work=float(rows) * H * (dy.element_size() + x.element_size() + (dres.element_size() if dres is not None else 0)
+                                 + (4 if dx32 is not None else 0) + (2 if dx16 is not None else 0)))
     return dx32, dx16, dw
 
 
@@ -70,6 +77,7 @@ def embed_ln_fwd(ids: Tensor, table: Tensor, weight: Tensor, eps: float, slot: O
 
 def embed_ln_bwd(dy: Tensor, ids: Tensor, table: Tensor, weight: Tensor, mean: Tensor, rstd: Tensor, padding_idx: int,
                  slot: Optional[Tensor] = None, override: Optional[Tensor] = None, want_table_grad: bool = True):
+    """dy [T, H] fp32 or bf16 (the gradient that leaves a bf16 residual stream) -> (d_table|None, d_override|None, dw), all fp32."""
     T = ids.numel()
     V, H = table.shape
     if want_table_grad and T > 0 and os.environ.get("CM3P_EMBED_BWD", "sorted") != "atomic":
@@ -81,7 +89,7 @@ def embed_ln_bwd(dy: Tensor, ids: Tensor, table: Tensor, weight: Tensor, mean: T
     nblk = query("cm3p_layernorm_bwd_blocks", T)
     part = _empty((nblk, H), torch.float32, table)
     dw = _empty((H,), torch.float32, table)
-    call("cm3p_embed_ln_bwd", ptr(dy), ptr(ids, torch.int64), ptr(table), dt(table), ptr(slot, torch.int32), ptr(override),
+    call("cm3p_embed_ln_bwd", ptr(dy), dt(dy), ptr(ids, torch.int64), ptr(table), dt(table), ptr(slot, torch.int32), ptr(override),
          dt(override) if override is not None else F32, ptr(weight, torch.float32), ptr(mean, torch.float32), ptr(rstd, torch.float32), ptr(d_table), ptr(d_ovr), ptr(part), ptr(dw),
          T, H, padding_idx, V, stream())
     return d_table, d_ovr, dw
@@ -105,7 +113,7 @@ def _embed_ln_bwd_sorted(dy, ids, table, weight, mean, rstd, padding_idx, slot, 
     nblk = (-(-T // chunk) + 3) // 4
     part = _empty((nblk, H), torch.float32, table)
     dw = _empty((H,), torch.float32, table)
-    call("cm3p_embed_ln_bwd_sorted", ptr(dy), ptr(flat, torch.int64), ptr(order, torch.int64), ptr(run_of, torch.int32), ptr(table), dt(table),
+    call("cm3p_embed_ln_bwd_sorted", ptr(dy), dt(dy), ptr(flat, torch.int64), ptr(order, torch.int64), ptr(run_of, torch.int32), ptr(table), dt(table),
          ptr(slot, torch.int32), ptr(override), dt(override) if override is not None else F32, ptr(weight, torch.float32),
          ptr(mean, torch.float32), ptr(rstd, torch.float32), ptr(d_table), ptr(d_ovr), ptr(run_rows), ptr(run_ids, torch.int64),
          ptr(part), ptr(dw), T, H, padding_idx, V, stream())
@@ -278,6 +286,12 @@ def cast_bf16_with_transpose_many(ws: list) -> list:
 
 
 def add_f32(a: Tensor, b: Tensor, want_bf16: bool = False, inplace: bool = True):
+    """fp32 a: -> (a + b as fp32, its bf16 rounding | None).  bf16 a (the bf16 residual stream of a training step): -> (None,
+    bf16(a + b)), the sum formed in fp32 and rounded once; b fp32 or bf16 either way."""
+    if a.dtype == torch.bfloat16:
+        y16 = a if inplace else torch.empty_like(a)
+        call("cm3p_add_f32", ptr(a), ptr(b), dt(b) | ADD_A_BF16, None, ptr(y16), a.numel(), stream())
+        return None, y16
     y32 = a if inplace else torch.empty_like(a)
     y16 = torch.empty(a.shape, dtype=torch.bfloat16, device=a.device) if want_bf16 else None
     call("cm3p_add_f32", ptr(a), ptr(b), dt(b), ptr(y32), ptr(y16), a.numel(), stream())
@@ -695,10 +709,11 @@ def pool_fwd(h: Tensor, mask: Optional[Tensor], Bn: int, S: int, cls: bool):
     return pooled, count
 
 
-def pool_bwd(dpooled: Tensor, mask: Optional[Tensor], count: Tensor, Bn: int, S: int, cls: bool) -> Tensor:
+def pool_bwd(dpooled: Tensor, mask: Optional[Tensor], count: Tensor, Bn: int, S: int, cls: bool, dtype: torch.dtype = torch.float32) -> Tensor:
+    """-> dh [Bn * S, H] of `dtype` (fp32, or bf16 when the pooled rows were a bf16 residual stream's: one rounding of the fp32 value)."""
     H = dpooled.shape[-1]
-    dh = torch.empty((Bn * S, H), dtype=torch.float32, device=dpooled.device)
-    call("cm3p_pool_bwd", ptr(dpooled), ptr(mask, torch.int64), ptr(count), ptr(dh), Bn, S, H, int(cls), stream())
+    dh = torch.empty((Bn * S, H), dtype=dtype, device=dpooled.device)
+    call("cm3p_pool_bwd", ptr(dpooled, torch.float32), ptr(mask, torch.int64), ptr(count), ptr(dh), dt(dh), Bn, S, H, int(cls), stream())
     return dh
 
 

@@ -70,7 +70,8 @@ class CM3POutput(ModelOutput):
 
 # ----------------------------------------------------------------------------------------------- autograd nodes
 class _PoolFn(torch.autograd.Function):
-    """cls: h[:, 0]; else masked mean in fp32 (ref:cm3p/modeling_cm3p.py:385-396,631-642)."""
+    """cls: h[:, 0]; else masked mean in fp32 (ref:cm3p/modeling_cm3p.py:385-396,631-642).  The gradient is written in h's dtype
+    (bf16 rows of a bf16 residual stream get a bf16 gradient, one rounding of the fp32 value)."""
 
     @staticmethod
     def forward(ctx, h: Tensor, mask: Optional[Tensor], cls: bool):
@@ -78,12 +79,13 @@ class _PoolFn(torch.autograd.Function):
         m = mask.contiguous().to(torch.int64) if mask is not None else None
         pooled, count = K.pool_fwd(h.detach().contiguous(), m, Bn, S, cls)
         ctx.pack = (m, count, Bn, S, cls)
+        ctx.hdtype = h.dtype
         return pooled
 
     @staticmethod
     def backward(ctx, dp: Tensor):
         m, count, Bn, S, cls = ctx.pack
-        dh = K.pool_bwd(dp.contiguous(), m, count, Bn, S, cls)
+        dh = K.pool_bwd(dp.contiguous(), m, count, Bn, S, cls, dtype=torch.bfloat16 if ctx.hdtype == torch.bfloat16 else torch.float32)
         return dh.view(Bn, S, -1), None, None
 
 
@@ -232,24 +234,24 @@ def _mlm_head_forward(h: Tensor, Wd: Tensor, bd: Optional[Tensor], norm_w: Tenso
     else:
         logits = K.gemm(y, Wdec_b, T, Vp, H, True, True, EPI_F32)
     pack = (hb, Wd_b, Wdec_b, bd32, w32, z, a32, y, mean, rstd, V)
-    meta = (Wd.dtype, bd.dtype if bd is not None else None, norm_w.dtype, Wdec.dtype, bdec.dtype if bdec is not None else None)
+    meta = (Wd.dtype, bd.dtype if bd is not None else None, norm_w.dtype, Wdec.dtype, bdec.dtype if bdec is not None else None, h.dtype)
     return logits, pack, meta
 
 
 def _mlm_head_backward(pack, meta, need_dh: bool, dlb: Tensor, dbdec_full: Optional[Tensor]):
     """dlb: bf16 [T, Vp] gradient of the padded logits; dbdec_full: its fp32 column sums.  -> gradients of
-    (h, Wd, bd, norm_w, Wdec, bdec)."""
-    from ._lib import EPI_F32
+    (h, Wd, bd, norm_w, Wdec, bdec); dh has the dtype of h (bf16 rows of a bf16 residual stream: the dgrad GEMM stores bf16)."""
+    from ._lib import EPI_BF16, EPI_F32
 
     hb, Wd_b, Wdec_b, bd32, w32, z, a32, y, mean, rstd, V = pack
-    dWd_t, dbd_t, dnw_t, dWdec_t, dbdec_t = meta
+    dWd_t, dbd_t, dnw_t, dWdec_t, dbdec_t, h_t = meta
     T, H = hb.shape
     dy = K.linear_dgrad(dlb, Wdec_b)
     dWdec = K.linear_wgrad(dlb, y)[:V]
     dbdec = dbdec_full[:V] if dbdec_t is not None else None
     da, _, dnw = K.layernorm_bwd(dy, a32, w32, mean, rstd, None, False, inplace=False)
     dz, dbd = K.bias_gelu_bwd(da, z, bd32)
-    dh = K.gemm(dz, Wd_b, T, H, H, True, False, EPI_F32) if need_dh else None
+    dh = K.gemm(dz, Wd_b, T, H, H, True, False, EPI_BF16 if h_t == torch.bfloat16 else EPI_F32) if need_dh else None
     dWd = K.linear_wgrad(dz, hb)
     return (dh, dWd.to(dWd_t), dbd.to(dbd_t) if dbd_t is not None else None, dnw.to(dnw_t), dWdec.to(dWdec_t),
             dbdec.to(dbdec_t) if dbdec is not None else None)
@@ -342,16 +344,23 @@ class CM3PPreTrainedModel(PreTrainedModel):
     _supports_sdpa = True
     _supports_flex_attn = False
 
-    def set_residual_dtype(self, dtype: Optional[torch.dtype]):
+    def set_residual_dtype(self, dtype: Optional[torch.dtype], training: bool = False):
         """Set `residual_dtype` on every encoder this model owns (beatmap, metadata and audio towers): torch.bfloat16 runs the
         residual stream of forward-only calls in bf16, the reference's inference recipe (a bf16 model called under no_grad);
-        None / torch.float32 keep the fp32 stream.  Training steps and dropout calls always run fp32 (CM3PEncoder.residual_dtype).
+        None / torch.float32 keep the fp32 stream.  With the default training=False, training steps always run fp32
+        (CM3PEncoder.residual_dtype).  training=True sets `train_residual_dtype` as well: calls that record a backward then run the
+        bf16 stream too, with a bf16 residual-stream gradient (CM3PEncoder.train_residual_dtype; master weights and weight
+        gradients keep their dtype).  Calls with dropout (train mode, any p > 0) run fp32 either way.
         Returns the model; the state dict and the config are unchanged."""
         from .encoder import CM3PEncoder
 
+        if dtype is not None and dtype not in (torch.float32, torch.bfloat16):  # (before anything is changed; the setters' rule)
+            raise ValueError(f"residual_dtype must be None, torch.float32 or torch.bfloat16, got {dtype!r}")
         encoders = [m for m in self.modules() if isinstance(m, CM3PEncoder)]
         for enc in encoders:
-            enc.residual_dtype = dtype  # (the setter validates; a bad dtype raises before anything is changed: all share one rule)
+            enc.residual_dtype = dtype
+            if training:
+                enc.train_residual_dtype = dtype
         return self
 
     def _check_and_adjust_attn_implementation(self, attn_implementation, *args, **kwargs):
@@ -547,7 +556,7 @@ class CM3PBeatmapTransformer(nn.Module):
                 first = cu_seqlens[:-1].to(device=h.device, dtype=torch.int64).contiguous()
                 pooled = _TakeRowsFn.apply(h, first)
                 if pooled.dtype != torch.float32:  # bf16 residual stream: the pooled rows widened exactly, as _PoolFn returns them
-                    pooled = pooled.float()
+                    pooled = _WidenRowsFn.apply(pooled)
             return CM3PBeatmapModelOutput(last_hidden_state=h, pooler_output=pooled, hidden_states=hiddens, attentions=None,
                                           audio_model_output=audio_out)
         if inputs_embeds is not None:
@@ -926,7 +935,8 @@ class CM3PBeatmapModelWithProjection(CM3PPreTrainedModel):
 
 
 class _TakeRowsFn(torch.autograd.Function):
-    """x [R, H] fp32 -> x[idx] (boolean-mask row selection of the sparse MLM head); backward scatters into zeros."""
+    """x [R, H] fp32 or bf16 -> x[idx] (boolean-mask row selection of the sparse MLM head); backward scatters into zeros (rows of
+    x's dtype both ways: bf16 rows move through the half-width copies)."""
 
     @staticmethod
     def forward(ctx, x: Tensor, idx: Tensor):
@@ -936,6 +946,19 @@ class _TakeRowsFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy: Tensor):
         return K.scatter_rows(dy.contiguous(), ctx.idx, ctx.rows), None
+
+
+class _WidenRowsFn(torch.autograd.Function):
+    """bf16 rows -> the same values as fp32 (exact; dtype plumbing of the pooled CLS rows of caller-packed inputs); backward: the
+    fp32 gradient rounded once to bf16 by cm3p_cast_f32_bf16, the dtype the bf16 residual stream takes its gradient in."""
+
+    @staticmethod
+    def forward(ctx, x: Tensor):
+        return x.float()
+
+    @staticmethod
+    def backward(ctx, dy: Tensor):
+        return K.cast_bf16(dy.float().contiguous())
 
 
 class CM3PForMaskedLM(CM3PPreTrainedModel):

@@ -31,7 +31,7 @@ extern "C" {
 #define CM3P_BF16 1
 
 /* ABI version of this header; cm3p_abi_version() must return it. */
-#define CM3P_ABI_VERSION 18
+#define CM3P_ABI_VERSION 19
 int cm3p_abi_version(void);
 
 /* ---------------------------------------------------------------------------------------------------------------
@@ -48,10 +48,14 @@ int cm3p_layernorm_bwd_blocks(int64_t rows);
 
 /* Backward of the above (autograd of the same nn.LayerNorm).  dx = dres + LN'(dy) where `dres` (may be NULL) is the
  * gradient already flowing on the residual stream: the pre-norm residual x + f(LN(x)) of
- * TF:...modeling_modernbert.py:331-332.  dx_f32 may alias dres.  dw[H] is fully overwritten. */
-int cm3p_layernorm_bwd(const void* dy, int dy_dtype, const float* x, const float* weight, const float* mean,
-                       const float* rstd, const float* dres, float* dx_f32, void* dx_bf16, float* dw_partial, float* dw,
-                       int64_t rows, int H, void* stream);
+ * TF:...modeling_modernbert.py:331-332.  dx_f32 may alias dres.  dw[H] is fully overwritten.
+ * x and dres are rows of x_dtype / dres_dtype (CM3P_F32 or CM3P_BF16; dres_dtype is ignored for a NULL dres).  With fp32 x and
+ * fp32 (or no) dres the fp32 residual stream's kernels run, as before ABI 19.  bf16 x and / or bf16 dres: the bf16 residual
+ * stream of a training step; with dx_f32 == NULL the only result is dx_bf16 = bf16(dres + LN'(dy)), the sum formed in fp32 and
+ * rounded once (dx_bf16 may alias a bf16 dres).  Statistics, row reductions and dw are fp32 in every form. */
+int cm3p_layernorm_bwd(const void* dy, int dy_dtype, const void* x, int x_dtype, const float* weight, const float* mean,
+                       const float* rstd, const void* dres, int dres_dtype, float* dx_f32, void* dx_bf16, float* dw_partial,
+                       float* dw, int64_t rows, int H, void* stream);
 
 /* Token embedding lookup + optional audio-embedding scatter + LayerNorm.
  * Replaces ModernBertEmbeddings.forward (TF:...modeling_modernbert.py:64-71) fed by
@@ -64,8 +68,9 @@ int cm3p_embed_ln_fwd(const int64_t* ids, const void* table, int table_dtype, co
                       float* mean, float* rstd, int64_t T, int H, float eps, int64_t vocab, void* stream);
 
 /* Backward: d_table[ids[t]] += row gradient (fp32 atomics; the caller zeroes d_table; row `padding_idx` gets none,
- * as nn.Embedding(padding_idx=...) does), d_override[slot[t]] = row gradient.  Either may be NULL. */
-int cm3p_embed_ln_bwd(const float* dy, const int64_t* ids, const void* table, int table_dtype, const int32_t* slot,
+ * as nn.Embedding(padding_idx=...) does), d_override[slot[t]] = row gradient.  Either may be NULL.
+ * dy: [T, H] of dy_dtype (CM3P_F32, or CM3P_BF16: the gradient that leaves a bf16 residual stream); every result is fp32. */
+int cm3p_embed_ln_bwd(const void* dy, int dy_dtype, const int64_t* ids, const void* table, int table_dtype, const int32_t* slot,
                       const void* override_rows, int override_dtype, const float* weight, const float* mean,
                       const float* rstd, float* d_table, float* d_override, float* dw_partial, float* dw, int64_t T, int H,
                       int64_t padding_idx, int64_t vocab, void* stream);
@@ -77,9 +82,10 @@ int cm3p_embed_ln_bwd(const float* dy, const int64_t* ids, const void* table, in
  *   run_of [T] int32: run number of sorted position p; a new run starts at p = 0, wherever ids[order[p]] != ids[order[p - 1]] and
  *                     at every multiple of cm3p_embed_ln_bwd_sorted_chunk() (64), i.e. run_of = cumsum(start flags) - 1;
  *   run_rows [R, H] fp32 and run_ids [R] int64: workspaces with R >= run_of[T - 1] + 1 (never more than min(T, vocab + T / 64 + 1));
- *   dw_partial: [ceil(ceil(T / 64) / 4), H] fp32.  d_table [vocab, H] is fully written (no zeroing by the caller). */
+ *   dw_partial: [ceil(ceil(T / 64) / 4), H] fp32.  d_table [vocab, H] is fully written (no zeroing by the caller).
+ *   dy: [T, H] of dy_dtype (CM3P_F32 or CM3P_BF16), as in cm3p_embed_ln_bwd. */
 int cm3p_embed_ln_bwd_sorted_chunk(void);
-int cm3p_embed_ln_bwd_sorted(const float* dy, const int64_t* ids, const int64_t* order, const int32_t* run_of, const void* table,
+int cm3p_embed_ln_bwd_sorted(const void* dy, int dy_dtype, const int64_t* ids, const int64_t* order, const int32_t* run_of, const void* table,
                              int table_dtype, const int32_t* slot, const void* override_rows, int override_dtype, const float* weight,
                              const float* mean, const float* rstd, float* d_table, float* d_override, float* run_rows, int64_t* run_ids,
                              float* dw_partial, float* dw, int64_t T, int H, int64_t padding_idx, int64_t vocab, void* stream);
@@ -175,8 +181,13 @@ int cm3p_cast_f32_bf16_t(const float* x, void* y, void* y_t, int64_t rows, int64
  * total_blocks = the sum of ceil(rows / 64) * ceil(cols / 64).  The table is the caller's (it must outlive the launch). */
 int cm3p_cast_f32_bf16_t_multi(const int64_t* table, int n, int64_t total_blocks, void* stream);
 /* y_f32 (and y_bf16 if not NULL) = a_f32 + b (b fp32 or bf16); n % 4 == 0.  Residual-gradient join for layer 0,
- * whose attn_norm is nn.Identity (TF:...modeling_modernbert.py:309-310). */
-int cm3p_add_f32(const float* a, const void* b, int b_dtype, float* y_f32, void* y_bf16, int64_t n, void* stream);
+ * whose attn_norm is nn.Identity (TF:...modeling_modernbert.py:309-310).
+ * b_dtype | CM3P_ADD_A_BF16: `a` is bf16 (the bf16 residual stream of a training step); then y_f32 must be NULL and
+ * y_bf16 = bf16(a + b), the sum formed in fp32 and rounded once (y_bf16 may alias a).  The flag rides in b_dtype, where the
+ * other entry points of ABI 19 got a dtype argument of their own, so that callers of the seven-argument form keep working
+ * unchanged.  Since ABI 19 a b_dtype with bits other than CM3P_BF16 and this flag is CM3P_ERR_INVALID (it used to read as fp32). */
+#define CM3P_ADD_A_BF16 16
+int cm3p_add_f32(const void* a, const void* b, int b_dtype, float* y_f32, void* y_bf16, int64_t n, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------------
  * Rotary position embedding.
@@ -380,8 +391,9 @@ int cm3p_bias_gelu_bwd(const void* da, int da_dtype, const float* z, const float
 int cm3p_pool_chunks(int S);
 int cm3p_pool_fwd(const void* h, int h_dtype, const int64_t* mask, float* pooled, float* partial, float* count, int Bn, int S, int H,
                   int cls, void* stream);
-int cm3p_pool_bwd(const float* dpooled, const int64_t* mask, const float* count, float* dh, int Bn, int S, int H, int cls,
-                  void* stream);
+/* dh: [Bn * S, H] of dh_dtype (CM3P_F32, or CM3P_BF16: written directly in the dtype of a bf16 residual stream, one rounding). */
+int cm3p_pool_bwd(const float* dpooled, const int64_t* mask, const float* count, void* dh, int dh_dtype, int Bn, int S, int H,
+                  int cls, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------------
  * Contrastive head, fp32 throughout (ref:cm3p/modeling_cm3p.py:27-62, 958-985).
