@@ -16,6 +16,18 @@ is the only exposed one (64 KiB per rank at b = 32).
 The autograd node is torch.distributed plumbing and device agnostic; the arithmetic around it (logits, loss) is the HIP
 head of modeling_cm3p.py.  Its backward is the transpose collective: a sum reduce-scatter of the gradient w.r.t. the
 gathered buffer, so gradients that other ranks hold for this rank's embeddings come home.
+
+Metadata variations, (b, V, L) metadata with `metadata_variation_classes` (b, V), are gathered too, in TRAINING mode
+(`gathered_contrastive_variations`).  Parity definition as above, against the reference's 3-D loss on the concatenated
+(N*b, V, N*b) batch.  Rank r gathers the whole (b, V, P) metadata embeddings (N*b*V*P fp32: 134 MB at N = 8, b = 32, V = 256,
+P = 512) and the (b, P) beatmap embeddings.  With idx[i] the first class-0 slot of row i:
+  metadata direction: rows i*V + idx[i] of me (b*V, P) x b_all^T (N*b columns), target r*b + i;
+  beatmap direction:  be (b, P) x m_all^T (N*b*V columns), target (r*b + i)*V + idx[i].
+Order: the beatmap gather starts after the beatmap projection, the metadata gather as soon as the metadata embeddings exist;
+the metadata-direction logits need no other rank's metadata and are computed while that gather travels; it is joined before
+the beatmap-direction logits.  In EVAL mode a 3-D batch stays rank-local: the reference's evaluation indexes
+logits_per_beatmap[i, i] of a (B, B, V) tensor (ref:train.py:101-131), which a gathered (b, N*b, V) would mis-index on every
+rank but 0; `warn_variations_stay_local` says so once.
 """
 from __future__ import annotations
 
@@ -107,17 +119,79 @@ def gathered_contrastive(metadata_embeds: Tensor, beatmap_embeds: Tensor, logit_
     return lpm, lpb, loss
 
 
+def variation_targets(rank: int, b: int, V: int, n_cols: int, idx: Tensor):
+    """The integer bookkeeping of the gathered 3-D loss on rank `rank`: idx (b,) = first class-0 slot of each local row,
+    n_cols = N*b.  -> (row_offset, target_metadata, target_beatmap), int64 on idx's device:
+    row_offset[i] = (i*V + idx[i]) * n_cols, where row idx[i] of sample i starts in the flat (b, V, n_cols) metadata logits;
+    target_metadata[i] = rank*b + i, this sample's beatmap among the n_cols gathered ones;
+    target_beatmap[i] = (rank*b + i)*V + idx[i], this sample's true variation among the n_cols*V gathered metadata rows."""
+    rows = torch.arange(b, device=idx.device, dtype=torch.int64)
+    slot = rows * V + idx.to(torch.int64)
+    return slot * n_cols, rows + rank * b, slot + rank * b * V
+
+
+def variation_head(me: Tensor, be: Tensor, m_all, b_all, idx: Tensor | None, rank: int, logit_scale: Tensor):
+    """The gathered 3-D head of one rank (HIP, no collective in it: one process can drive it as any rank of any world size).
+    me (b, V, P), be (b, P): this rank's embeddings; m_all (N*b*V, P) or (N*b, V, P), b_all (N*b, P): the gathered ones, each a
+    tensor or a PendingGather, which is joined where its logits need it (the metadata-direction logits are launched before
+    m_all is joined).  -> (lpm (b, V, N*b), lpb (b, N*b*V), loss); loss is None without idx."""
+    from .modeling_cm3p import _CrossEntropySumFn, _LogitsFn
+
+    b, V, P = me.shape
+    if isinstance(b_all, PendingGather):
+        b_all = b_all.wait()
+    n = b_all.shape[0]
+    lpm = _LogitsFn.apply(me.reshape(b * V, P), b_all, logit_scale)  # this rank's b*V metadata rows vs every beatmap
+    if isinstance(m_all, PendingGather):
+        m_all = m_all.wait()
+    m_all = m_all.reshape(-1, P)
+    if m_all.shape[0] != n * V:
+        raise ValueError(f"gathered metadata has {m_all.shape[0]} rows, expected N*b*V = {n * V}")
+    lpb = _LogitsFn.apply(be, m_all, logit_scale)  # this rank's beatmap rows vs every metadata variation
+    loss = None
+    if idx is not None:
+        roff, tgt_m, tgt_b = variation_targets(rank, b, V, n, idx)
+        specs = [(0, b, n, 0, 1, roff, tgt_m, 0.5), (1, b, n * V, n * V, 1, None, tgt_b, 0.5)]
+        loss = _CrossEntropySumFn.apply(specs, lpm, lpb)
+    return lpm.view(b, V, n), lpb, loss
+
+
+def gathered_contrastive_variations(me: Tensor, be: Tensor, classes: Tensor | None, logit_scale: Tensor, group=None,
+                                    beatmap_pending: PendingGather | None = None):
+    """(b, V, L) metadata variations with cross-rank negatives.  me (b, V, P), be (b, P), classes (b, V) or None (no loss).
+    -> (logits_per_metadata (b, V, N*b), logits_per_beatmap (b, N*b, V), loss) on this rank.  `beatmap_pending`: the beatmap
+    gather the caller started earlier.  b, V and P must be the same on every rank (drop_last, and a processor that emits exactly
+    `metadata_variations` rows per sample); L may differ.  A mismatch is a caller error that the collective library reports."""
+    from . import kernels as K
+
+    b, V, _ = me.shape
+    pm = start_gather(me, group)  # the big one, as soon as its input exists
+    pb = beatmap_pending if beatmap_pending is not None else start_gather(be, group)
+    try:
+        idx = None if classes is None else K.first_zero_index(classes.contiguous().to(torch.int64))  # (classes == 0).argmax(1)
+        lpm, lpb, loss = variation_head(me, be, pm, pb, idx, dist.get_rank(group), logit_scale)
+    except BaseException:
+        try:  # never leave a collective un-joined behind an exception
+            pb.wait()
+        finally:
+            pm.wait()
+        raise
+    return lpm, lpb.view(b, -1, V), loss
+
+
 _warned_3d = False
 
 
 def warn_variations_stay_local():
-    """gather_negatives with (B, V, L) metadata variations: the variations are per-sample structured negatives and stay
-    rank-local (decided and documented in DESIGN.md §6); say so once instead of silently ignoring the flag."""
+    """gather_negatives with (B, V, L) metadata variations in EVAL mode: the batch is scored rank-locally, because the
+    reference's evaluation reads logits_per_beatmap[i, i] of a (B, B, V) tensor (ref:train.py:101-131) and a gathered
+    (b, N*b, V) would be mis-indexed on every rank but 0; say so once instead of silently ignoring the flag."""
     global _warned_3d
     if not _warned_3d:
         _warned_3d = True
-        warnings.warn("CM3PModel.gather_negatives is set but metadata_ids is (B, V, L): metadata variations are rank-local "
-                      "negatives; this batch is scored without cross-rank gathering.", RuntimeWarning, stacklevel=3)
+        warnings.warn("CM3PModel.gather_negatives is set but the model is in eval mode and metadata_ids is (B, V, L): metadata "
+                      "variations are gathered across ranks in training mode only; this batch is scored rank-locally, so that "
+                      "logits_per_beatmap keeps the (B, B, V) layout evaluation code indexes.", RuntimeWarning, stacklevel=3)
 
 
 # ---- what a multi-rank run says about itself (bench.py; device agnostic, so that world sizes one card cannot host are rehearsed over gloo

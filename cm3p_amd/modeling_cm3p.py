@@ -687,7 +687,8 @@ class CM3PModel(CM3PPreTrainedModel):
             bc = config.beatmap_config
             self.head = CM3PPredictionHead(bc)
             self.decoder = nn.Linear(bc.hidden_size, bc.vocab_size, bias=bc.decoder_bias)
-        # Opt-in: in-batch negatives across all ranks of the default process group (new behaviour).
+        # Opt-in: in-batch negatives across all ranks of the default process group (new behaviour): (B, L)
+        # metadata always, (B, V, L) metadata variations in training mode (eval scores them rank-locally; cm3p_amd/dist.py).
         self.gather_negatives = False
         self.unpad_inputs = None  # True / False overrides the reference's rule (unpad iff attn_implementation is flash_attention_2)
         self.post_init()
@@ -785,7 +786,7 @@ class CM3PModel(CM3PPreTrainedModel):
                     main.wait_stream(side)
                 raise
             if self.gather_negatives and metadata_ids is not None:
-                if metadata_ids.dim() == 2:
+                if metadata_ids.dim() == 2 or self.training:
                     # start the all-gather now: it runs on the process group's side stream under the whole metadata tower and is
                     # joined just before the logits (cm3p_amd/dist.py)
                     from .dist import start_gather
@@ -816,6 +817,16 @@ class CM3PModel(CM3PPreTrainedModel):
 
                 logits_per_metadata, logits_per_beatmap, gl = gathered_contrastive(me2, beatmap_embeds, self.logit_scale,
                                                                                    beatmap_pending=beatmap_pending)
+                if return_loss:
+                    loss = gl
+            elif self.gather_negatives and self.training:
+                # (B, V, L) variations, training: (b, V, N*b) / (b, N*b, V) logits against every rank's rows; both pending gathers
+                # are joined inside, also behind an exception
+                from .dist import gathered_contrastive_variations
+
+                logits_per_metadata, logits_per_beatmap, gl = gathered_contrastive_variations(
+                    metadata_embeds, beatmap_embeds, metadata_variation_classes if return_loss else None, self.logit_scale,
+                    beatmap_pending=beatmap_pending)
                 if return_loss:
                     loss = gl
             else:
