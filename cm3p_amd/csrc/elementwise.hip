@@ -548,6 +548,94 @@ __global__ __launch_bounds__(256) void pool_bwd_kernel(const float* __restrict__
     }
 }
 
+// ---- pooling of packed rows: h [total, H], sequence b owns rows cu[b] .. cu[b+1]-1 -----------------------------------------------
+// The same expressions in the same order as the padded kernels above over the valid rows only: a padded row adds h * 0.0f, which
+// leaves a finite sum as it is, so the results are the bits the padded kernels give on a right-padded batch of the same rows.
+
+// partial[b, c, :] = sum over positions c*128 .. min(len_b, c*128+128)-1 of sequence b, ascending; zeros for a chunk past len_b
+// (the final kernel reads every slot of the uninitialised workspace)
+template <typename T>
+__global__ __launch_bounds__(256) void pool_partial_packed_kernel(const T* __restrict__ h, const int* __restrict__ cu,
+                                                                  float* __restrict__ partial, int H, int nchunks) {
+    const int b = blockIdx.x / nchunks, c = blockIdx.x % nchunks;
+    const int64_t row0 = cu[b];
+    const int len = cu[b + 1] - cu[b];
+    const int s0 = c * kPoolChunk, s1 = min(len, s0 + kPoolChunk);
+    for (int col = threadIdx.x * 4; col < H; col += 1024) {
+        f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+        for (int s = s0; s < s1; ++s) acc += load4_f32(h + (row0 + s) * H + col);
+        *reinterpret_cast<f32x4*>(partial + ((int64_t)b * nchunks + c) * H + col) = acc;
+    }
+}
+
+__global__ __launch_bounds__(256) void pool_final_packed_kernel(const float* __restrict__ partial, const int* __restrict__ cu,
+                                                                float* __restrict__ pooled, float* __restrict__ count, int H,
+                                                                int nchunks) {
+    const int b = blockIdx.x;
+    const float cnt = (float)(cu[b + 1] - cu[b]);
+    const float inv = 1.0f / fmaxf(cnt, 1e-9f);
+    if (threadIdx.x == 0 && count) count[b] = cnt;
+    for (int col = threadIdx.x; col < H; col += 256) {
+        float s = 0.f;
+        for (int c = 0; c < nchunks; ++c) s += partial[((int64_t)b * nchunks + c) * H + col];
+        pooled[(int64_t)b * H + col] = s * inv;
+    }
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void pool_cls_packed_kernel(const T* __restrict__ h, const int* __restrict__ cu,
+                                                              float* __restrict__ pooled, int H) {
+    const int b = blockIdx.x;
+    const int64_t row = cu[b];
+    for (int col = threadIdx.x; col < H; col += 256) pooled[(int64_t)b * H + col] = to_f32(h[row * H + col]);
+}
+
+// Every row 0 .. total-1 of dh is written once.  A workgroup owns kPoolBwdRows consecutive rows: its first lanes find each row's
+// sequence (the last b with cu[b] <= row, by bisection, so an empty sequence is never chosen) and its factor, then all lanes store.
+// Rows at or past cu[Bn] (alignment rows behind the packed ones) get zeros.
+constexpr int kPoolBwdRows = 32;
+
+template <bool DH_BF16>
+__global__ __launch_bounds__(256) void pool_bwd_packed_kernel(const float* __restrict__ dpooled, const int* __restrict__ cu,
+                                                              void* __restrict__ dh, int Bn, int64_t total, int H, int cls) {
+    __shared__ int seq_of[kPoolBwdRows];
+    __shared__ float scale_of[kPoolBwdRows];
+    const int64_t r0 = (int64_t)blockIdx.x * kPoolBwdRows;
+    if (threadIdx.x < kPoolBwdRows) {
+        const int64_t row = r0 + threadIdx.x;
+        int b = -1;
+        float scale = 0.0f;
+        if (row < total && row < (int64_t)cu[Bn]) {
+            int lo = 0, hi = Bn - 1;
+            while (lo < hi) {
+                const int mid = (lo + hi + 1) >> 1;
+                if ((int64_t)cu[mid] <= row) lo = mid;
+                else hi = mid - 1;
+            }
+            b = lo;
+            if (cls) scale = (row == (int64_t)cu[b]) ? 1.0f : 0.0f;
+            else scale = 1.0f / fmaxf((float)(cu[b + 1] - cu[b]), 1e-9f);
+        }
+        seq_of[threadIdx.x] = b;
+        scale_of[threadIdx.x] = scale;
+    }
+    __syncthreads();
+    const int h4 = H / 4;
+    for (int i = threadIdx.x; i < kPoolBwdRows * h4; i += 256) {
+        const int r = i / h4;
+        const int col = (i - r * h4) * 4;
+        const int64_t row = r0 + r;
+        if (row >= total) break;
+        const int b = seq_of[r];
+        f32x4 d = {0.f, 0.f, 0.f, 0.f};
+        if (b >= 0) d = *reinterpret_cast<const f32x4*>(dpooled + (int64_t)b * H + col) * scale_of[r];
+        if constexpr (DH_BF16)
+            *reinterpret_cast<uint2*>(static_cast<uint16_t*>(dh) + row * H + col) = uint2{pack_bf16x2(d.x, d.y), pack_bf16x2(d.z, d.w)};
+        else
+            *reinterpret_cast<f32x4*>(static_cast<float*>(dh) + row * H + col) = d;
+    }
+}
+
 // dst row i = src row idx[i] (GATHER) or dst row idx[i] = src row i (scatter); rows of H fp32 values, H % 4 == 0
 template <bool GATHER>
 __global__ __launch_bounds__(256) void move_rows_kernel(const float* __restrict__ src, const int64_t* __restrict__ idx,
@@ -750,9 +838,26 @@ int cm3p_pool_fwd(const void* h, int h_dtype, const int64_t* mask, float* pooled
                   int cls, void* stream) {
     CM3P_REQUIRE(h && pooled && Bn > 0 && S > 0 && H > 0 && H % 4 == 0 && (h_dtype == CM3P_F32 || h_dtype == CM3P_BF16));
     CM3P_REQUIRE(cls || h_dtype == CM3P_F32 || reinterpret_cast<uintptr_t>(h) % 8 == 0);  // (bf16 rows: 8-byte loads of 4 columns)
+    const bool packed = (cls & CM3P_POOL_PACKED) != 0;
+    cls &= ~CM3P_POOL_PACKED;
+    CM3P_REQUIRE(!packed || (mask && reinterpret_cast<uintptr_t>(mask) % 4 == 0));  // packed rows: `mask` is their cu_seqlens
     hipStream_t s = static_cast<hipStream_t>(stream);
     const bool bf = h_dtype == CM3P_BF16;
-    if (cls) {
+    if (packed) {
+        CM3P_REQUIRE(h_dtype == CM3P_F32 || reinterpret_cast<uintptr_t>(h) % 8 == 0);
+        const int* cu = reinterpret_cast<const int*>(mask);
+        if (cls) {
+            if (bf) pool_cls_packed_kernel<<<Bn, 256, 0, s>>>(static_cast<const uint16_t*>(h), cu, pooled, H);
+            else pool_cls_packed_kernel<<<Bn, 256, 0, s>>>(static_cast<const float*>(h), cu, pooled, H);
+        } else {
+            CM3P_REQUIRE(partial);
+            const int nch = cm3p_pool_chunks(S);
+            if (bf) pool_partial_packed_kernel<<<Bn * nch, 256, 0, s>>>(static_cast<const uint16_t*>(h), cu, partial, H, nch);
+            else pool_partial_packed_kernel<<<Bn * nch, 256, 0, s>>>(static_cast<const float*>(h), cu, partial, H, nch);
+            CM3P_LAUNCH_CHECK();
+            pool_final_packed_kernel<<<Bn, 256, 0, s>>>(partial, cu, pooled, count, H, nch);
+        }
+    } else if (cls) {
         if (bf) pool_cls_kernel<<<Bn, 256, 0, s>>>(static_cast<const uint16_t*>(h), pooled, S, H);
         else pool_cls_kernel<<<Bn, 256, 0, s>>>(static_cast<const float*>(h), pooled, S, H);
     } else {
@@ -770,9 +875,21 @@ int cm3p_pool_fwd(const void* h, int h_dtype, const int64_t* mask, float* pooled
 int cm3p_pool_bwd(const float* dpooled, const int64_t* mask, const float* count, void* dh, int dh_dtype, int Bn, int S, int H, int cls,
                   void* stream) {
     CM3P_REQUIRE(dpooled && dh && Bn > 0 && S > 0 && H > 0 && H % 4 == 0);
-    CM3P_REQUIRE(cls || !mask || count);
+    const bool packed = (cls & CM3P_POOL_PACKED) != 0;
+    cls &= ~CM3P_POOL_PACKED;
+    CM3P_REQUIRE(packed || cls || !mask || count);
     CM3P_REQUIRE(dh_dtype == CM3P_F32 || dh_dtype == CM3P_BF16);
+    CM3P_REQUIRE(!packed || (mask && reinterpret_cast<uintptr_t>(mask) % 4 == 0));  // packed rows: `mask` is their cu_seqlens
     hipStream_t s = static_cast<hipStream_t>(stream);
+    if (packed) {  // S is the row count of dh; count is not read (a packed sequence's count is its length)
+        const int64_t total = S;
+        const int grid = (int)((total + kPoolBwdRows - 1) / kPoolBwdRows);
+        const int* cu = reinterpret_cast<const int*>(mask);
+        if (dh_dtype == CM3P_BF16) pool_bwd_packed_kernel<true><<<grid, 256, 0, s>>>(dpooled, cu, dh, Bn, total, H, cls);
+        else pool_bwd_packed_kernel<false><<<grid, 256, 0, s>>>(dpooled, cu, dh, Bn, total, H, cls);
+        CM3P_LAUNCH_CHECK();
+        return CM3P_OK;
+    }
     const int grid = ew_grid((int64_t)Bn * S * (H / 4));
     if (dh_dtype == CM3P_BF16) pool_bwd_kernel<true><<<grid, 256, 0, s>>>(dpooled, mask, count, dh, Bn, S, H, cls);
     else pool_bwd_kernel<false><<<grid, 256, 0, s>>>(dpooled, mask, count, dh, Bn, S, H, cls);

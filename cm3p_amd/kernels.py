@@ -11,7 +11,7 @@ from typing import Optional
 import torch
 
 from . import _lib
-from ._lib import ADD_A_BF16, BF16, EPI_BF16, EPI_BF16_RESID, EPI_F32, EPI_F32_RESID, F32, call, dt, ptr, query, stream
+from ._lib import ADD_A_BF16, BF16, POOL_PACKED, EPI_BF16, EPI_BF16_RESID, EPI_F32, EPI_F32_RESID, F32, call, dt, ptr, query, stream
 
 Tensor = torch.Tensor
 
@@ -699,9 +699,17 @@ def bias_gelu_bwd(da: Tensor, z: Tensor, bias: Tensor):
 
 
 # ------------------------------------------------------------------------------------------------ pooling
-def pool_fwd(h: Tensor, mask: Optional[Tensor], Bn: int, S: int, cls: bool):
-    """h [Bn, S, H] fp32 or bf16 (fp32 accumulation either way) -> (pooled [Bn, H] fp32, count [Bn] fp32)."""
+def pool_fwd(h: Tensor, mask: Optional[Tensor], Bn: int, S: int, cls: bool, cu: Optional[Tensor] = None, total: Optional[int] = None):
+    """h [Bn, S, H] fp32 or bf16 (fp32 accumulation either way) -> (pooled [Bn, H] fp32, count [Bn] fp32).
+    Packed rows: h [total, H], cu int32 [Bn + 1] (sequence b owns rows cu[b] .. cu[b+1]-1), S = max_seqlen, no mask."""
     H = h.shape[-1]
+    if cu is not None:  # (the entry point takes cu_seqlens where a padded batch has its mask, flagged in cls)
+        _packed_pool_args(h.shape[0], mask, Bn, S, cu, total)
+        pooled = torch.empty((Bn, H), dtype=torch.float32, device=h.device)
+        count = torch.empty((Bn,), dtype=torch.float32, device=h.device)
+        part = None if cls else torch.empty((Bn, query("cm3p_pool_chunks", S), H), dtype=torch.float32, device=h.device)
+        call("cm3p_pool_fwd", ptr(h), dt(h), ptr(cu, torch.int32), ptr(pooled), ptr(part), ptr(count), Bn, S, H, int(cls) | POOL_PACKED, stream())
+        return pooled, count
     pooled = torch.empty((Bn, H), dtype=torch.float32, device=h.device)
     count = torch.empty((Bn,), dtype=torch.float32, device=h.device)
     part = None if cls else torch.empty((Bn, query("cm3p_pool_chunks", S), H), dtype=torch.float32, device=h.device)
@@ -709,9 +717,37 @@ def pool_fwd(h: Tensor, mask: Optional[Tensor], Bn: int, S: int, cls: bool):
     return pooled, count
 
 
-def pool_bwd(dpooled: Tensor, mask: Optional[Tensor], count: Tensor, Bn: int, S: int, cls: bool, dtype: torch.dtype = torch.float32) -> Tensor:
-    """-> dh [Bn * S, H] of `dtype` (fp32, or bf16 when the pooled rows were a bf16 residual stream's: one rounding of the fp32 value)."""
+def _packed_pool_args(rows: int, mask, Bn: int, S: int, cu: Tensor, total: Optional[int]) -> int:
+    """What can be checked of a packed description without a host read (the forward kernels read the rows cu names, as the varlen
+    attention kernels do: _PoolPackedFn checks cu itself; the backward writes rows below total only, whatever cu holds)."""
+    total = rows if total is None else int(total)
+    if mask is not None:
+        raise ValueError("packed rows carry no mask: pass cu alone")
+    if cu.numel() != Bn + 1:
+        raise ValueError(f"cu has {cu.numel()} entries for {Bn} sequences (Bn + 1 expected)")
+    if not 0 < total <= rows:
+        raise ValueError(f"total {total} must lie in 1 .. {rows}, the rows of the packed tensor")
+    return total
+
+
+def pool_bwd(dpooled: Tensor, mask: Optional[Tensor], count: Optional[Tensor], Bn: int, S: int, cls: bool, dtype: torch.dtype = torch.float32,
+             cu: Optional[Tensor] = None, total: Optional[int] = None, out: Optional[Tensor] = None) -> Tensor:
+    """-> dh [Bn * S, H] of `dtype` (fp32, or bf16 when the pooled rows were a bf16 residual stream's: one rounding of the fp32 value).
+    Packed rows (cu int32 [Bn + 1], total): dh [total, H], every row written once, zeros at and past cu[Bn].  out: write the first
+    `total` rows of this [>= total, H] tensor instead of a new one (it fixes the dtype)."""
     H = dpooled.shape[-1]
+    if cu is not None:
+        if total is None and out is None:
+            raise ValueError("packed pooling backward needs total (the rows of dh)")
+        dh = out if out is not None else torch.empty((int(total), H), dtype=dtype, device=dpooled.device)
+        if dh.dim() != 2 or dh.shape[1] != H or dpooled.shape[0] != Bn:
+            raise ValueError(f"dh {tuple(dh.shape)} / dpooled {tuple(dpooled.shape)} do not fit {Bn} sequences of width {H}")
+        total = _packed_pool_args(dh.shape[0], mask, Bn, S, cu, total)
+        if total >= 2 ** 31:
+            raise ValueError("packed pooling backward: the row count must fit an int")
+        call("cm3p_pool_bwd", ptr(dpooled, torch.float32), ptr(cu, torch.int32), ptr(count), ptr(dh), dt(dh), Bn, total, H, int(cls) | POOL_PACKED,
+             stream())  # (S carries the row count of dh)
+        return dh
     dh = torch.empty((Bn * S, H), dtype=dtype, device=dpooled.device)
     call("cm3p_pool_bwd", ptr(dpooled, torch.float32), ptr(mask, torch.int64), ptr(count), ptr(dh), dt(dh), Bn, S, H, int(cls), stream())
     return dh

@@ -89,6 +89,41 @@ class _PoolFn(torch.autograd.Function):
         return dh.view(Bn, S, -1), None, None
 
 
+class _PoolPackedFn(torch.autograd.Function):
+    """_PoolFn for rows the caller packed: h [total, H] fp32 or bf16, cu int32 [Bn + 1] (sequence b owns rows cu[b] .. cu[b+1]-1),
+    max_seqlen -> pooled [Bn, H] fp32.  cls: row cu[b]; else the mean of the sequence's rows, summed in the order of the padded
+    kernels, so the result has the bits _PoolFn gives on a right-padded batch of the same rows.  The gradient
+    is [total, H] in h's dtype, every row written once (zeros at and past cu[Bn]).  One host read checks that cu describes rows of h:
+    the kernels index h with it."""
+
+    @staticmethod
+    def forward(ctx, h: Tensor, cu: Tensor, max_seqlen: int, cls: bool):
+        if h.dim() != 2:
+            raise ValueError("packed pooling takes the (total_nnz, H) rows of an unpadded batch")
+        total = h.shape[0]
+        cu = cu.to(device=h.device, dtype=torch.int32).reshape(-1).contiguous()
+        if cu.numel() < 2:
+            raise ValueError("cu_seqlens needs at least two entries (batch + 1)")
+        lens = cu[1:] - cu[:-1]
+        first, last, mx, mn = torch.stack((cu[0], cu[-1], lens.max(), lens.min())).tolist()
+        if first != 0 or last > total or mn < 0:
+            raise ValueError(f"cu_seqlens must start at 0, not decrease and end within the {total} rows; got start {first}, end {last}, min length {mn}")
+        if int(max_seqlen) < mx:
+            raise ValueError(f"max_seqlen {max_seqlen} is smaller than the longest sequence ({mx})")
+        Bn, S = cu.numel() - 1, max(int(max_seqlen), 1)
+        pooled, _ = K.pool_fwd(h.detach().contiguous(), None, Bn, S, cls, cu=cu, total=total)  # (.contiguous() of a y[:total] slice: no copy)
+        ctx.pack = (cu, Bn, S, total, cls)
+        ctx.hdtype = h.dtype
+        return pooled
+
+    @staticmethod
+    def backward(ctx, dp: Tensor):
+        cu, Bn, S, total, cls = ctx.pack
+        dh = K.pool_bwd(dp.contiguous(), None, None, Bn, S, cls, dtype=torch.bfloat16 if ctx.hdtype == torch.bfloat16 else torch.float32,
+                        cu=cu, total=total)
+        return dh, None, None, None
+
+
 class _ProjectFn(torch.autograd.Function):
     """y = x W^T in fp32: the bias-free projection heads (ref:cm3p/modeling_cm3p.py:761-762,959,971)."""
 
@@ -390,6 +425,13 @@ class CM3PPreTrainedModel(PreTrainedModel):
             module.logit_scale.fill_(cfg.logit_scale_init_value)
 
 
+def _pool_packed(h: Tensor, cu_seqlens: Tensor, max_seqlen: Optional[int], cls: bool) -> Tensor:
+    """Pooled rows [Bn, H] fp32 of caller-packed rows h (total_nnz, H); max_seqlen None: the longest sequence (one host read)."""
+    if max_seqlen is None:
+        max_seqlen = int((cu_seqlens[1:] - cu_seqlens[:-1]).max().item())
+    return _PoolPackedFn.apply(h, cu_seqlens, int(max_seqlen), cls)
+
+
 def _require_gpu(t: Tensor, what: str):
     if not t.is_cuda:
         raise RuntimeError(f"cm3p_amd: {what} must be on the GPU; this build has no CPU path (use the reference package on CPU)")
@@ -404,6 +446,7 @@ class CM3PMetadataTransformer(nn.Module):
         self.config = config
         self.encoder = CM3PEncoder(config)
         self.unpad_inputs = None  # as CM3PBeatmapTransformer.unpad_inputs: run padded (B, L) batches on their valid tokens only
+        self.pool_unpadded = False  # opt-in: pool caller-packed rows (CLS and mean), which the reference does not implement
 
     def get_input_embeddings(self):
         return self.encoder.get_input_embeddings()
@@ -414,6 +457,9 @@ class CM3PMetadataTransformer(nn.Module):
     def forward(self, input_ids: Optional[Tensor] = None, attention_mask: Optional[Tensor] = None, indices=None, cu_seqlens=None,
                 max_seqlen=None, batch_size=None, seq_len=None, output_attentions=None, output_hidden_states=None,
                 output_pooler: bool = True) -> BaseModelOutputWithPooling:
+        """Caller-packed rows (`cu_seqlens` given) are pooled only with `self.pool_unpadded = True`; otherwise the call raises the
+        reference's NotImplementedError.  A caller-packed batch has no variation axis, so its `pooler_output` is 2-D, [Bn, H] in
+        fp32 (one row per sequence of `cu_seqlens`), while `last_hidden_state` stays (total_nnz, H)."""
         if input_ids is None:
             raise ValueError("You have to specify input_ids")
         if indices is not None or cu_seqlens is not None:
@@ -423,14 +469,15 @@ class CM3PMetadataTransformer(nn.Module):
                 raise ValueError("unpadded inputs need cu_seqlens (and max_seqlen)")
             if output_attentions:
                 raise NotImplementedError("output_attentions with unpadded inputs: attention probabilities are (B, nh, S, S) tensors of a padded batch")
-            if output_pooler:  # (before the encoder runs: the reference's own message, ref:cm3p/modeling_cm3p.py:383-384)
+            if output_pooler and not self.pool_unpadded:  # (before the encoder runs: the reference's own message, ref:cm3p/modeling_cm3p.py:383-384)
                 raise NotImplementedError("Pooling with unpadded input is not implemented yet.")
             _require_gpu(input_ids, "input_ids")
             h = self.encoder(input_ids=input_ids, cu_seqlens=cu_seqlens, max_seqlen=max_seqlen, output_hidden_states=bool(output_hidden_states))
             hiddens = None
             if output_hidden_states:
                 h, hiddens = h
-            return BaseModelOutputWithPooling(last_hidden_state=h, pooler_output=None, hidden_states=hiddens, attentions=None)
+            pooled = _pool_packed(h, cu_seqlens, max_seqlen, bool(self.config.cls_embed)) if output_pooler else None
+            return BaseModelOutputWithPooling(last_hidden_state=h, pooler_output=pooled, hidden_states=hiddens, attentions=None)
         _require_gpu(input_ids, "input_ids")
         is_3d = input_ids.dim() == 3
         B0 = input_ids.size(0)
@@ -509,6 +556,7 @@ class CM3PBeatmapTransformer(nn.Module):
         self.audio_encoder = CM3PAudioEncoder(config.audio_config)
         self.encoder = CM3PEncoder(config)
         self.unpad_inputs = None  # None: follow config._attn_implementation == 'flash_attention_2' (the reference's rule)
+        self.pool_unpadded = False  # opt-in: mean pooling of caller-packed rows, which the reference does not implement
 
     def get_input_embeddings(self):
         return self.encoder.get_input_embeddings()
@@ -528,7 +576,8 @@ class CM3PBeatmapTransformer(nn.Module):
         if indices is not None or cu_seqlens is not None:
             # Caller-supplied unpadded rows (ref:cm3p/modeling_cm3p.py:911-931 with indices / cu_seqlens / max_seqlen given, layout of
             # _unpad_cm3p_input :65-104): input_ids (total_nnz,), last_hidden_state stays (total_nnz, H), CLS pooling reads row
-            # cu_seqlens[:-1] of it (:624-627); mean pooling of unpadded rows is not implemented in the reference either (:628-629).
+            # cu_seqlens[:-1] of it (:624-627); mean pooling of unpadded rows is not implemented in the reference (:628-629) and here
+            # only behind pool_unpadded: pooler_output [B, H] fp32 from the packed pooling kernels.
             if cu_seqlens is None:
                 raise ValueError("unpadded inputs need cu_seqlens (and max_seqlen)")
             if inputs_embeds is not None:
@@ -542,7 +591,7 @@ class CM3PBeatmapTransformer(nn.Module):
                 n = int(count.item())
                 if n != rows.shape[0]:
                     raise RuntimeError(f"shape mismatch: {n} audio placeholder tokens but {rows.shape[0]} audio embeddings")
-            if output_pooler and not self.config.cls_embed:  # before the encoder runs (ref:cm3p/modeling_cm3p.py:628-629)
+            if output_pooler and not self.config.cls_embed and not self.pool_unpadded:  # before the encoder runs (ref:cm3p/modeling_cm3p.py:628-629)
                 raise NotImplementedError("Pooling with unpadded input is not implemented yet.")
             h = self.encoder(input_ids=input_ids, position_ids=position_ids, audio_slot=slot, audio_rows=rows, cu_seqlens=cu_seqlens,
                              max_seqlen=max_seqlen, output_hidden_states=ohs)
@@ -550,9 +599,9 @@ class CM3PBeatmapTransformer(nn.Module):
             if ohs:
                 h, hiddens = h
             pooled = None
-            if output_pooler:
-                if not self.config.cls_embed:
-                    raise NotImplementedError("Pooling with unpadded input is not implemented yet.")
+            if output_pooler and not self.config.cls_embed:
+                pooled = _pool_packed(h, cu_seqlens, max_seqlen, False)
+            elif output_pooler:
                 first = cu_seqlens[:-1].to(device=h.device, dtype=torch.int64).contiguous()
                 pooled = _TakeRowsFn.apply(h, first)
                 if pooled.dtype != torch.float32:  # bf16 residual stream: the pooled rows widened exactly, as _PoolFn returns them
@@ -692,6 +741,16 @@ class CM3PModel(CM3PPreTrainedModel):
         self.gather_negatives = False
         self.unpad_inputs = None  # True / False overrides the reference's rule (unpad iff attn_implementation is flash_attention_2)
         self.post_init()
+
+    @property
+    def pool_unpadded(self) -> bool:
+        """Opt-in pooling of caller-packed rows (`cu_seqlens` given), which the reference does not implement: set on both towers,
+        True when both have it.  Off by default: such a call then raises the reference's NotImplementedError."""
+        return bool(self.beatmap_model.pool_unpadded) and bool(self.metadata_model.pool_unpadded)
+
+    @pool_unpadded.setter
+    def pool_unpadded(self, value: bool):
+        self.beatmap_model.pool_unpadded = self.metadata_model.pool_unpadded = bool(value)
 
     def _overlap_towers(self, input_ids, metadata_ids) -> bool:
         """Run the metadata tower on a second stream beside the beatmap tower?  (CM3P_TOWER_OVERLAP=0 switches it off.)"""

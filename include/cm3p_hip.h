@@ -387,11 +387,22 @@ int cm3p_bias_gelu_bwd(const void* da, int da_dtype, const float* z, const float
  * h: [Bn, S, H] of h_dtype (CM3P_F32, or CM3P_BF16: the bf16 residual stream of a forward-only call; accumulated in fp32 in
  * the same order, so bf16 rows pool to the bits of their fp32 upcast), mask: [Bn, S] int64 or NULL, pooled: [Bn, H] fp32.
  * partial: fp32 workspace [Bn, cm3p_pool_chunks(S), H]; count: [Bn] fp32, sum of the mask row (saved for the backward pass).
+ *
+ * Packed rows: CM3P_POOL_PACKED or-ed into `cls` (the argument lists are unchanged; any other non-zero bit of `cls` still means
+ * CLS pooling).  h is then [total, H], and `mask` does not point to a mask but to the int32 cu_seqlens of the rows (Bn + 1 entries
+ * on the device, as in cm3p_attn_fwd_varlen; required): sequence b owns rows cu_seqlens[b] .. cu_seqlens[b+1]-1, which must be
+ * rows of h.  S is max_seqlen (it sizes `partial` only: the result does not depend on it as long as no sequence is longer);
+ * count[b] is the sequence length; with CLS pooling pooled[b] = h[cu_seqlens[b]].  The sums run over the valid rows in the order
+ * of the padded form, so the result is, bit for bit, what the padded form gives on a right-padded batch of the same (finite) rows.
  */
+#define CM3P_POOL_PACKED 2
 int cm3p_pool_chunks(int S);
 int cm3p_pool_fwd(const void* h, int h_dtype, const int64_t* mask, float* pooled, float* partial, float* count, int Bn, int S, int H,
                   int cls, void* stream);
-/* dh: [Bn * S, H] of dh_dtype (CM3P_F32, or CM3P_BF16: written directly in the dtype of a bf16 residual stream, one rounding). */
+/* dh: [Bn * S, H] of dh_dtype (CM3P_F32, or CM3P_BF16: written directly in the dtype of a bf16 residual stream, one rounding).
+ * Packed rows (CM3P_POOL_PACKED in `cls`, `mask` = int32 cu_seqlens as above; count is not read): dh is [S, H], S being the row
+ * count here, not a sequence length.  A row of sequence b gets dpooled[b] / max(len_b, 1e-9), or with CLS pooling dpooled[b] in
+ * row cu_seqlens[b] and zeros elsewhere.  Every row 0 .. S-1 is written once; rows at or past cu_seqlens[Bn] get zeros. */
 int cm3p_pool_bwd(const float* dpooled, const int64_t* mask, const float* count, void* dh, int dh_dtype, int Bn, int S, int H,
                   int cls, void* stream);
 

@@ -6,8 +6,12 @@ the judged number comes from bench.py):
               default config, B x 4096 beatmap tokens -> beatmap_embeds
   variations  evaluation with V metadata variations per row (ref:configs/train/default.yaml:147 test_metadata_variations: 1000):
               a (B, V, 256) metadata batch through the metadata tower + logits + loss
+  packed-pool mean pooling of the valid rows of the variation-evaluation shape (--pool-seqs 8000 sequences, L = 256, H = 256, valid
+              lengths ~ U{1..128}), forward + backward, two ways on the same rows, alternating in one process: the packed pooling
+              node (_PoolPackedFn on the [total, H] rows) against re-padding them (cm3p_scatter_rows_f32) and pooling the padded
+              batch (_PoolFn).  Only when named; no model is built.  The two times and the bytes each way moves go to --pool-out.
 
-    python tools/bench_eval.py [extract] [variations] [--batch 32] [--variations 1000] [--var-batch 8] [--iters 5]
+    python tools/bench_eval.py [extract] [variations] [packed-pool] [--batch 32] [--variations 1000] [--var-batch 8] [--iters 5]
                                [--residual {fp32,bf16,both}]
 
 --residual: the residual stream of the encoders (model.set_residual_dtype): fp32 (the default), bf16, or both - the two modes timed in
@@ -71,6 +75,59 @@ def breakdown(fn, top=8):
     return {k: round(v[1], 3) for k, v in sorted(prof.items(), key=lambda kv: -kv[1][1])[:top]}
 
 
+def packed_pool(args, dev):
+    """_PoolPackedFn against scatter + _PoolFn on the same valid rows: ms per forward + backward and the algorithmic bytes of each."""
+    from cm3p_amd.encoder import _PadRowsFn
+    from cm3p_amd.modeling_cm3p import _PoolFn, _PoolPackedFn
+
+    Bn, L, H = args.pool_seqs, 256, 256
+    g = torch.Generator().manual_seed(11)
+    lens = torch.randint(1, 129, (Bn,), generator=g)
+    mask = (torch.arange(L)[None, :] < lens[:, None]).to(torch.int64).to(dev)
+    idx = torch.nonzero(mask.flatten()).flatten()
+    cu = torch.nn.functional.pad(torch.cumsum(lens, 0), (1, 0)).to(torch.int32).to(dev)
+    total, max_s = int(lens.sum()), int(lens.max())
+    rows = torch.randn(total, H, generator=g).to(dev).requires_grad_(True)
+    dp = torch.randn(Bn, H, generator=g).to(dev)
+
+    def packed():
+        rows.grad = None
+        _PoolPackedFn.apply(rows, cu, max_s, False).backward(dp)
+
+    def padded():
+        rows.grad = None
+        _PoolFn.apply(_PadRowsFn.apply(rows, idx, total, Bn * L).view(Bn, L, H), mask, False).backward(dp)
+
+    ms = {"packed": [], "padded": []}
+    for _ in range(args.rounds):
+        for name, fn in (("packed", packed), ("padded", padded)):
+            ms[name].append(timed(fn, args.iters))
+    ms = {k: sorted(v)[len(v) // 2] for k, v in ms.items()}
+    row, chunks = H * 4, -(-max_s // 128)
+    small = Bn * row * 2 + Bn * 4  # pooled, dpooled, count
+    nbytes = {
+        # rows read once; the chunk sums written and read; every row of the gradient written once
+        "packed": 2 * total * row + 2 * Bn * chunks * row + small + (Bn + 1) * 4 * 3,
+        # zero fill + scatter (read, write) of the rows; the padded batch and its mask read (twice: chunk sums, count); the padded
+        # gradient written, then its valid rows gathered (read, write); the row indices read twice
+        "padded": Bn * L * row + 2 * total * row + Bn * L * row + 3 * Bn * L * 8 + 2 * Bn * (-(-L // 128)) * row + Bn * L * row
+                  + 2 * total * row + 2 * total * 8 + small,
+    }
+    out = {"path": "packed-pool", "sequences": Bn, "L": L, "H": H, "valid_rows": total, "max_seqlen": max_s, "iters": args.iters,
+           "rounds": args.rounds, "ms_packed": round(ms["packed"], 4), "ms_scatter_then_padded": round(ms["padded"], 4),
+           "ratio_packed_over_padded": round(ms["packed"] / ms["padded"], 4), "bytes_packed": nbytes["packed"], "bytes_scatter_then_padded": nbytes["padded"],
+           "GBps_packed": round(nbytes["packed"] / ms["packed"] / 1e6, 1), "GBps_scatter_then_padded": round(nbytes["padded"] / ms["padded"] / 1e6, 1)}
+    print(json.dumps(out))
+    if args.pool_out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.pool_out)), exist_ok=True)
+        with open(args.pool_out, "w") as f:
+            f.write("Mean pooling of the valid rows of the variation-evaluation shape, forward + backward, fp32 rows (tools/bench_eval.py packed-pool).\n"
+                    "packed: _PoolPackedFn on the [total, H] rows.  scatter_then_padded: cm3p_scatter_rows_f32 to [Bn, L, H], then _PoolFn.\n"
+                    "ms: median over the rounds of the mean of `iters` calls, the two variants alternating in one process; bytes: algorithmic.\n")
+            for k, v in out.items():
+                f.write(f"{k:28s} {v}\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("what", nargs="*", default=["extract", "variations"])
@@ -83,8 +140,14 @@ def main():
     ap.add_argument("--meta-valid", type=float, default=1.0,
                     help="variations: valid length of a metadata row ~ U{1..meta_valid * L} (right-padded); below 1 the run is repeated with "
                          "unpadded execution (model.unpad_inputs = True)")
+    ap.add_argument("--pool-seqs", type=int, default=8000, help="packed-pool: number of sequences")
+    ap.add_argument("--pool-out", default=None, help="packed-pool: also write the result to this text file")
     args = ap.parse_args()
     dev = torch.device("cuda", 0)
+    if "packed-pool" in args.what:
+        packed_pool(args, dev)
+        if set(args.what) == {"packed-pool"}:
+            return
     cfg = CM3PConfig(beatmap_config=dict(cls_embed=False), metadata_config=dict(cls_embed=False))
     torch.manual_seed(0)
     model = CM3PModel(cfg).to(dev).eval()
