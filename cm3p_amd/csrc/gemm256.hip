@@ -329,6 +329,16 @@ __global__ __launch_bounds__(kThreads, kWN == 4 ? 2 : 1) void gemm256_kernel(con
                                 const uint4 rb = *reinterpret_cast<const uint4*>(reinterpret_cast<const uint16_t*>(R) + m * ldc + n);
                                 x = uint4{add_bf16x2(x.x, rb.x), add_bf16x2(x.y, rb.y), add_bf16x2(x.z, rb.z), add_bf16x2(x.w, rb.w)};
                             }
+                            if constexpr (EPI == CM3P_EPI_BF16) {
+                                // N % 8 == 4 (cm3p_gemm_bf16 asks for N % 4 == 0 only): the row's last chunk holds four columns - a
+                                // 16-byte store there would land on the next row's first four and, on the last row, past the matrix.
+                                // (With ldc % 8 == 4 the 16-byte stores of the full chunks are 8-byte aligned on every odd row: global
+                                // memory takes unaligned dwordx4 stores, and this path relies on that.)
+                                if (n + 8 > N) {
+                                    *reinterpret_cast<uint2*>(C + m * ldc + n) = uint2{x.x, x.y};
+                                    continue;
+                                }
+                            }
                             *reinterpret_cast<uint4*>(C + m * ldc + n) = x;
                         }
                     }

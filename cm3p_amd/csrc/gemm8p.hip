@@ -6,7 +6,7 @@
 //     four phases of 16 MFMAs (one quadrant of the wave's 128 x 64 output each); a phase first requests the fragments it needs
 //     (12 / 4 / 8 / 0 ds_read_b128) and issues the LDS-DMA of ONE half-tile of a later k-tile, then passes a barrier and runs
 //     its MFMAs.  Three half-tiles are always in flight across the barriers behind ONE counted wait per k-tile
-//     (`s_waitcnt vmcnt(6)`, never 0 inside the loop).
+//     (`s_waitcnt vmcnt(6)`, never 0 inside the loop; the REBAL instances add a `vmcnt(10)` for the half-tile they read early).
 //   * The two waves of a SIMD (w and w + 4: wave rows 0 and 1) run one barrier apart: while one is in its MFMA cluster the other
 //     reads fragments and issues DMA.
 //   * The ring does not drain between work items: the half-tile stream simply continues with the next item's k-tiles, and the
@@ -21,6 +21,8 @@
 // Synchronisation (p = phase, two barriers per phase; group 1 = waves 4-7 runs one barrier behind group 0):
 //   RAW  LDS-DMA data is ordered for a ds_read only by the issuing waves' counted vmcnt wait followed by a barrier the reader has
 //        passed.  The wait sits in phase 4 (before its first barrier) and covers the whole NEXT k-tile; reads start in phase 1.
+//        REBAL reads B-lo of the next k-tile already in phase 4, before that wait: its instances retire that one half-tile with a
+//        second counted wait, `vmcnt(10)` before the first barrier of phase 3 (group 1, one barrier behind, has passed it too).
 //   WAR  a slot is restaged >= 2 phases after its last ds_read (A-lo: read p1, restaged p3; B-hi: p2 -> p4; A-hi: p3 -> p1 of the
 //        next k-tile), except B-lo (read p1, restaged p2): its four reads are issued first and retired by `lgkmcnt(8)` before the
 //        first barrier of p1.
@@ -326,6 +328,11 @@ __global__ __launch_bounds__(512, 2) void gemm8p_kernel(const uint16_t* __restri
             for (int kk = 0; kk < 2; ++kk) fa[mt][kk] = oa.frag(smem, pofs + slot_off(0, kAH), mt, kk);
         __builtin_amdgcn_sched_barrier(0);
         oa.template stage<slot_off(0, kAL)>(0, lds_p);
+        // REBAL reads B-lo of the next k-tile in phase 4, ahead of that phase's counted wait, which is the first to cover it (the
+        // previous k-tile's vmcnt(6) leaves exactly B-lo, A-lo and B-hi of the next k-tile in flight).  Behind them this wave has
+        // issued A-hi, B-lo and A-lo since: 12 pieces, so vmcnt(10) retires the two oldest - B-lo of the next k-tile - and both of
+        // this phase's barriers lie between this wait and the read: the group that runs one barrier behind has passed it as well.
+        if constexpr (REBAL && !(CM3P_G8P_ABL & 8)) G8P_WAIT_VM(10);
         __builtin_amdgcn_s_barrier();
         G8P_WAIT_LGKM(0);
         __builtin_amdgcn_sched_barrier(0);
@@ -334,8 +341,8 @@ __global__ __launch_bounds__(512, 2) void gemm8p_kernel(const uint16_t* __restri
         __builtin_amdgcn_s_barrier();
         // ---- phase 4: (A-hi, B-lo); the counted wait retires every half-tile of the next k-tile
         if constexpr (REBAL) {
-            // B-lo of the NEXT k-tile (other parity; it landed before this k-tile began: retired by the previous k-tile's counted
-            // wait) into the set B-hi has just left; its slot is restaged two phases after the next k-tile starts
+            // B-lo of the NEXT k-tile (other parity; retired by every wave's vmcnt(10) of phase 3, two barriers back) into the set
+            // B-hi has just left; its slot is restaged two phases after the next k-tile starts
 #pragma unroll
             for (int nt = 0; nt < 2; ++nt)
 #pragma unroll

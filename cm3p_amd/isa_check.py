@@ -57,7 +57,8 @@ def loops(body: str):
 # ------------------------------------------------------------------------------------------------ gemm8p.hip
 def check_gemm8p(isa: str):
     """The half-tile ring of gemm8p.hip: per k-tile exactly 8 LDS-DMA instructions (4 half-tiles x 2 pieces per wave), 8 raw
-    barriers, 64 MFMAs and ONE vector-memory wait, `s_waitcnt vmcnt(6)`, right in front of a barrier; no scratch anywhere.
+    barriers, 64 MFMAs and ONE vector-memory wait, `s_waitcnt vmcnt(6)`, right in front of a barrier (the REBAL instances: a
+    `vmcnt(10)` in front of phase 3's first barrier before it, which retires the B-lo half-tile they read in phase 4); no scratch anywhere.
     Plain instances (one k-tile per loop iteration): the B-lo fragment reads are retired by `lgkmcnt(8 | 15)` in front of the first
     barrier of phase 1.  REBAL instances (two k-tiles per iteration, B register sets swapping roles): no such wait - B-lo is read
     three phases before its slot is restaged.  The MFMAs are inline assembly with tied accumulators: D and C are the same
@@ -77,9 +78,15 @@ def check_gemm8p(isa: str):
         _need(dma == 8 * n, f"{sym}: {dma} LDS-DMA instructions per loop iteration, expected {8 * n}")
         _need(seg.count("s_barrier") == 8 * n, f"{sym}: {seg.count('s_barrier')} barriers per loop iteration, expected {8 * n}")
         waits = re.findall(r"s_waitcnt vmcnt\((\d+)\)", seg)
-        _need(waits == ["6"] * n, f"{sym}: vector-memory waits in the k-loop are {waits}, expected {n} x vmcnt(6)")
-        for m in re.finditer(r"s_waitcnt vmcnt\(6\)", seg):
+        want = ["10", "6"] * n if rebal else ["6"]  # (the compiler may start the loop at either wait)
+        _need(sorted(waits) == sorted(want) and all(a != b for a, b in zip(waits, waits[1:])),
+              f"{sym}: vector-memory waits in the k-loop are {waits}, expected alternating {want}")
+        for m in re.finditer(r"s_waitcnt vmcnt\((?:6|10)\)", seg):
             _need(re.match(r"\s*s_barrier", seg[m.end():]), f"{sym}: a counted wait is not directly in front of a barrier")
+        if rebal:  # behind a vmcnt(6): A-hi, B-lo, A-lo = 6 pieces up to the vmcnt(10); behind that: B-hi = 2 up to the next vmcnt(6)
+            runs = [len(re.findall(r"\bglobal_load_lds_dwordx4\b", part)) for part in re.split(r"s_waitcnt vmcnt\(\d+\)", seg)]
+            after = runs[1:-1] + [runs[-1] + runs[0]]  # (the loop closes on itself)
+            _need(after == [6 if w == "6" else 2 for w in waits], f"{sym}: LDS-DMA instructions behind the counted waits {waits} are {after}")
         _need("scratch_" not in seg and not re.search(r"\b(buffer_|flat_|global_load_dword|global_store)", seg),
               f"{sym}: stray memory instruction in the k-loop")
         lg = re.findall(r"s_waitcnt lgkmcnt\((8|15)\)\s*\n\s*s_barrier", seg)

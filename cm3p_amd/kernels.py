@@ -175,7 +175,8 @@ def _gemm_tag(M: int, N: int, K: int, a_kc, b_kc, epilogue, split_k: int) -> str
     """Profiler tag = the kernel the library will pick (same rule as cm3p_gemm_bf16 in csrc/gemm.hip), spelled like rocprof."""
     q = 128 if K % 128 == 0 else 64  # (csrc/gemm.hip: k-split lengths are multiples of 128 where K allows it)
     kchunk = K if split_k <= 1 else -(-(-(-K // split_k)) // q) * q
-    big = K % 64 == 0 and kchunk % 64 == 0 and (-(-M // 256)) * (-(-N // 256)) * max(1, -(-K // kchunk)) >= 200
+    big = K % 64 == 0 and kchunk % 64 == 0 and (-(-M // 256)) * (-(-N // 256)) * max(1, -(-K // kchunk)) >= 200 \
+        and not os.environ.get("CM3P_GEMM_IMPL", "").startswith("1")  # (CM3P_GEMM_IMPL=128: the 128 x 128 kernel for every shape)
     b2s = lambda v: "true" if v else "false"
     if not big:
         return f"gemm_bf16_kernel<{b2s(a_kc)}, {b2s(b_kc)}, {epilogue}>"

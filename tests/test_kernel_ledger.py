@@ -15,6 +15,7 @@ DR = "tests/test_dropout_gpu.py::"
 MU = "tests/test_muon_gpu.py::"
 MG = "tests/test_model_gpu.py::"
 RK = "tests/test_row_kernels_gpu.py::"
+GK = "tests/test_gemm_kernels_gpu.py::"
 
 LEDGER = {
     "cm3p_layernorm_fwd": [KG + "test_layernorm_fwd_bwd", CH + "test_layernorm_with_many_rows_per_wave",
@@ -31,10 +32,17 @@ LEDGER = {
     "cm3p_audio_slots": [KG + "test_embed_ln_with_audio_override",
                          RK + "test_audio_slots_is_the_exclusive_cumsum"],
     "cm3p_gemm_bf16": [KG + "test_gemm_forward_layout", KG + "test_gemm_dgrad_layout", KG + "test_gemm_wgrad_layout",
-                       KG + "test_gemm256_forward_and_dgrad_layout", KG + "test_gemm256_wgrad_layout", KG + "test_gemm_bias_epilogue"],
-    "cm3p_gemm8p_set_grid": [KG + "test_ring_gemm_with_more_workgroups_than_cus_is_the_same_gemm"],
-    "cm3p_gemm8p_get_grid": [KG + "test_ring_gemm_with_more_workgroups_than_cus_is_the_same_gemm"],
-    "cm3p_qkv_gemm_rope": [KG + "test_fused_qkv_rope_gemm_and_inverse_in_attention_backward"],
+                       KG + "test_gemm256_forward_and_dgrad_layout", KG + "test_gemm256_wgrad_layout", KG + "test_gemm_bias_epilogue",
+                       GK + "test_forward_every_epilogue_at_one_to_five_k_tiles", GK + "test_forward_edge_tiles",
+                       GK + "test_k_strided_operands_with_ragged_tiles", GK + "test_wgrad_split_k_with_a_short_last_split",
+                       GK + "test_linear_wgrad_reaches_the_big_kernel_by_the_librarys_own_split", GK + "test_small_kernel_natively",
+                       GK + "test_pitched_operands_and_output", GK + "test_random_data_within_the_derived_bound"],
+    "cm3p_gemm8p_set_grid": [KG + "test_ring_gemm_with_more_workgroups_than_cus_is_the_same_gemm",
+                             GK + "test_forward_every_epilogue_at_one_to_five_k_tiles"],
+    "cm3p_gemm8p_get_grid": [KG + "test_ring_gemm_with_more_workgroups_than_cus_is_the_same_gemm",
+                             GK + "test_forward_every_epilogue_at_one_to_five_k_tiles"],
+    "cm3p_qkv_gemm_rope": [KG + "test_fused_qkv_rope_gemm_and_inverse_in_attention_backward",
+                           GK + "test_rope_epilogue_against_its_kernels_specification"],
     "cm3p_cast_f32_bf16": [CH + "test_cast_f32_bf16_is_rne"],
     "cm3p_cast_f32_bf16_t": [KG + "test_cast_with_transpose"],
     "cm3p_cast_f32_bf16_t_multi": [KG + "test_cast_with_transpose_of_many_matrices_in_one_launch"],
@@ -59,7 +67,8 @@ LEDGER = {
     "cm3p_attn_bwd_dropout_varlen": [DR + "test_attention_dropout_varlen_equals_padded"],
     "cm3p_geglu_fwd": [KG + "test_geglu_and_gelu",
                        RK + "test_geglu_against_float64"],
-    "cm3p_gemm_geglu": [KG + "test_wi_gemm_with_geglu_in_its_store_phase_equals_the_two_kernels"],
+    "cm3p_gemm_geglu": [KG + "test_wi_gemm_with_geglu_in_its_store_phase_equals_the_two_kernels",
+                        GK + "test_geglu_epilogue_against_float64_and_the_two_kernel_chain"],
     "cm3p_geglu_bwd": [KG + "test_geglu_and_gelu",
                        RK + "test_geglu_against_float64"],
     "cm3p_dropout_f32": [DR + "test_dropout_f32_matches_the_mask_and_packed_equals_padded"],

@@ -103,9 +103,13 @@ def test_gemm256_forward_and_dgrad_layout(K, M, N, K_):
 
 @pytest.mark.parametrize("T,N,K_", [(16384, 768, 2304), (32768, 776, 264)])
 def test_gemm256_wgrad_layout(K, T, N, K_):
+    """Both shapes reach the 256 x 256 ring kernel: the second one has only 4 x 2 tiles, but cm3p_gemm_wgrad_splits answers 49 for
+    it, cm3p_gemm_bf16 makes that 43 splits of 768 tokens, and 8 x 43 work items pass the 200-item threshold.  (Short and odd last
+    splits and ragged extents under few splits: tests/test_gemm_kernels_gpu.py.)"""
     g = torch.Generator().manual_seed(T + N)
     dy = torch.randint(-2, 3, (T, N), generator=g).float()
     x = torch.randint(-2, 3, (T, K_), generator=g).float()
+    assert K._gemm_tag(N, K_, T, False, False, 1, K._wgrad_splits(N, K_, T)) == "gemm8p_kernel<false, false, 1, true>"
     got = K.linear_wgrad(_bf(dy).to(DEV), _bf(x).to(DEV))
     _assert_close(got, dy.t() @ x, 0, 0, "wgrad256")
 
@@ -317,8 +321,11 @@ def test_rope_matches_reference_formula(K, per_batch):
 
 @pytest.mark.parametrize("T,S,nh,per_batch", [(600, 300, 2, False), (600, 300, 2, True), (8192, 2048, 12, False)])
 def test_fused_qkv_rope_gemm_and_inverse_in_attention_backward(K, T, S, nh, per_batch):
-    """Wqkv GEMM with the rotary epilogue == plain GEMM followed by the stand-alone RoPE kernel (bf16 ulp: the fused path
-    rotates fp32 accumulators before rounding); attention backward with the fused inverse rotation == separate passes."""
+    """Wqkv GEMM with the rotary epilogue against the plain GEMM followed by the stand-alone RoPE kernel, within bf16 ulps: the
+    128 x 128 kernel (the two T = 600 cases) rotates the fp32 accumulators and rounds once, the 256 x 256 kernels (T = 8192: 32 x 9
+    tiles) round the projection to bf16 first and rotate the rounded values, as the two-kernel chain does - the rounding changes at
+    the 200-tile threshold, and tests/test_gemm_kernels_gpu.py holds each kernel to its own float64 specification.  Attention
+    backward with the fused inverse rotation == separate passes."""
     from oracle import cm3p_oracle as O
 
     g = torch.Generator().manual_seed(T + nh)
