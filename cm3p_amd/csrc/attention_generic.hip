@@ -1,4 +1,5 @@
-// Attention for head sizes other than 64 (16 and 32; 64 is instantiated as a cross-check of the MFMA kernels).
+// Attention for head sizes other than 64 (16 and 32; 64 is instantiated as a cross-check of the MFMA kernels; 96 and 128 enter here and
+// run on the matrix-core kernels of attention_hd.hip).
 //
 // Every tower of the reference's default configuration has head_dim 64 (768 / 12, 256 / 4, 512 / 8:
 // ref:configs/model/default.yaml:16-19,88-91) and that is what attention.hip / attention_fwd.hip / attention_bwd_fused.hip are built for.  BASELINE.json's
@@ -10,6 +11,7 @@
 // Same contract as attention.hip (TF:integrations/sdpa_attention.py:153-163 with the mask rule of TF:masking_utils.py:141-151,168-179):
 //     visible(b, q, kv) = key_mask[b, kv] AND (window < 0 OR |q - kv| <= window);  rows with no visible key: exact zeros, lse = +inf.
 // Layout: qkv [B, S, 3, nh, D] bf16 (q, k already rotated: cm3p_rope_apply_generic), out [B, S, nh, D] bf16, lse / delta [B, nh, S] fp32.
+#include "attention_hd.h"
 #include "common.h"
 #include "dropout_rng.h"
 
@@ -292,7 +294,8 @@ __global__ __launch_bounds__(256) void rope_gen_kernel(uint16_t* __restrict__ qk
 
 extern "C" {
 
-int cm3p_attn_generic_supported(int head_dim) { return head_dim == 16 || head_dim == 32 || head_dim == 64; }
+// 16 / 32 / 64: the fp32 kernels above; 96 / 128: attention_hd.hip (no dropout form)
+int cm3p_attn_generic_supported(int head_dim) { return head_dim == 16 || head_dim == 32 || head_dim == 64 || cm3p_attn_hd_supported(head_dim); }
 
 int cm3p_attn_fwd_generic(const void* qkv, void* out, float* lse, const uint8_t* key_mask, int B, int S, int nh, int head_dim, int window,
                           float scale, void* stream) {
@@ -300,6 +303,8 @@ int cm3p_attn_fwd_generic(const void* qkv, void* out, float* lse, const uint8_t*
     CM3P_REQUIRE(cm3p_aligned16(qkv) && cm3p_aligned16(out));
     const dim3 grid((S + 63) / 64, nh, B);
     hipStream_t s = static_cast<hipStream_t>(stream);
+    if (cm3p_attn_hd_supported(head_dim))
+        return cm3p_attn_hd_fwd((const uint16_t*)qkv, (uint16_t*)out, lse, key_mask, B, S, nh, head_dim, window, scale, s);
 #define CM3P_GEN_FWD(DD) attn_gen_fwd_kernel<DD><<<grid, 64, 0, s>>>((const uint16_t*)qkv, (uint16_t*)out, lse, key_mask, S, nh, window, scale)
     if (head_dim == 16) CM3P_GEN_FWD(16);
     else if (head_dim == 32) CM3P_GEN_FWD(32);
@@ -315,6 +320,9 @@ int cm3p_attn_bwd_generic(const void* qkv, const void* out, const void* dout, co
     CM3P_REQUIRE(cm3p_aligned16(qkv) && cm3p_aligned16(out) && cm3p_aligned16(dout) && cm3p_aligned16(dqkv));
     const dim3 grid((S + 63) / 64, nh, B);
     hipStream_t s = static_cast<hipStream_t>(stream);
+    if (cm3p_attn_hd_supported(head_dim))
+        return cm3p_attn_hd_bwd((const uint16_t*)qkv, (const uint16_t*)out, (const uint16_t*)dout, lse, delta, (uint16_t*)dqkv, key_mask, B, S, nh,
+                                head_dim, window, scale, s);
 #define CM3P_GEN_BWD(DD)                                                                                                                   \
     attn_gen_dq_kernel<DD><<<grid, 64, 0, s>>>((const uint16_t*)qkv, (const uint16_t*)out, (const uint16_t*)dout, lse, delta, (uint16_t*)dqkv, \
                                                key_mask, S, nh, window, scale);                                                            \
@@ -332,6 +340,7 @@ int cm3p_attn_fwd_generic_dropout(const void* qkv, void* out, float* lse, const 
     CM3P_REQUIRE(qkv && out && lse && B > 0 && S > 0 && nh > 0 && scale > 0.f && cm3p_attn_generic_supported(head_dim));
     CM3P_REQUIRE(cm3p_aligned16(qkv) && cm3p_aligned16(out));
     CM3P_REQUIRE(thr >= 0 && thr <= 65536 && layer >= 0 && layer < (1 << 29));
+    CM3P_REQUIRE(!cm3p_attn_hd_supported(head_dim));  // the matrix-core kernels of 96 / 128 have no dropout form
     const dim3 grid((S + 63) / 64, nh, B);
     hipStream_t s = static_cast<hipStream_t>(stream);
     const cm3p_drop::DropCfg dc = cm3p_drop::make_cfg(layer, cm3p_drop::kSiteAttnProbs, thr, seed);
@@ -351,6 +360,7 @@ int cm3p_attn_bwd_generic_dropout(const void* qkv, const void* out, const void* 
     CM3P_REQUIRE(qkv && out && dout && lse && delta && dqkv && B > 0 && S > 0 && nh > 0 && scale > 0.f && cm3p_attn_generic_supported(head_dim));
     CM3P_REQUIRE(cm3p_aligned16(qkv) && cm3p_aligned16(out) && cm3p_aligned16(dout) && cm3p_aligned16(dqkv));
     CM3P_REQUIRE(thr >= 0 && thr <= 65536 && layer >= 0 && layer < (1 << 29));
+    CM3P_REQUIRE(!cm3p_attn_hd_supported(head_dim));  // the matrix-core kernels of 96 / 128 have no dropout form
     const dim3 grid((S + 63) / 64, nh, B);
     hipStream_t s = static_cast<hipStream_t>(stream);
     const cm3p_drop::DropCfg dc = cm3p_drop::make_cfg(layer, cm3p_drop::kSiteAttnProbs, thr, seed);

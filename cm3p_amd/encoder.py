@@ -50,10 +50,11 @@ Tensor = torch.Tensor
 def _check_supported(cfg):
     H, nh = cfg.hidden_size, cfg.num_attention_heads
     problems = []
-    if H % nh or H // nh not in (16, 32, 64):
+    if H % nh or H // nh not in (16, 32, 64, 96, 128):
         # 64: the MFMA kernels every default tower runs on; 16 / 32: csrc/attention_generic.hip (plain fp32 kernels, so that the
-        # reference's small test configurations run as well)
-        problems.append(f"head_dim must be 64 (or 16 / 32 on the generic kernels); hidden_size={H}, heads={nh}")
+        # reference's small test configurations run as well); 96 / 128: csrc/attention_hd.hip (MFMA kernels for widened towers:
+        # padded execution, no attention dropout)
+        problems.append(f"head_dim must be 64 (or 16 / 32 on the generic kernels, or 96 / 128 on the wide-head MFMA kernels); hidden_size={H}, heads={nh}")
     if getattr(cfg, "hidden_activation", "gelu") != "gelu":
         problems.append("hidden_activation must be 'gelu'")
     for flag in ("norm_bias", "attention_bias", "mlp_bias"):
@@ -617,6 +618,10 @@ class CM3PEncoder(nn.Module):
         if not self.training or (p_emb == 0.0 and p_attn == 0.0 and p_mlp == 0.0):
             return None
         _check_supported(cfg)  # (the fields are read per call: a value set after construction is held to the same rules)
+        hd = cfg.hidden_size // cfg.num_attention_heads
+        if p_attn > 0.0 and hd in K.HD_MFMA_SIZES:
+            raise NotImplementedError(f"attention_dropout > 0 in training mode at head_dim {hd}: the head_dim 96 / 128 attention kernels have no "
+                                      "dropout form (embedding and MLP dropout work)")
         if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
             raise NotImplementedError("dropout in training mode inside a CUDA-graph capture: the host-drawn seed would be frozen into the graph")
         seed = int(torch.randint(-(2 ** 63), 2 ** 63 - 1, (), dtype=torch.int64)) & (2 ** 64 - 1)
@@ -669,7 +674,7 @@ class CM3PEncoder(nn.Module):
         if (input_ids is None) == (inputs_embeds is None):
             raise ValueError("You must specify exactly one of input_ids or inputs_embeds")
         if cfg.hidden_size // cfg.num_attention_heads != 64:
-            # the generic attention kernels (head_dim 16 / 32) know the padded layout only
+            # the generic attention kernels (head_dim 16 / 32) and the wide-head ones (96 / 128) know the padded layout only
             if cu_seqlens is not None:
                 raise NotImplementedError("unpadded inputs need head_dim 64 (the generic attention kernels run padded batches)")
             if output_attentions:

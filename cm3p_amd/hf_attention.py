@@ -104,7 +104,7 @@ def _run(query: Tensor, key: Tensor, value: Tensor, key_mask: Optional[Tensor], 
     if not query.is_cuda:
         raise RuntimeError("cm3p_hip attention needs the tensors on an MI355X: there is no CPU path")
     if hd != 64 and not K.attn_generic_supported(hd):
-        raise NotImplementedError(f"cm3p_hip attention: head_dim {hd} is not supported (64, or 16 / 32 on the generic kernels)")
+        raise NotImplementedError(f"cm3p_hip attention: head_dim {hd} is not supported (64, 96 / 128 on their own MFMA kernels, or 16 / 32 on the generic kernels)")
     # -> [B, S, 3, nh, hd] bf16: a copy - this seam's price (the product's Wqkv GEMM writes that layout directly)
     qkv = torch.stack((query, key, value), dim=1).permute(0, 3, 1, 2, 4).to(torch.bfloat16).contiguous()
     return _AttnFn.apply(qkv, key_mask, B, S, nh, hd, window, scale)

@@ -191,7 +191,31 @@ def check_attention_fwd(isa: str):
         _need(body.count("s_waitcnt vmcnt(0)") >= 2, f"{sym}: the prologue wait / the final drain of the ring is missing")
 
 
-CHECKS = {"gemm8p.hip": check_gemm8p, "attention_fwd.hip": check_attention_fwd, "attention_bwd_fused.hip": check_attention_bwd_fused}
+# ------------------------------------------------------------------------------------------------ attention_hd.hip
+def check_attention_hd(isa: str):
+    """The head_dim 96 / 128 kernels (attention_hd.hip) are compiler-scheduled: nothing in them counts on an instruction pattern.  What
+    they count on is the register file - O^T and Q^T (dK/dV: two O^T-sized accumulators and K, V) stay resident across the tile loop -
+    so every one of the six instances must be built without a spill or a private segment, and on the matrix cores."""
+    descs = {}
+    for m in re.finditer(r"^\s*\.name:\s*(\S*attn_hd_(fwd|dq|dkv)_kernelILi(96|128)E\S*)\s*$", isa, re.M):
+        # one descriptor: the map entry this .name line sits in (from the previous "  - " item up to the next one)
+        start = isa.rfind("\n  - ", 0, m.start())
+        end = isa.find("\n  - ", m.end())
+        descs[(m.group(2), m.group(3))] = (m.group(1), isa[start:end if end >= 0 else len(isa)])
+    want = {(k, d) for k in ("fwd", "dq", "dkv") for d in ("96", "128")}
+    _need(set(descs) == want, f"attention_hd.hip: kernel descriptors found for {sorted(descs)}, expected {sorted(want)}")
+    for (kind, d), (sym, desc) in sorted(descs.items()):
+        for key in ("vgpr_spill_count", "private_segment_fixed_size"):
+            m = re.search(r"\." + key + r":\s*(\d+)", desc)
+            _need(m is not None, f"{sym}: no .{key} in the kernel descriptor")
+            _need(int(m.group(1)) == 0, f"{sym}: {key} = {m.group(1)} (the accumulators of a head_dim {d} tile must stay in registers)")
+        body = kernel_bodies(isa, f"attn_hd_{kind}_kernelILi{d}E")
+        _need(len(body) == 1, f"attn_hd_{kind}_kernel<{d}>: {len(body)} instances")
+        _need("v_mfma_f32_32x32x16_bf16" in next(iter(body.values())), f"{sym}: no v_mfma_f32_32x32x16_bf16")
+
+
+CHECKS = {"gemm8p.hip": check_gemm8p, "attention_fwd.hip": check_attention_fwd, "attention_bwd_fused.hip": check_attention_bwd_fused,
+          "attention_hd.hip": check_attention_hd}
 
 
 def check_file(src: str, flags: list[str]) -> None:

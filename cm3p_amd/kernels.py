@@ -353,9 +353,22 @@ def attn_fwd(qkv: Tensor, key_mask: Optional[Tensor], B: int, S: int, nh: int, w
     return out, lse
 
 
-# ---- head sizes other than 64 (csrc/attention_generic.hip: plain fp32 kernels so that every reference configuration runs)
+# ---- head sizes other than 64 (csrc/attention_generic.hip: plain fp32 kernels for 16 / 32 so that every reference configuration runs;
+# 96 / 128 leave through the same entry points for the matrix-core kernels of csrc/attention_hd.hip)
+HD_MFMA_SIZES = (96, 128)  # no dropout form, padded batches only
+
+
 def attn_generic_supported(head_dim: int) -> bool:
     return bool(query("cm3p_attn_generic_supported", int(head_dim)))
+
+
+def _attn_hd_prof(names: tuple, products: int, B: int, S: int, nh: int, hd: int, window: int) -> dict:
+    """tag / work of a head_dim 96 / 128 launch (the 16 / 32 kernels are not on any measured path and carry none).  `work` is the
+    algorithmic count of attn_fwd / attn_bwd (`products` matmuls of 2 B nh S keys hd; recomputed scores are not credited)."""
+    if hd not in HD_MFMA_SIZES:
+        return {}
+    keys = S if window < 0 else min(S, 2 * window + 1)
+    return dict(tag=_attn_tag(" + ".join(f"{n}<{hd}>" for n in names), window, False), work=2.0 * products * B * nh * S * keys * hd)
 
 
 def rope_apply_generic_(qkv: Tensor, cos: Tensor, sin: Tensor, B: int, S: int, nh: int, hd: int, per_batch: bool, inverse: bool = False):
@@ -373,7 +386,8 @@ def attn_fwd_generic(qkv: Tensor, key_mask: Optional[Tensor], B: int, S: int, nh
         call("cm3p_attn_fwd_generic_dropout", ptr(qkv, torch.bfloat16), ptr(out), ptr(lse, torch.float32), ptr(key_mask, torch.uint8), B, S, nh, hd,
              window, scale, layer, thr, seed, stream())
         return out, lse
-    call("cm3p_attn_fwd_generic", ptr(qkv, torch.bfloat16), ptr(out), ptr(lse, torch.float32), ptr(key_mask, torch.uint8), B, S, nh, hd, window, scale, stream())
+    call("cm3p_attn_fwd_generic", ptr(qkv, torch.bfloat16), ptr(out), ptr(lse, torch.float32), ptr(key_mask, torch.uint8), B, S, nh, hd, window, scale, stream(),
+         **_attn_hd_prof(("attn_hd_fwd_kernel",), 2, B, S, nh, hd, window))
     return out, lse
 
 
@@ -388,7 +402,8 @@ def attn_bwd_generic(qkv: Tensor, out: Tensor, dout: Tensor, lse: Tensor, key_ma
              ptr(delta), ptr(dqkv), ptr(key_mask, torch.uint8), B, S, nh, hd, window, scale, layer, thr, seed, stream())
         return dqkv
     call("cm3p_attn_bwd_generic", ptr(qkv, torch.bfloat16), ptr(out, torch.bfloat16), ptr(dout, torch.bfloat16), ptr(lse, torch.float32), ptr(delta), ptr(dqkv),
-         ptr(key_mask, torch.uint8), B, S, nh, hd, window, scale, stream())
+         ptr(key_mask, torch.uint8), B, S, nh, hd, window, scale, stream(),
+         **_attn_hd_prof(("attn_hd_dq_kernel", "attn_hd_dkv_kernel"), 4, B, S, nh, hd, window))  # one call, two kernels; attn_bwd's count: 2 x forward
     return dqkv
 
 

@@ -253,7 +253,10 @@ int cm3p_attn_bwd(const void* qkv, const void* out, const void* dout, const floa
  * test configuration (hidden 64, 4 heads; BASELINE.json configs[0]); the default towers are all head_dim 64 and never come here.  q is
  * plain (no pre-scaling), dqkv's q / k thirds are gradients w.r.t. the ROTATED q / k: cm3p_rope_apply_generic(..., inverse = 1) on dqkv
  * completes the backward of apply_rotary_pos_emb (TF:models/modernbert/modeling_modernbert.py:188-219), whose forward it also is
- * (in place on the q and k thirds of a packed qkv; cos / sin [n_pos, head_dim / 2] from cm3p_rope_table). */
+ * (in place on the q and k thirds of a packed qkv; cos / sin [n_pos, head_dim / 2] from cm3p_rope_table).
+ * head_dim 96 and 128 (a 768- / 1024-wide tower with 8 heads) enter through the same two entries with the same contract and run on
+ * matrix-core kernels (csrc/attention_hd.hip: v_mfma_f32_32x32x16_bf16, fixed summation order, no workspace);
+ * cm3p_attn_generic_supported returns 1 for 16, 32, 64, 96 and 128 and 0 for every other size. */
 int cm3p_attn_generic_supported(int head_dim);
 int cm3p_attn_fwd_generic(const void* qkv, void* out, float* lse, const uint8_t* key_mask, int B, int S, int nh, int head_dim, int window,
                           float scale, void* stream);
@@ -261,7 +264,7 @@ int cm3p_attn_bwd_generic(const void* qkv, const void* out, const void* dout, co
                           const uint8_t* key_mask, int B, int S, int nh, int head_dim, int window, float scale, void* stream);
 /* Attention-probability dropout on the generic kernels (TF:models/modernbert/modeling_modernbert.py:181 eager, :292 sdpa dropout_p): the
  * rule and the decisions of cm3p_attn_fwd_dropout / cm3p_attn_bwd_dropout (dropout contract below, site 1), arguments as the two entries
- * above plus layer, thr, seed. */
+ * above plus layer, thr, seed.  head_dim 96 / 128 have no dropout form: CM3P_ERR_INVALID. */
 int cm3p_attn_fwd_generic_dropout(const void* qkv, void* out, float* lse, const uint8_t* key_mask, int B, int S, int nh, int head_dim,
                                   int window, float scale, int layer, int thr, uint64_t seed, void* stream);
 int cm3p_attn_bwd_generic_dropout(const void* qkv, const void* out, const void* dout, const float* lse, float* delta, void* dqkv,
