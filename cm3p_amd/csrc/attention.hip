@@ -101,19 +101,13 @@ constexpr int kFwdStage = 8192 + 8192 + 64 + 16;  // K image R, V image T, mask 
 // shows up as its own row in a profile.
 // Drop = {cm3p_drop::DropCfg}: attention-probability dropout (dropout_rng.h, site 1): l sums the undropped p, PV takes p o keep,
 // 1 / (1 - p) joins 1 / l at the store; lse is unchanged.  Drop = {} (every instance without dropout) compiles to the kernel without it:
-// same signature, same code.
-template <typename... T>
-__device__ __forceinline__ cm3p_drop::DropCfg drop_cfg(T... t) {
-    if constexpr (sizeof...(T) > 0) return (t, ...);
-    else return cm3p_drop::DropCfg{};
-}
-
+// same signature, same code (cm3p_drop::drop_cfg).
 template <int QSUB, bool PRE, bool BAND, typename... Drop>
 __global__ __launch_bounds__(256, QSUB == 1 ? 2 : 1) void attn_fwd_kernel(const uint16_t* __restrict__ qkv, uint16_t* __restrict__ out,
                                                                         float* __restrict__ lse, const uint8_t* __restrict__ kmask,
                                                                         int Smax, int nh, int window_arg, float scale, VarLen vl, Drop... drop) {
     constexpr bool DROP = sizeof...(Drop) > 0;
-    const cm3p_drop::DropCfg dc = drop_cfg(drop...);
+    const cm3p_drop::DropCfg dc = cm3p_drop::drop_cfg(drop...);
     const int window = BAND ? window_arg : -1;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int QW = 32 * QSUB;  // queries per wave
@@ -502,35 +496,21 @@ __device__ __forceinline__ void band_dq_block(char* smem, int qblk, int head, in
     BAND_T(15);
 }
 
-template <bool PRE, bool MASK>
+// Drop = {cm3p_drop::DropCfg} | {}: as in the forward
+template <bool PRE, bool MASK, typename... Drop>
 __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(const uint16_t* __restrict__ qkv, const uint16_t* __restrict__ d_o,
                                                              const uint16_t* __restrict__ o_rows, const float* __restrict__ lse,
                                                              float* __restrict__ delta,
                                                              uint16_t* __restrict__ dqkv, const uint8_t* __restrict__ kmask,
                                                              int Smax, int nh, int window, float scale,
                                                              const float* __restrict__ rope_cos,
-                                                             const float* __restrict__ rope_sin, int64_t pos_batch_stride, VarLen vl) {
+                                                             const float* __restrict__ rope_sin, int64_t pos_batch_stride, VarLen vl, Drop... drop) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     int qblk, head, b;
     if (window >= 0) decode_block_band((Smax + 127) / 128, nh, qblk, head, b);
     else decode_block((Smax + 127) / 128, nh, qblk, head, b);
-    band_dq_block<PRE, MASK>(smem, qblk, head, b, qkv, d_o, o_rows, lse, delta, dqkv, kmask, Smax, nh, window, scale, rope_cos, rope_sin,
-                                    pos_batch_stride, vl);
-}
-
-template <bool PRE, bool MASK>
-__global__ __launch_bounds__(256, 2) void attn_bwd_dq_drop_kernel(const uint16_t* __restrict__ qkv, const uint16_t* __restrict__ d_o,
-                                                                  const uint16_t* __restrict__ o_rows, const float* __restrict__ lse,
-                                                                  float* __restrict__ delta, uint16_t* __restrict__ dqkv,
-                                                                  const uint8_t* __restrict__ kmask, int Smax, int nh, int window, float scale,
-                                                                  const float* __restrict__ rope_cos, const float* __restrict__ rope_sin,
-                                                                  int64_t pos_batch_stride, VarLen vl, cm3p_drop::DropCfg dc) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    int qblk, head, b;
-    if (window >= 0) decode_block_band((Smax + 127) / 128, nh, qblk, head, b);
-    else decode_block((Smax + 127) / 128, nh, qblk, head, b);
-    band_dq_block<PRE, MASK, true>(smem, qblk, head, b, qkv, d_o, o_rows, lse, delta, dqkv, kmask, Smax, nh, window, scale, rope_cos, rope_sin,
-                                   pos_batch_stride, vl, dc);
+    band_dq_block<PRE, MASK, (sizeof...(Drop) > 0)>(smem, qblk, head, b, qkv, d_o, o_rows, lse, delta, dqkv, kmask, Smax, nh, window, scale, rope_cos,
+                                                    rope_sin, pos_batch_stride, vl, cm3p_drop::drop_cfg(drop...));
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -733,35 +713,20 @@ __device__ __forceinline__ void band_dkv_block(char* smem, int kblk, int head, i
     }
 }
 
-template <bool PRE>
+template <bool PRE, typename... Drop>
 __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(const uint16_t* __restrict__ qkv, const uint16_t* __restrict__ d_o,
                                                               const float* __restrict__ lse, const float* __restrict__ delta,
                                                               uint16_t* __restrict__ dqkv, const uint8_t* __restrict__ kmask,
                                                               int Smax, int nh, int window, float scale,
                                                               const float* __restrict__ rope_cos,
-                                                              const float* __restrict__ rope_sin, int64_t pos_batch_stride, VarLen vl) {
+                                                              const float* __restrict__ rope_sin, int64_t pos_batch_stride, VarLen vl, Drop... drop) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     int kblk, head, b;
     if (window >= 0) decode_block_band((Smax + 127) / 128, nh, kblk, head, b);
     else decode_block((Smax + 127) / 128, nh, kblk, head, b);
-    band_dkv_block<PRE>(smem, kblk, head, b, qkv, d_o, lse, delta, dqkv, kmask, Smax, nh, window, scale, rope_cos, rope_sin, pos_batch_stride, vl);
+    band_dkv_block<PRE, (sizeof...(Drop) > 0)>(smem, kblk, head, b, qkv, d_o, lse, delta, dqkv, kmask, Smax, nh, window, scale, rope_cos, rope_sin,
+                                               pos_batch_stride, vl, cm3p_drop::drop_cfg(drop...));
 }
-
-template <bool PRE>
-__global__ __launch_bounds__(256, 2) void attn_bwd_dkv_drop_kernel(const uint16_t* __restrict__ qkv, const uint16_t* __restrict__ d_o,
-                                                                   const float* __restrict__ lse, const float* __restrict__ delta,
-                                                                   uint16_t* __restrict__ dqkv, const uint8_t* __restrict__ kmask, int Smax, int nh,
-                                                                   int window, float scale, const float* __restrict__ rope_cos,
-                                                                   const float* __restrict__ rope_sin, int64_t pos_batch_stride, VarLen vl,
-                                                                   cm3p_drop::DropCfg dc) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    int kblk, head, b;
-    if (window >= 0) decode_block_band((Smax + 127) / 128, nh, kblk, head, b);
-    else decode_block((Smax + 127) / 128, nh, kblk, head, b);
-    band_dkv_block<PRE, true>(smem, kblk, head, b, qkv, d_o, lse, delta, dqkv, kmask, Smax, nh, window, scale, rope_cos, rope_sin, pos_batch_stride,
-                              vl, dc);
-}
-
 
 // ---------------------------------------------------------------------------------------------------------------
 // output_attentions: the probabilities themselves, [B, nh, S, S] fp32 - what the reference returns when a caller asks for
@@ -825,110 +790,87 @@ static bool fwd_takes_pipelined(int S, int nh, int window, int pre) {
     return window < 0 && pre && (int64_t)S * 3 * nh * 128 < (int64_t(1) << 31);
 }
 
+// One launcher per kernel family.  Drop = {} or {cm3p_drop::DropCfg}: the kernels' trailing pack.  Attention-probability dropout runs
+// the band kernels at every window (global layers at window -1), never the pipelined forward.
+template <typename... Drop>
 static int launch_attn_fwd(const void* qkv, void* out, float* lse, const uint8_t* key_mask, int B, int S, int nh, int window,
-                           float scale, VarLen vl, int pre, hipStream_t s) {
-    if (fwd_takes_pipelined(S, nh, window, pre))
-        return cm3p_launch_attn_fwd_global(qkv, out, lse, key_mask, B, S, nh, vl.cu, vl.total, s);
+                           float scale, VarLen vl, int pre, hipStream_t s, Drop... drop) {
+    if constexpr (sizeof...(Drop) == 0) {
+        if (fwd_takes_pipelined(S, nh, window, pre))
+            return cm3p_launch_attn_fwd_global(qkv, out, lse, key_mask, B, S, nh, vl.cu, vl.total, s);
+    }
     // QSUB = 1 (32 queries per wave, 3 waves per SIMD) measured faster than QSUB = 2 (64 per wave, compiler-scheduled):
     // 2.29 ms vs 3.49 ms per C2 global layer.  The two-chain variant needs a hand-placed MFMA/VALU interleave to pay.
     const dim3 grid(((S + 127) / 128) * nh * B);  // 1-D: decode_block() maps it XCD-aware
-#define CM3P_FWD_ARGS (const uint16_t*)qkv, (uint16_t*)out, lse, key_mask, S, nh, window, scale, vl
+#define CM3P_FWD_ARGS (const uint16_t*)qkv, (uint16_t*)out, lse, key_mask, S, nh, window, scale, vl, drop...
     if (window >= 0) {
-        if (pre) attn_fwd_kernel<1, true, true><<<grid, 256, 2 * kFwdStage, s>>>(CM3P_FWD_ARGS);
-        else attn_fwd_kernel<1, false, true><<<grid, 256, 2 * kFwdStage, s>>>(CM3P_FWD_ARGS);
+        if (pre) attn_fwd_kernel<1, true, true, Drop...><<<grid, 256, 2 * kFwdStage, s>>>(CM3P_FWD_ARGS);
+        else attn_fwd_kernel<1, false, true, Drop...><<<grid, 256, 2 * kFwdStage, s>>>(CM3P_FWD_ARGS);
     } else {
-        if (pre) attn_fwd_kernel<1, true, false><<<grid, 256, 2 * kFwdStage, s>>>(CM3P_FWD_ARGS);
-        else attn_fwd_kernel<1, false, false><<<grid, 256, 2 * kFwdStage, s>>>(CM3P_FWD_ARGS);
+        if (pre) attn_fwd_kernel<1, true, false, Drop...><<<grid, 256, 2 * kFwdStage, s>>>(CM3P_FWD_ARGS);
+        else attn_fwd_kernel<1, false, false, Drop...><<<grid, 256, 2 * kFwdStage, s>>>(CM3P_FWD_ARGS);
     }
 #undef CM3P_FWD_ARGS
-    return CM3P_OK;
-}
-
-// attention-probability dropout: the band kernels at every window (global layers at window -1), never the pipelined forward
-static int launch_attn_fwd_drop(const void* qkv, void* out, float* lse, const uint8_t* key_mask, int B, int S, int nh, int window,
-                                float scale, VarLen vl, int pre, const cm3p_drop::DropCfg& dc, hipStream_t s) {
-    const dim3 grid(((S + 127) / 128) * nh * B);
-#define CM3P_FWD_ARGS (const uint16_t*)qkv, (uint16_t*)out, lse, key_mask, S, nh, window, scale, vl, dc
-    if (window >= 0) {
-        if (pre) attn_fwd_kernel<1, true, true, cm3p_drop::DropCfg><<<grid, 256, 2 * kFwdStage, s>>>(CM3P_FWD_ARGS);
-        else attn_fwd_kernel<1, false, true, cm3p_drop::DropCfg><<<grid, 256, 2 * kFwdStage, s>>>(CM3P_FWD_ARGS);
-    } else {
-        if (pre) attn_fwd_kernel<1, true, false, cm3p_drop::DropCfg><<<grid, 256, 2 * kFwdStage, s>>>(CM3P_FWD_ARGS);
-        else attn_fwd_kernel<1, false, false, cm3p_drop::DropCfg><<<grid, 256, 2 * kFwdStage, s>>>(CM3P_FWD_ARGS);
-    }
-#undef CM3P_FWD_ARGS
-    return CM3P_OK;
-}
-
-static int launch_attn_bwd_drop(const void* qkv, const void* out, const void* dout, const float* lse, float* delta, void* dqkv,
-                                const uint8_t* key_mask, int B, int S, int nh, int window, float scale, const float* cos_tab,
-                                const float* sin_tab, int64_t pos_batch_stride, VarLen vl, int stages, int pre, const cm3p_drop::DropCfg& dc,
-                                hipStream_t s) {
-    const dim3 grid(((S + 127) / 128) * nh * B);
-    if (stages & CM3P_ATTN_BWD_DQ) {
-#define CM3P_DQ_ARGS (const uint16_t*)qkv, (const uint16_t*)dout, (const uint16_t*)out, lse, delta, (uint16_t*)dqkv, key_mask, S, nh, window, scale, cos_tab, sin_tab, pos_batch_stride, vl, dc
-        static Cm3pDevOnce once;
-        const int rc_once = once.run([] {
-            return cm3p_set_max_lds({reinterpret_cast<const void*>(&attn_bwd_dq_drop_kernel<true, true>), reinterpret_cast<const void*>(&attn_bwd_dq_drop_kernel<true, false>),
-                                     reinterpret_cast<const void*>(&attn_bwd_dq_drop_kernel<false, true>), reinterpret_cast<const void*>(&attn_bwd_dq_drop_kernel<false, false>)},
-                                    kDqSlots * kDqStage);
-        });
-        if (rc_once != CM3P_OK) return rc_once;
-        if (pre && key_mask) attn_bwd_dq_drop_kernel<true, true><<<grid, 256, kDqSlots * kDqStage, s>>>(CM3P_DQ_ARGS);
-        else if (pre) attn_bwd_dq_drop_kernel<true, false><<<grid, 256, kDqSlots * kDqStage, s>>>(CM3P_DQ_ARGS);
-        else if (key_mask) attn_bwd_dq_drop_kernel<false, true><<<grid, 256, kDqSlots * kDqStage, s>>>(CM3P_DQ_ARGS);
-        else attn_bwd_dq_drop_kernel<false, false><<<grid, 256, kDqSlots * kDqStage, s>>>(CM3P_DQ_ARGS);
-#undef CM3P_DQ_ARGS
-        if (hipGetLastError() != hipSuccess) return CM3P_ERR_LAUNCH;
-    }
-    if (stages & CM3P_ATTN_BWD_DKV) {
-#define CM3P_DKV_ARGS (const uint16_t*)qkv, (const uint16_t*)dout, lse, delta, (uint16_t*)dqkv, key_mask, S, nh, window, scale, cos_tab, sin_tab, pos_batch_stride, vl, dc
-        static Cm3pDevOnce once2;
-        const int rc_once = once2.run([] {
-            return cm3p_set_max_lds({reinterpret_cast<const void*>(&attn_bwd_dkv_drop_kernel<true>), reinterpret_cast<const void*>(&attn_bwd_dkv_drop_kernel<false>)},
-                                    kDkvSlots * kDkvStage);
-        });
-        if (rc_once != CM3P_OK) return rc_once;
-        if (pre) attn_bwd_dkv_drop_kernel<true><<<grid, 256, kDkvSlots * kDkvStage, s>>>(CM3P_DKV_ARGS);
-        else attn_bwd_dkv_drop_kernel<false><<<grid, 256, kDkvSlots * kDkvStage, s>>>(CM3P_DKV_ARGS);
-#undef CM3P_DKV_ARGS
-    }
     return CM3P_OK;
 }
 
 // stages: CM3P_ATTN_BWD_DQ (dq and delta) | CM3P_ATTN_BWD_DKV (dk, dv; reads the delta the dq stage wrote)
+template <typename... Drop>
 static int launch_attn_bwd(const void* qkv, const void* out, const void* dout, const float* lse, float* delta, void* dqkv,
                            const uint8_t* key_mask, int B, int S, int nh, int window, float scale, const float* cos_tab,
-                           const float* sin_tab, int64_t pos_batch_stride, VarLen vl, int stages, int pre, hipStream_t s) {
+                           const float* sin_tab, int64_t pos_batch_stride, VarLen vl, int stages, int pre, hipStream_t s, Drop... drop) {
     const dim3 grid(((S + 127) / 128) * nh * B);  // 1-D: decode_block() maps it XCD-aware
     if (stages & CM3P_ATTN_BWD_DQ) {
-#define CM3P_DQ_ARGS (const uint16_t*)qkv, (const uint16_t*)dout, (const uint16_t*)out, lse, delta, (uint16_t*)dqkv, key_mask, S, nh, window, scale, cos_tab, sin_tab, pos_batch_stride, vl
-        static Cm3pDevOnce once;  // (per device: common.h)
+#define CM3P_DQ_ARGS (const uint16_t*)qkv, (const uint16_t*)dout, (const uint16_t*)out, lse, delta, (uint16_t*)dqkv, key_mask, S, nh, window, scale, cos_tab, sin_tab, pos_batch_stride, vl, drop...
+        static Cm3pDevOnce once;  // (per device: common.h; one per instantiation, as the kernels it prepares are)
         const int rc_once = once.run([] {
-            return cm3p_set_max_lds({reinterpret_cast<const void*>(&attn_bwd_dq_kernel<true, true>), reinterpret_cast<const void*>(&attn_bwd_dq_kernel<true, false>),
-                                     reinterpret_cast<const void*>(&attn_bwd_dq_kernel<false, true>), reinterpret_cast<const void*>(&attn_bwd_dq_kernel<false, false>)},
+            return cm3p_set_max_lds({reinterpret_cast<const void*>(&attn_bwd_dq_kernel<true, true, Drop...>), reinterpret_cast<const void*>(&attn_bwd_dq_kernel<true, false, Drop...>),
+                                     reinterpret_cast<const void*>(&attn_bwd_dq_kernel<false, true, Drop...>), reinterpret_cast<const void*>(&attn_bwd_dq_kernel<false, false, Drop...>)},
                                     kDqSlots * kDqStage);
         });
         if (rc_once != CM3P_OK) return rc_once;
-        if (pre && key_mask) attn_bwd_dq_kernel<true, true><<<grid, 256, kDqSlots * kDqStage, s>>>(CM3P_DQ_ARGS);
-        else if (pre) attn_bwd_dq_kernel<true, false><<<grid, 256, kDqSlots * kDqStage, s>>>(CM3P_DQ_ARGS);
-        else if (key_mask) attn_bwd_dq_kernel<false, true><<<grid, 256, kDqSlots * kDqStage, s>>>(CM3P_DQ_ARGS);
-        else attn_bwd_dq_kernel<false, false><<<grid, 256, kDqSlots * kDqStage, s>>>(CM3P_DQ_ARGS);
+        if (pre && key_mask) attn_bwd_dq_kernel<true, true, Drop...><<<grid, 256, kDqSlots * kDqStage, s>>>(CM3P_DQ_ARGS);
+        else if (pre) attn_bwd_dq_kernel<true, false, Drop...><<<grid, 256, kDqSlots * kDqStage, s>>>(CM3P_DQ_ARGS);
+        else if (key_mask) attn_bwd_dq_kernel<false, true, Drop...><<<grid, 256, kDqSlots * kDqStage, s>>>(CM3P_DQ_ARGS);
+        else attn_bwd_dq_kernel<false, false, Drop...><<<grid, 256, kDqSlots * kDqStage, s>>>(CM3P_DQ_ARGS);
 #undef CM3P_DQ_ARGS
         if (hipGetLastError() != hipSuccess) return CM3P_ERR_LAUNCH;
     }
     if (stages & CM3P_ATTN_BWD_DKV) {
-#define CM3P_DKV_ARGS (const uint16_t*)qkv, (const uint16_t*)dout, lse, delta, (uint16_t*)dqkv, key_mask, S, nh, window, scale, cos_tab, sin_tab, pos_batch_stride, vl
+#define CM3P_DKV_ARGS (const uint16_t*)qkv, (const uint16_t*)dout, lse, delta, (uint16_t*)dqkv, key_mask, S, nh, window, scale, cos_tab, sin_tab, pos_batch_stride, vl, drop...
         static Cm3pDevOnce once2;
         const int rc_once = once2.run([] {
-            return cm3p_set_max_lds({reinterpret_cast<const void*>(&attn_bwd_dkv_kernel<true>), reinterpret_cast<const void*>(&attn_bwd_dkv_kernel<false>)},
+            return cm3p_set_max_lds({reinterpret_cast<const void*>(&attn_bwd_dkv_kernel<true, Drop...>), reinterpret_cast<const void*>(&attn_bwd_dkv_kernel<false, Drop...>)},
                                     kDkvSlots * kDkvStage);
         });
         if (rc_once != CM3P_OK) return rc_once;
-        if (pre) attn_bwd_dkv_kernel<true><<<grid, 256, kDkvSlots * kDkvStage, s>>>(CM3P_DKV_ARGS);
-        else attn_bwd_dkv_kernel<false><<<grid, 256, kDkvSlots * kDkvStage, s>>>(CM3P_DKV_ARGS);
+        if (pre) attn_bwd_dkv_kernel<true, Drop...><<<grid, 256, kDkvSlots * kDkvStage, s>>>(CM3P_DKV_ARGS);
+        else attn_bwd_dkv_kernel<false, Drop...><<<grid, 256, kDkvSlots * kDkvStage, s>>>(CM3P_DKV_ARGS);
 #undef CM3P_DKV_ARGS
     }
+    return CM3P_OK;
+}
+
+// What the eight launching entry points require of their arguments.  S: the sequence length (max_seqlen of the packed forms);
+// packed: the _varlen forms hand in their VarLen, whose cu_seqlens and positive row total are required then.
+static bool attn_fwd_args_ok(const void* qkv, const void* out, const float* lse, int B, int S, int nh, float scale, const VarLen* packed) {
+    return qkv && out && lse && B > 0 && S > 0 && nh > 0 && scale > 0.f && (!packed || (packed->cu && packed->total > 0)) && cm3p_aligned16(qkv) &&
+           cm3p_aligned16(out);
+}
+
+// pos_batch_stride: 0 or S (the packed forms have no such argument and pass 0)
+static bool attn_bwd_args_ok(const void* qkv, const void* out, const void* dout, const float* lse, const float* delta, const void* dqkv, int B, int S,
+                             int nh, float scale, const float* cos_tab, const float* sin_tab, int64_t pos_batch_stride, int stages,
+                             const VarLen* packed) {
+    return attn_fwd_args_ok(qkv, out, lse, B, S, nh, scale, packed) && dout && delta && dqkv && cm3p_aligned16(dout) && cm3p_aligned16(dqkv) &&
+           (cos_tab == nullptr) == (sin_tab == nullptr) && stages >= 1 && stages <= 3 && (pos_batch_stride == 0 || pos_batch_stride == S) &&
+           (int64_t)S * 3 * nh * 128 < (int64_t(1) << 31);  // TileDma::rows: 32-bit row * pitch source offsets (attn_common.h)
+}
+
+// a launcher's return code, or what the launch itself left behind
+static int attn_launched(int rc) {
+    if (rc != CM3P_OK) return rc;
+    CM3P_LAUNCH_CHECK();
     return CM3P_OK;
 }
 
@@ -936,13 +878,9 @@ extern "C" {
 
 int cm3p_attn_fwd(const void* qkv, void* out, float* lse, const uint8_t* key_mask, int B, int S, int nh, int window,
                   float scale, int q_prescaled, void* stream) {
-    CM3P_REQUIRE(qkv && out && lse && B > 0 && S > 0 && nh > 0 && scale > 0.f);
-    CM3P_REQUIRE(cm3p_aligned16(qkv) && cm3p_aligned16(out));
-    const int rc = launch_attn_fwd(qkv, out, lse, key_mask, B, S, nh, window, scale, VarLen{nullptr, 0}, q_prescaled != 0,
-                                   static_cast<hipStream_t>(stream));
-    if (rc != CM3P_OK) return rc;
-    CM3P_LAUNCH_CHECK();
-    return CM3P_OK;
+    CM3P_REQUIRE(attn_fwd_args_ok(qkv, out, lse, B, S, nh, scale, nullptr));
+    return attn_launched(launch_attn_fwd(qkv, out, lse, key_mask, B, S, nh, window, scale, VarLen{nullptr, 0}, q_prescaled != 0,
+                                         static_cast<hipStream_t>(stream)));
 }
 
 int cm3p_attn_fwd_impl(int S, int nh, int window, int q_prescaled) { return fwd_takes_pipelined(S, nh, window, q_prescaled != 0) ? 1 : 0; }
@@ -950,108 +888,64 @@ int cm3p_attn_fwd_impl(int S, int nh, int window, int q_prescaled) { return fwd_
 int cm3p_attn_bwd(const void* qkv, const void* out, const void* dout, const float* lse, float* delta, void* dqkv,
                   const uint8_t* key_mask, int B, int S, int nh, int window, float scale, const float* cos_tab,
                   const float* sin_tab, int64_t pos_batch_stride, int stages, int q_prescaled, void* stream) {
-    CM3P_REQUIRE((cos_tab == nullptr) == (sin_tab == nullptr));
-    CM3P_REQUIRE(stages >= 1 && stages <= 3);
-    CM3P_REQUIRE(pos_batch_stride == 0 || pos_batch_stride == S);
-    CM3P_REQUIRE(qkv && out && dout && lse && delta && dqkv && B > 0 && S > 0 && nh > 0 && scale > 0.f);
-    CM3P_REQUIRE(cm3p_aligned16(qkv) && cm3p_aligned16(out) && cm3p_aligned16(dout) && cm3p_aligned16(dqkv));
-    CM3P_REQUIRE((int64_t)S * 3 * nh * 128 < (int64_t(1) << 31));  // TileDma::rows: 32-bit row * pitch source offsets (attn_common.h)
-    const int rc = launch_attn_bwd(qkv, out, dout, lse, delta, dqkv, key_mask, B, S, nh, window, scale, cos_tab, sin_tab,
-                                   pos_batch_stride, VarLen{nullptr, 0}, stages, q_prescaled != 0, static_cast<hipStream_t>(stream));
-    if (rc != CM3P_OK) return rc;
-    CM3P_LAUNCH_CHECK();
-    return CM3P_OK;
+    CM3P_REQUIRE(attn_bwd_args_ok(qkv, out, dout, lse, delta, dqkv, B, S, nh, scale, cos_tab, sin_tab, pos_batch_stride, stages, nullptr));
+    return attn_launched(launch_attn_bwd(qkv, out, dout, lse, delta, dqkv, key_mask, B, S, nh, window, scale, cos_tab, sin_tab, pos_batch_stride,
+                                         VarLen{nullptr, 0}, stages, q_prescaled != 0, static_cast<hipStream_t>(stream)));
 }
 
 int cm3p_attn_fwd_varlen(const void* qkv, void* out, float* lse, const int* cu_seqlens, int B, int max_seqlen, int64_t total,
                          int nh, int window, float scale, int q_prescaled, void* stream) {
-    CM3P_REQUIRE(qkv && out && lse && cu_seqlens && B > 0 && max_seqlen > 0 && total > 0 && nh > 0 && scale > 0.f);
-    CM3P_REQUIRE(cm3p_aligned16(qkv) && cm3p_aligned16(out));
-    const int rc = launch_attn_fwd(qkv, out, lse, nullptr, B, max_seqlen, nh, window, scale, VarLen{cu_seqlens, total}, q_prescaled != 0,
-                                   static_cast<hipStream_t>(stream));
-    if (rc != CM3P_OK) return rc;
-    CM3P_LAUNCH_CHECK();
-    return CM3P_OK;
+    const VarLen vl{cu_seqlens, total};
+    CM3P_REQUIRE(attn_fwd_args_ok(qkv, out, lse, B, max_seqlen, nh, scale, &vl));
+    return attn_launched(launch_attn_fwd(qkv, out, lse, nullptr, B, max_seqlen, nh, window, scale, vl, q_prescaled != 0, static_cast<hipStream_t>(stream)));
 }
 
 int cm3p_attn_bwd_varlen(const void* qkv, const void* out, const void* dout, const float* lse, float* delta, void* dqkv,
                          const int* cu_seqlens, int B, int max_seqlen, int64_t total, int nh, int window, float scale,
                          const float* cos_tab, const float* sin_tab, int stages, int q_prescaled, void* stream) {
-    CM3P_REQUIRE((cos_tab == nullptr) == (sin_tab == nullptr));
-    CM3P_REQUIRE(stages >= 1 && stages <= 3);
-    CM3P_REQUIRE(qkv && out && dout && lse && delta && dqkv && cu_seqlens && B > 0 && max_seqlen > 0 && total > 0 && nh > 0 && scale > 0.f);
-    CM3P_REQUIRE(cm3p_aligned16(qkv) && cm3p_aligned16(out) && cm3p_aligned16(dout) && cm3p_aligned16(dqkv));
-    CM3P_REQUIRE((int64_t)max_seqlen * 3 * nh * 128 < (int64_t(1) << 31));  // TileDma::rows: 32-bit row * pitch source offsets
-    const int rc = launch_attn_bwd(qkv, out, dout, lse, delta, dqkv, nullptr, B, max_seqlen, nh, window, scale, cos_tab, sin_tab, 0,
-                                   VarLen{cu_seqlens, total}, stages, q_prescaled != 0, static_cast<hipStream_t>(stream));
-    if (rc != CM3P_OK) return rc;
-    CM3P_LAUNCH_CHECK();
-    return CM3P_OK;
+    const VarLen vl{cu_seqlens, total};
+    CM3P_REQUIRE(attn_bwd_args_ok(qkv, out, dout, lse, delta, dqkv, B, max_seqlen, nh, scale, cos_tab, sin_tab, 0, stages, &vl));
+    return attn_launched(launch_attn_bwd(qkv, out, dout, lse, delta, dqkv, nullptr, B, max_seqlen, nh, window, scale, cos_tab, sin_tab, 0, vl, stages,
+                                         q_prescaled != 0, static_cast<hipStream_t>(stream)));
 }
-
-#define CM3P_ATTN_DROP_REQUIRE() CM3P_REQUIRE(thr >= 0 && thr <= 65536 && layer >= 0 && layer < (1 << 29))
 
 int cm3p_attn_fwd_dropout(const void* qkv, void* out, float* lse, const uint8_t* key_mask, int B, int S, int nh, int window, float scale,
                           int q_prescaled, int layer, int thr, uint64_t seed, void* stream) {
-    CM3P_REQUIRE(qkv && out && lse && B > 0 && S > 0 && nh > 0 && scale > 0.f);
-    CM3P_REQUIRE(cm3p_aligned16(qkv) && cm3p_aligned16(out));
-    CM3P_ATTN_DROP_REQUIRE();
-    const int rc = launch_attn_fwd_drop(qkv, out, lse, key_mask, B, S, nh, window, scale, VarLen{nullptr, 0}, q_prescaled != 0,
-                                        cm3p_drop::make_cfg(layer, cm3p_drop::kSiteAttnProbs, thr, seed), static_cast<hipStream_t>(stream));
-    if (rc != CM3P_OK) return rc;
-    CM3P_LAUNCH_CHECK();
-    return CM3P_OK;
+    CM3P_REQUIRE(attn_fwd_args_ok(qkv, out, lse, B, S, nh, scale, nullptr) && cm3p_drop::cfg_args_ok(layer, thr));
+    return attn_launched(launch_attn_fwd(qkv, out, lse, key_mask, B, S, nh, window, scale, VarLen{nullptr, 0}, q_prescaled != 0,
+                                         static_cast<hipStream_t>(stream), cm3p_drop::make_cfg(layer, cm3p_drop::kSiteAttnProbs, thr, seed)));
 }
 
 int cm3p_attn_bwd_dropout(const void* qkv, const void* out, const void* dout, const float* lse, float* delta, void* dqkv,
                           const uint8_t* key_mask, int B, int S, int nh, int window, float scale, const float* cos_tab,
                           const float* sin_tab, int64_t pos_batch_stride, int stages, int q_prescaled, int layer, int thr, uint64_t seed,
                           void* stream) {
-    CM3P_REQUIRE((cos_tab == nullptr) == (sin_tab == nullptr));
-    CM3P_REQUIRE(stages >= 1 && stages <= 3);
-    CM3P_REQUIRE(pos_batch_stride == 0 || pos_batch_stride == S);
-    CM3P_REQUIRE(qkv && out && dout && lse && delta && dqkv && B > 0 && S > 0 && nh > 0 && scale > 0.f);
-    CM3P_REQUIRE(cm3p_aligned16(qkv) && cm3p_aligned16(out) && cm3p_aligned16(dout) && cm3p_aligned16(dqkv));
-    CM3P_REQUIRE((int64_t)S * 3 * nh * 128 < (int64_t(1) << 31));
-    CM3P_ATTN_DROP_REQUIRE();
-    const int rc = launch_attn_bwd_drop(qkv, out, dout, lse, delta, dqkv, key_mask, B, S, nh, window, scale, cos_tab, sin_tab, pos_batch_stride,
-                                        VarLen{nullptr, 0}, stages, q_prescaled != 0, cm3p_drop::make_cfg(layer, cm3p_drop::kSiteAttnProbs, thr, seed),
-                                        static_cast<hipStream_t>(stream));
-    if (rc != CM3P_OK) return rc;
-    CM3P_LAUNCH_CHECK();
-    return CM3P_OK;
+    CM3P_REQUIRE(attn_bwd_args_ok(qkv, out, dout, lse, delta, dqkv, B, S, nh, scale, cos_tab, sin_tab, pos_batch_stride, stages, nullptr) &&
+                 cm3p_drop::cfg_args_ok(layer, thr));
+    return attn_launched(launch_attn_bwd(qkv, out, dout, lse, delta, dqkv, key_mask, B, S, nh, window, scale, cos_tab, sin_tab, pos_batch_stride,
+                                         VarLen{nullptr, 0}, stages, q_prescaled != 0, static_cast<hipStream_t>(stream),
+                                         cm3p_drop::make_cfg(layer, cm3p_drop::kSiteAttnProbs, thr, seed)));
 }
 
 int cm3p_attn_fwd_dropout_varlen(const void* qkv, void* out, float* lse, const int* cu_seqlens, int B, int max_seqlen, int64_t total, int nh,
                                  int window, float scale, int q_prescaled, int layer, int thr, uint64_t seed, void* stream) {
-    CM3P_REQUIRE(qkv && out && lse && cu_seqlens && B > 0 && max_seqlen > 0 && total > 0 && nh > 0 && scale > 0.f);
-    CM3P_REQUIRE(cm3p_aligned16(qkv) && cm3p_aligned16(out));
-    CM3P_ATTN_DROP_REQUIRE();
-    const int rc = launch_attn_fwd_drop(qkv, out, lse, nullptr, B, max_seqlen, nh, window, scale, VarLen{cu_seqlens, total}, q_prescaled != 0,
-                                        cm3p_drop::make_cfg(layer, cm3p_drop::kSiteAttnProbs, thr, seed), static_cast<hipStream_t>(stream));
-    if (rc != CM3P_OK) return rc;
-    CM3P_LAUNCH_CHECK();
-    return CM3P_OK;
+    const VarLen vl{cu_seqlens, total};
+    CM3P_REQUIRE(attn_fwd_args_ok(qkv, out, lse, B, max_seqlen, nh, scale, &vl) && cm3p_drop::cfg_args_ok(layer, thr));
+    return attn_launched(launch_attn_fwd(qkv, out, lse, nullptr, B, max_seqlen, nh, window, scale, vl, q_prescaled != 0, static_cast<hipStream_t>(stream),
+                                         cm3p_drop::make_cfg(layer, cm3p_drop::kSiteAttnProbs, thr, seed)));
 }
 
 int cm3p_attn_bwd_dropout_varlen(const void* qkv, const void* out, const void* dout, const float* lse, float* delta, void* dqkv,
                                  const int* cu_seqlens, int B, int max_seqlen, int64_t total, int nh, int window, float scale,
                                  const float* cos_tab, const float* sin_tab, int stages, int q_prescaled, int layer, int thr, uint64_t seed,
                                  void* stream) {
-    CM3P_REQUIRE((cos_tab == nullptr) == (sin_tab == nullptr));
-    CM3P_REQUIRE(stages >= 1 && stages <= 3);
-    CM3P_REQUIRE(qkv && out && dout && lse && delta && dqkv && cu_seqlens && B > 0 && max_seqlen > 0 && total > 0 && nh > 0 && scale > 0.f);
-    CM3P_REQUIRE(cm3p_aligned16(qkv) && cm3p_aligned16(out) && cm3p_aligned16(dout) && cm3p_aligned16(dqkv));
-    CM3P_REQUIRE((int64_t)max_seqlen * 3 * nh * 128 < (int64_t(1) << 31));
-    CM3P_ATTN_DROP_REQUIRE();
-    const int rc = launch_attn_bwd_drop(qkv, out, dout, lse, delta, dqkv, nullptr, B, max_seqlen, nh, window, scale, cos_tab, sin_tab, 0,
-                                        VarLen{cu_seqlens, total}, stages, q_prescaled != 0,
-                                        cm3p_drop::make_cfg(layer, cm3p_drop::kSiteAttnProbs, thr, seed), static_cast<hipStream_t>(stream));
-    if (rc != CM3P_OK) return rc;
-    CM3P_LAUNCH_CHECK();
-    return CM3P_OK;
+    const VarLen vl{cu_seqlens, total};
+    CM3P_REQUIRE(attn_bwd_args_ok(qkv, out, dout, lse, delta, dqkv, B, max_seqlen, nh, scale, cos_tab, sin_tab, 0, stages, &vl) &&
+                 cm3p_drop::cfg_args_ok(layer, thr));
+    return attn_launched(launch_attn_bwd(qkv, out, dout, lse, delta, dqkv, nullptr, B, max_seqlen, nh, window, scale, cos_tab, sin_tab, 0, vl, stages,
+                                         q_prescaled != 0, static_cast<hipStream_t>(stream),
+                                         cm3p_drop::make_cfg(layer, cm3p_drop::kSiteAttnProbs, thr, seed)));
 }
-#undef CM3P_ATTN_DROP_REQUIRE
 
 int cm3p_attn_probs(const void* qkv, const float* lse, const uint8_t* key_mask, float* probs, int B, int S, int nh, int window, float scale,
                     int q_prescaled, void* stream) {

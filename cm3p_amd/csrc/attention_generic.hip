@@ -19,13 +19,7 @@ namespace {
 
 // Drop = {cm3p_drop::DropCfg}: attention-probability dropout (dropout_rng.h, site 1; the rule of attention.hip's band kernels): l sums the
 // undropped p, PV takes p o keep, dS = P o (Z o dP - delta), dV = (P o Z)^T dO.  Drop = {} is the kernel without dropout: same signature,
-// same code.
-template <typename... T>
-__device__ __forceinline__ cm3p_drop::DropCfg gen_drop_cfg(T... t) {
-    if constexpr (sizeof...(T) > 0) return (t, ...);
-    else return cm3p_drop::DropCfg{};
-}
-
+// same code (cm3p_drop::drop_cfg).
 constexpr float kLog2eG = 1.4426950408889634f;
 
 template <int D>
@@ -47,13 +41,31 @@ __device__ __forceinline__ void store_row_bf16(uint16_t* dst, const float (&src)
     }
 }
 
+// A key tile of the forward and the dq kernel: thread tid stages row `key` of K and V as fp32 (rows past the sequence repeat the last one)
+// and whether the key is visible at all (inside the sequence and not masked out).  `base`: this (batch, head)'s q rows.
+template <int D>
+__device__ __forceinline__ void stage_kv_tile(float (&Ks)[64][D + 1], float (&Vs)[64][D + 1], int (&Ms)[64], const uint16_t* __restrict__ base,
+                                              const uint8_t* __restrict__ kmask, int b, int S, int nh, int key, int tid) {
+    const int64_t ld = (int64_t)3 * nh * D;
+    float kr[D], vr[D];
+    const int kc = min(key, S - 1);
+    load_row_f32<D>(kr, base + (int64_t)kc * ld + nh * D);
+    load_row_f32<D>(vr, base + (int64_t)kc * ld + 2 * nh * D);
+#pragma unroll
+    for (int d = 0; d < D; ++d) {
+        Ks[tid][d] = kr[d];
+        Vs[tid][d] = vr[d];
+    }
+    Ms[tid] = key < S && (kmask ? kmask[(int64_t)b * S + key] != 0 : true);
+}
+
 // one workgroup = 64 queries of one (batch, head), one thread per query; key tiles of 64 rows staged in LDS as fp32
 template <int D, typename... Drop>
 __global__ __launch_bounds__(64) void attn_gen_fwd_kernel(const uint16_t* __restrict__ qkv, uint16_t* __restrict__ out, float* __restrict__ lse,
                                                           const uint8_t* __restrict__ kmask, int S, int nh, int window, float scale,
                                                           Drop... drop) {
     constexpr bool DROP = sizeof...(Drop) > 0;
-    const cm3p_drop::DropCfg dc = gen_drop_cfg(drop...);
+    const cm3p_drop::DropCfg dc = cm3p_drop::drop_cfg(drop...);
     __shared__ float Ks[64][D + 1], Vs[64][D + 1];
     __shared__ int Ms[64];
     const int tid = threadIdx.x, head = blockIdx.y, b = blockIdx.z;
@@ -68,19 +80,7 @@ __global__ __launch_bounds__(64) void attn_gen_fwd_kernel(const uint16_t* __rest
     float m = -__builtin_huge_valf(), l = 0.f;
     const int klo = window < 0 ? 0 : max(0, Q0 - window), khi = window < 0 ? S - 1 : min(S - 1, Q0 + 63 + window);
     for (int t = klo / 64; t <= khi / 64; ++t) {
-        const int key = t * 64 + tid;
-        {
-            float kr[D], vr[D];
-            const int kc = min(key, S - 1);
-            load_row_f32<D>(kr, base + (int64_t)kc * ld + nh * D);
-            load_row_f32<D>(vr, base + (int64_t)kc * ld + 2 * nh * D);
-#pragma unroll
-            for (int d = 0; d < D; ++d) {
-                Ks[tid][d] = kr[d];
-                Vs[tid][d] = vr[d];
-            }
-            Ms[tid] = key < S && (kmask ? kmask[(int64_t)b * S + key] != 0 : true);
-        }
+        stage_kv_tile<D>(Ks, Vs, Ms, base, kmask, b, S, nh, t * 64 + tid, tid);
         __syncthreads();
         uint32_t m8 = 0;
         for (int k = 0; k < 64; ++k) {
@@ -123,7 +123,7 @@ __global__ __launch_bounds__(64) void attn_gen_dq_kernel(const uint16_t* __restr
                                                          float* __restrict__ delta, uint16_t* __restrict__ dqkv, const uint8_t* __restrict__ kmask,
                                                          int S, int nh, int window, float scale, Drop... drop) {
     constexpr bool DROP = sizeof...(Drop) > 0;
-    const cm3p_drop::DropCfg dc = gen_drop_cfg(drop...);
+    const cm3p_drop::DropCfg dc = cm3p_drop::drop_cfg(drop...);
     __shared__ float Ks[64][D + 1], Vs[64][D + 1];
     __shared__ int Ms[64];
     const int tid = threadIdx.x, head = blockIdx.y, b = blockIdx.z;
@@ -148,19 +148,7 @@ __global__ __launch_bounds__(64) void attn_gen_dq_kernel(const uint16_t* __restr
     for (int d = 0; d < D; ++d) dq[d] = 0.f;
     const int klo = window < 0 ? 0 : max(0, Q0 - window), khi = window < 0 ? S - 1 : min(S - 1, Q0 + 63 + window);
     for (int t = klo / 64; t <= khi / 64; ++t) {
-        const int key = t * 64 + tid;
-        {
-            float kr[D], vr[D];
-            const int kc = min(key, S - 1);
-            load_row_f32<D>(kr, base + (int64_t)kc * ld + nh * D);
-            load_row_f32<D>(vr, base + (int64_t)kc * ld + 2 * nh * D);
-#pragma unroll
-            for (int d = 0; d < D; ++d) {
-                Ks[tid][d] = kr[d];
-                Vs[tid][d] = vr[d];
-            }
-            Ms[tid] = key < S && (kmask ? kmask[(int64_t)b * S + key] != 0 : true);
-        }
+        stage_kv_tile<D>(Ks, Vs, Ms, base, kmask, b, S, nh, t * 64 + tid, tid);
         __syncthreads();
         uint32_t m8 = 0;
         for (int k = 0; k < 64; ++k) {
@@ -194,7 +182,7 @@ __global__ __launch_bounds__(64) void attn_gen_dkv_kernel(const uint16_t* __rest
                                                           uint16_t* __restrict__ dqkv, const uint8_t* __restrict__ kmask, int S, int nh, int window,
                                                           float scale, Drop... drop) {
     constexpr bool DROP = sizeof...(Drop) > 0;
-    const cm3p_drop::DropCfg dc = gen_drop_cfg(drop...);
+    const cm3p_drop::DropCfg dc = cm3p_drop::drop_cfg(drop...);
     __shared__ float Qs[64][D + 1], Gs[64][D + 1];
     __shared__ float Ls[64], Ds[64];
     const int tid = threadIdx.x, head = blockIdx.y, b = blockIdx.z;
@@ -292,20 +280,29 @@ __global__ __launch_bounds__(256) void rope_gen_kernel(uint16_t* __restrict__ qk
 
 }  // namespace
 
-extern "C" {
+// What the four launching entry points require of their arguments (the dropout forms add cm3p_drop::cfg_args_ok and refuse 96 / 128).
+static bool gen_fwd_args_ok(const void* qkv, const void* out, const float* lse, int B, int S, int nh, int head_dim, float scale) {
+    return qkv && out && lse && B > 0 && S > 0 && nh > 0 && scale > 0.f && cm3p_attn_generic_supported(head_dim) && cm3p_aligned16(qkv) &&
+           cm3p_aligned16(out);
+}
 
-// 16 / 32 / 64: the fp32 kernels above; 96 / 128: attention_hd.hip (no dropout form)
-int cm3p_attn_generic_supported(int head_dim) { return head_dim == 16 || head_dim == 32 || head_dim == 64 || cm3p_attn_hd_supported(head_dim); }
+static bool gen_bwd_args_ok(const void* qkv, const void* out, const void* dout, const float* lse, const float* delta, const void* dqkv, int B, int S,
+                            int nh, int head_dim, float scale) {
+    return gen_fwd_args_ok(qkv, out, lse, B, S, nh, head_dim, scale) && dout && delta && dqkv && cm3p_aligned16(dout) && cm3p_aligned16(dqkv);
+}
 
-int cm3p_attn_fwd_generic(const void* qkv, void* out, float* lse, const uint8_t* key_mask, int B, int S, int nh, int head_dim, int window,
-                          float scale, void* stream) {
-    CM3P_REQUIRE(qkv && out && lse && B > 0 && S > 0 && nh > 0 && scale > 0.f && cm3p_attn_generic_supported(head_dim));
-    CM3P_REQUIRE(cm3p_aligned16(qkv) && cm3p_aligned16(out));
+// One launcher per direction.  Drop = {} or {cm3p_drop::DropCfg}: the kernels' trailing pack.  16 / 32 / 64: the fp32 kernels above;
+// 96 / 128: the matrix-core kernels of attention_hd.hip, which have no dropout form.
+template <typename... Drop>
+static int launch_gen_fwd(const void* qkv, void* out, float* lse, const uint8_t* key_mask, int B, int S, int nh, int head_dim, int window, float scale,
+                          hipStream_t s, Drop... drop) {
+    if (cm3p_attn_hd_supported(head_dim)) {
+        if constexpr (sizeof...(Drop) == 0) return cm3p_attn_hd_fwd((const uint16_t*)qkv, (uint16_t*)out, lse, key_mask, B, S, nh, head_dim, window, scale, s);
+        else return CM3P_ERR_INVALID;
+    }
     const dim3 grid((S + 63) / 64, nh, B);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (cm3p_attn_hd_supported(head_dim))
-        return cm3p_attn_hd_fwd((const uint16_t*)qkv, (uint16_t*)out, lse, key_mask, B, S, nh, head_dim, window, scale, s);
-#define CM3P_GEN_FWD(DD) attn_gen_fwd_kernel<DD><<<grid, 64, 0, s>>>((const uint16_t*)qkv, (uint16_t*)out, lse, key_mask, S, nh, window, scale)
+#define CM3P_GEN_FWD(DD) \
+    attn_gen_fwd_kernel<DD, Drop...><<<grid, 64, 0, s>>>((const uint16_t*)qkv, (uint16_t*)out, lse, key_mask, S, nh, window, scale, drop...)
     if (head_dim == 16) CM3P_GEN_FWD(16);
     else if (head_dim == 32) CM3P_GEN_FWD(32);
     else CM3P_GEN_FWD(64);
@@ -314,19 +311,21 @@ int cm3p_attn_fwd_generic(const void* qkv, void* out, float* lse, const uint8_t*
     return CM3P_OK;
 }
 
-int cm3p_attn_bwd_generic(const void* qkv, const void* out, const void* dout, const float* lse, float* delta, void* dqkv,
-                          const uint8_t* key_mask, int B, int S, int nh, int head_dim, int window, float scale, void* stream) {
-    CM3P_REQUIRE(qkv && out && dout && lse && delta && dqkv && B > 0 && S > 0 && nh > 0 && scale > 0.f && cm3p_attn_generic_supported(head_dim));
-    CM3P_REQUIRE(cm3p_aligned16(qkv) && cm3p_aligned16(out) && cm3p_aligned16(dout) && cm3p_aligned16(dqkv));
+template <typename... Drop>
+static int launch_gen_bwd(const void* qkv, const void* out, const void* dout, const float* lse, float* delta, void* dqkv, const uint8_t* key_mask, int B,
+                          int S, int nh, int head_dim, int window, float scale, hipStream_t s, Drop... drop) {
+    if (cm3p_attn_hd_supported(head_dim)) {
+        if constexpr (sizeof...(Drop) == 0)
+            return cm3p_attn_hd_bwd((const uint16_t*)qkv, (const uint16_t*)out, (const uint16_t*)dout, lse, delta, (uint16_t*)dqkv, key_mask, B, S, nh,
+                                    head_dim, window, scale, s);
+        else return CM3P_ERR_INVALID;
+    }
     const dim3 grid((S + 63) / 64, nh, B);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (cm3p_attn_hd_supported(head_dim))
-        return cm3p_attn_hd_bwd((const uint16_t*)qkv, (const uint16_t*)out, (const uint16_t*)dout, lse, delta, (uint16_t*)dqkv, key_mask, B, S, nh,
-                                head_dim, window, scale, s);
-#define CM3P_GEN_BWD(DD)                                                                                                                   \
-    attn_gen_dq_kernel<DD><<<grid, 64, 0, s>>>((const uint16_t*)qkv, (const uint16_t*)out, (const uint16_t*)dout, lse, delta, (uint16_t*)dqkv, \
-                                               key_mask, S, nh, window, scale);                                                            \
-    attn_gen_dkv_kernel<DD><<<grid, 64, 0, s>>>((const uint16_t*)qkv, (const uint16_t*)dout, lse, delta, (uint16_t*)dqkv, key_mask, S, nh, window, scale)
+#define CM3P_GEN_BWD(DD)                                                                                                                       \
+    attn_gen_dq_kernel<DD, Drop...><<<grid, 64, 0, s>>>((const uint16_t*)qkv, (const uint16_t*)out, (const uint16_t*)dout, lse, delta, (uint16_t*)dqkv, \
+                                                        key_mask, S, nh, window, scale, drop...);                                              \
+    attn_gen_dkv_kernel<DD, Drop...><<<grid, 64, 0, s>>>((const uint16_t*)qkv, (const uint16_t*)dout, lse, delta, (uint16_t*)dqkv, key_mask, S, nh, window, \
+                                                         scale, drop...)
     if (head_dim == 16) { CM3P_GEN_BWD(16); }
     else if (head_dim == 32) { CM3P_GEN_BWD(32); }
     else { CM3P_GEN_BWD(64); }
@@ -335,46 +334,35 @@ int cm3p_attn_bwd_generic(const void* qkv, const void* out, const void* dout, co
     return CM3P_OK;
 }
 
+extern "C" {
+
+int cm3p_attn_generic_supported(int head_dim) { return head_dim == 16 || head_dim == 32 || head_dim == 64 || cm3p_attn_hd_supported(head_dim); }
+
+int cm3p_attn_fwd_generic(const void* qkv, void* out, float* lse, const uint8_t* key_mask, int B, int S, int nh, int head_dim, int window,
+                          float scale, void* stream) {
+    CM3P_REQUIRE(gen_fwd_args_ok(qkv, out, lse, B, S, nh, head_dim, scale));
+    return launch_gen_fwd(qkv, out, lse, key_mask, B, S, nh, head_dim, window, scale, static_cast<hipStream_t>(stream));
+}
+
+int cm3p_attn_bwd_generic(const void* qkv, const void* out, const void* dout, const float* lse, float* delta, void* dqkv,
+                          const uint8_t* key_mask, int B, int S, int nh, int head_dim, int window, float scale, void* stream) {
+    CM3P_REQUIRE(gen_bwd_args_ok(qkv, out, dout, lse, delta, dqkv, B, S, nh, head_dim, scale));
+    return launch_gen_bwd(qkv, out, dout, lse, delta, dqkv, key_mask, B, S, nh, head_dim, window, scale, static_cast<hipStream_t>(stream));
+}
+
 int cm3p_attn_fwd_generic_dropout(const void* qkv, void* out, float* lse, const uint8_t* key_mask, int B, int S, int nh, int head_dim,
                                   int window, float scale, int layer, int thr, uint64_t seed, void* stream) {
-    CM3P_REQUIRE(qkv && out && lse && B > 0 && S > 0 && nh > 0 && scale > 0.f && cm3p_attn_generic_supported(head_dim));
-    CM3P_REQUIRE(cm3p_aligned16(qkv) && cm3p_aligned16(out));
-    CM3P_REQUIRE(thr >= 0 && thr <= 65536 && layer >= 0 && layer < (1 << 29));
-    CM3P_REQUIRE(!cm3p_attn_hd_supported(head_dim));  // the matrix-core kernels of 96 / 128 have no dropout form
-    const dim3 grid((S + 63) / 64, nh, B);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const cm3p_drop::DropCfg dc = cm3p_drop::make_cfg(layer, cm3p_drop::kSiteAttnProbs, thr, seed);
-#define CM3P_GEN_FWD(DD) \
-    attn_gen_fwd_kernel<DD, cm3p_drop::DropCfg><<<grid, 64, 0, s>>>((const uint16_t*)qkv, (uint16_t*)out, lse, key_mask, S, nh, window, scale, dc)
-    if (head_dim == 16) CM3P_GEN_FWD(16);
-    else if (head_dim == 32) CM3P_GEN_FWD(32);
-    else CM3P_GEN_FWD(64);
-#undef CM3P_GEN_FWD
-    CM3P_LAUNCH_CHECK();
-    return CM3P_OK;
+    CM3P_REQUIRE(gen_fwd_args_ok(qkv, out, lse, B, S, nh, head_dim, scale) && cm3p_drop::cfg_args_ok(layer, thr));
+    return launch_gen_fwd(qkv, out, lse, key_mask, B, S, nh, head_dim, window, scale, static_cast<hipStream_t>(stream),
+                          cm3p_drop::make_cfg(layer, cm3p_drop::kSiteAttnProbs, thr, seed));
 }
 
 int cm3p_attn_bwd_generic_dropout(const void* qkv, const void* out, const void* dout, const float* lse, float* delta, void* dqkv,
                                   const uint8_t* key_mask, int B, int S, int nh, int head_dim, int window, float scale, int layer, int thr,
                                   uint64_t seed, void* stream) {
-    CM3P_REQUIRE(qkv && out && dout && lse && delta && dqkv && B > 0 && S > 0 && nh > 0 && scale > 0.f && cm3p_attn_generic_supported(head_dim));
-    CM3P_REQUIRE(cm3p_aligned16(qkv) && cm3p_aligned16(out) && cm3p_aligned16(dout) && cm3p_aligned16(dqkv));
-    CM3P_REQUIRE(thr >= 0 && thr <= 65536 && layer >= 0 && layer < (1 << 29));
-    CM3P_REQUIRE(!cm3p_attn_hd_supported(head_dim));  // the matrix-core kernels of 96 / 128 have no dropout form
-    const dim3 grid((S + 63) / 64, nh, B);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const cm3p_drop::DropCfg dc = cm3p_drop::make_cfg(layer, cm3p_drop::kSiteAttnProbs, thr, seed);
-#define CM3P_GEN_BWD(DD)                                                                                                                   \
-    attn_gen_dq_kernel<DD, cm3p_drop::DropCfg><<<grid, 64, 0, s>>>((const uint16_t*)qkv, (const uint16_t*)out, (const uint16_t*)dout, lse, delta,  \
-                                                                   (uint16_t*)dqkv, key_mask, S, nh, window, scale, dc);                          \
-    attn_gen_dkv_kernel<DD, cm3p_drop::DropCfg><<<grid, 64, 0, s>>>((const uint16_t*)qkv, (const uint16_t*)dout, lse, delta, (uint16_t*)dqkv,      \
-                                                                    key_mask, S, nh, window, scale, dc)
-    if (head_dim == 16) { CM3P_GEN_BWD(16); }
-    else if (head_dim == 32) { CM3P_GEN_BWD(32); }
-    else { CM3P_GEN_BWD(64); }
-#undef CM3P_GEN_BWD
-    CM3P_LAUNCH_CHECK();
-    return CM3P_OK;
+    CM3P_REQUIRE(gen_bwd_args_ok(qkv, out, dout, lse, delta, dqkv, B, S, nh, head_dim, scale) && cm3p_drop::cfg_args_ok(layer, thr));
+    return launch_gen_bwd(qkv, out, dout, lse, delta, dqkv, key_mask, B, S, nh, head_dim, window, scale, static_cast<hipStream_t>(stream),
+                          cm3p_drop::make_cfg(layer, cm3p_drop::kSiteAttnProbs, thr, seed));
 }
 
 int cm3p_rope_apply_generic(void* qkv, const float* cos_tab, const float* sin_tab, int B, int S, int nh, int head_dim, int64_t pos_batch_stride,

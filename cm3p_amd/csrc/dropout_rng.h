@@ -89,7 +89,18 @@ CM3P_DROP_HD DropCfg make_cfg(int layer, uint32_t site, int thr, uint64_t seed) 
     return DropCfg{seed, site_word(layer, site), (uint32_t)thr, keep_scale((uint32_t)thr)};
 }
 
+// the (layer, thr) an entry point may hand to make_cfg: a threshold in [0, 65536], a layer whose counter word fits 32 bits with room
+CM3P_DROP_HD bool cfg_args_ok(int layer, int thr) { return thr >= 0 && thr <= 65536 && layer >= 0 && layer < (1 << 29); }
+
 #if defined(__HIPCC__)
+// A kernel with an optional dropout site takes a trailing `Drop... drop` pack: {DropCfg} with dropout, {} without - the same kernel with
+// the same signature as before it had the site.  This is the configuration either way (unread when the pack is empty).
+template <typename... T>
+__device__ __forceinline__ DropCfg drop_cfg(T... t) {
+    if constexpr (sizeof...(T) > 0) return (t, ...);
+    else return DropCfg{};
+}
+
 // Row t of an activation -> (sequence b, position s).  Padded: cu == nullptr, rows of S positions.  Packed: cu_seqlens [nseq + 1],
 // b = the last sequence whose first row is <= t (alignment rows form a pseudo-sequence of their own and take no gradient).
 __device__ __forceinline__ void row_to_seq(int64_t t, int S, const int* __restrict__ cu, int nseq, uint32_t& b, uint32_t& s) {

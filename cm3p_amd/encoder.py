@@ -249,6 +249,18 @@ def _layer_forward(geo: _Geometry, i: int, x: Tensor, wb, want_stats: bool):
     return x_out, (x, xn, mean_a, rstd_a, qkv, o, lse, x_mid, xn2, mean_m, rstd_m, h, g)
 
 
+def _attn_backward(geo: _Geometry, i: int, qkv: Tensor, o: Tensor, do: Tensor, lse: Tensor, ad: Optional[tuple]) -> Tensor:
+    """Layer i's attention backward -> dqkv; the inverse rotary rotation of dq / dk is applied in the kernels' epilogue (head_dim 64)
+    or as its own pass (the generic kernels).  ad: the layer's attention dropout (thr, seed, layer), or None."""
+    B, S, nh, window, scale = geo.B, geo.S, geo.nh, geo.windows[i], geo.hd ** -0.5
+    if geo.hd != 64:
+        dqkv = K.attn_bwd_generic(qkv, o, do, lse, geo.key_mask, B, S, nh, geo.hd, window, scale, drop=ad)
+        return K.rope_apply_generic_(dqkv, geo.rope[i][0], geo.rope[i][1], B, S, nh, geo.hd, geo.per_batch_pos, inverse=True)
+    if geo.cu is not None:
+        return K.attn_bwd_varlen(qkv, o, do, lse, geo.cu, B, geo.max_s, nh, window, scale, geo.rope[i], prescaled=True, drop=ad)
+    return K.attn_bwd(qkv, o, do, lse, geo.key_mask, B, S, nh, window, scale, geo.rope[i], geo.per_batch_pos, prescaled=True, drop=ad)
+
+
 class _EncoderLayerFn(torch.autograd.Function):
     """One ModernBERT encoder layer (TF:...modeling_modernbert.py:318-333): x [T,H] fp32 + its weights -> x_out [T,H] fp32
     (bf16 -> bf16 on the bf16 residual stream: the residual GEMMs take x's dtype; its backward is _backward_bf16).
@@ -286,8 +298,6 @@ class _EncoderLayerFn(torch.autograd.Function):
         dgrad / wgrad GEMMs read, and each LayerNorm backward replaces it by bf16(g + LN'(dy)) - fp32 sum, one rounding (torch's bf16
         LayerNorm backward rounds LN'(dy) first and the sum again; the single rounding is the more accurate of the two)."""
         geo, i = ctx.geo, ctx.i
-        B, S, nh = geo.B, geo.S, geo.nh
-        scale = geo.hd ** -0.5
         need = ctx.needs_input_grad  # (geo, i, x, *weights)
         need_w = list(need[3:])
         if i == 0:
@@ -316,13 +326,7 @@ class _EncoderLayerFn(torch.autograd.Function):
         # ---- attention branch: x_mid = x + o Wo^T
         do = K.linear_dgrad(g, Wo_b, Wo_t)
         dWo = K.linear_wgrad(g, o) if n_o else None
-        if geo.hd != 64:
-            dqkv = K.attn_bwd_generic(qkv, o, do, lse, geo.key_mask, B, S, nh, geo.hd, geo.windows[i], scale)
-            K.rope_apply_generic_(dqkv, geo.rope[i][0], geo.rope[i][1], B, S, nh, geo.hd, geo.per_batch_pos, inverse=True)
-        elif geo.cu is not None:
-            dqkv = K.attn_bwd_varlen(qkv, o, do, lse, geo.cu, B, geo.max_s, nh, geo.windows[i], scale, geo.rope[i], prescaled=True)
-        else:
-            dqkv = K.attn_bwd(qkv, o, do, lse, geo.key_mask, B, S, nh, geo.windows[i], scale, geo.rope[i], geo.per_batch_pos, prescaled=True)
+        dqkv = _attn_backward(geo, i, qkv, o, do, lse, None)
         del do, o, qkv
         dWqkv = K.linear_wgrad(dqkv, xn) if n_qkv else None
         dw_an = None
@@ -344,8 +348,6 @@ class _EncoderLayerFn(torch.autograd.Function):
         if ctx.geo.bf16:
             return _EncoderLayerFn._backward_bf16(ctx, dy)
         geo, i = ctx.geo, ctx.i
-        B, S, nh = geo.B, geo.S, geo.nh
-        scale = geo.hd ** -0.5
         need = ctx.needs_input_grad  # (geo, i, x, *weights)
         need_w = list(need[3:])
         if i == 0:
@@ -380,15 +382,7 @@ class _EncoderLayerFn(torch.autograd.Function):
         do = K.linear_dgrad(gt16, Wo_b, Wo_t)
         dWo = K.linear_wgrad(gt16, o) if n_o else None
         del gt16
-        # attention backward; the inverse rotary rotation of dq / dk is applied in its epilogue
-        if geo.hd != 64:
-            dqkv = K.attn_bwd_generic(qkv, o, do, lse, geo.key_mask, B, S, nh, geo.hd, geo.windows[i], scale, drop=ad)
-            K.rope_apply_generic_(dqkv, geo.rope[i][0], geo.rope[i][1], B, S, nh, geo.hd, geo.per_batch_pos, inverse=True)
-        elif geo.cu is not None:
-            dqkv = K.attn_bwd_varlen(qkv, o, do, lse, geo.cu, B, geo.max_s, nh, geo.windows[i], scale, geo.rope[i], prescaled=True, drop=ad)
-        else:
-            dqkv = K.attn_bwd(qkv, o, do, lse, geo.key_mask, B, S, nh, geo.windows[i], scale, geo.rope[i], geo.per_batch_pos,
-                              prescaled=True, drop=ad)
+        dqkv = _attn_backward(geo, i, qkv, o, do, lse, ad)
         del do, o, qkv
         dWqkv = K.linear_wgrad(dqkv, xn) if n_qkv else None
         if i == 0:

@@ -326,13 +326,22 @@ def gemm8p_get_grid() -> int:
     return int(_lib.load().cm3p_gemm8p_get_grid())
 
 
-def _attn_fwd_name(window: int, prescaled: bool, masked: bool, S: int, nh: int) -> str:
+def _drop_abi(drop: Optional[tuple]) -> tuple:
+    """drop = (thr, seed, layer) or None -> (what the entry point's name gains, the arguments it takes before the stream in the ABI's
+    order, how the kernels' template argument list ends as rocprofv3 prints it)."""
+    if drop is None:
+        return "", (), ">"
+    thr, seed, layer = drop
+    return "_dropout", (layer, thr, seed), ", DropCfg>"
+
+
+def _attn_fwd_name(window: int, prescaled: bool, masked: bool, S: int, nh: int, targs_end: str = ">") -> str:
     """The forward kernel a call lands on, as rocprofv3 names it.  The routing is the library's (cm3p_attn_fwd_impl: global layers with
-    pre-scaled q run the pipelined kernel of csrc/attention_fwd.hip unless the sequence is too long for its 32-bit row offsets);
-    this function only spells the answer (r05 advisor: it used to re-derive the rule)."""
-    if query("cm3p_attn_fwd_impl", S, nh, window, int(prescaled)):
+    pre-scaled q run the pipelined kernel of csrc/attention_fwd.hip unless the sequence is too long for its 32-bit row offsets, and
+    never with dropout); this function only spells the answer (r05 advisor: it used to re-derive the rule)."""
+    if targs_end == ">" and query("cm3p_attn_fwd_impl", S, nh, window, int(prescaled)):
         return "attn_fwd_g_kernel<4, " + ("true>" if masked else "false>")
-    return "attn_fwd_kernel<1, %s, " + ("true>" if window >= 0 else "false>")
+    return "attn_fwd_kernel<1, %s, " + ("true" if window >= 0 else "false") + targs_end
 
 
 def attn_fwd(qkv: Tensor, key_mask: Optional[Tensor], B: int, S: int, nh: int, window: int, scale: float, prescaled: bool = False,
@@ -342,14 +351,10 @@ def attn_fwd(qkv: Tensor, key_mask: Optional[Tensor], B: int, S: int, nh: int, w
     out = torch.empty((B * S, nh * 64), dtype=torch.bfloat16, device=qkv.device)
     lse = torch.empty((B, nh, S), dtype=torch.float32, device=qkv.device)
     keys = S if window < 0 else min(S, 2 * window + 1)
-    if drop is not None:
-        thr, seed, layer = drop
-        call("cm3p_attn_fwd_dropout", ptr(qkv), ptr(out), ptr(lse, torch.float32), ptr(key_mask, torch.uint8), B, S, nh, window, scale, int(prescaled),
-             layer, thr, seed, stream(), tag=_attn_tag("attn_fwd_kernel<1, %s, " + ("true" if window >= 0 else "false") + ", DropCfg>", window, prescaled),
-             work=4.0 * B * nh * S * keys * 64)
-        return out, lse
-    call("cm3p_attn_fwd", ptr(qkv), ptr(out), ptr(lse, torch.float32), ptr(key_mask, torch.uint8), B, S, nh, window, scale, int(prescaled), stream(),
-         tag=_attn_tag(_attn_fwd_name(window, prescaled, key_mask is not None, S, nh), window, prescaled), work=4.0 * B * nh * S * keys * 64)
+    sfx, drop_args, targs_end = _drop_abi(drop)
+    call("cm3p_attn_fwd" + sfx, ptr(qkv), ptr(out), ptr(lse, torch.float32), ptr(key_mask, torch.uint8), B, S, nh, window, scale, int(prescaled),
+         *drop_args, stream(), tag=_attn_tag(_attn_fwd_name(window, prescaled, key_mask is not None, S, nh, targs_end), window, prescaled),
+         work=4.0 * B * nh * S * keys * 64)
     return out, lse
 
 
@@ -381,13 +386,10 @@ def attn_fwd_generic(qkv: Tensor, key_mask: Optional[Tensor], B: int, S: int, nh
     """drop = (thr, seed, layer): attention-probability dropout (the rule of attn_fwd's)."""
     out = torch.empty((B * S, nh * hd), dtype=torch.bfloat16, device=qkv.device)
     lse = torch.empty((B, nh, S), dtype=torch.float32, device=qkv.device)
-    if drop is not None:
-        thr, seed, layer = drop
-        call("cm3p_attn_fwd_generic_dropout", ptr(qkv, torch.bfloat16), ptr(out), ptr(lse, torch.float32), ptr(key_mask, torch.uint8), B, S, nh, hd,
-             window, scale, layer, thr, seed, stream())
-        return out, lse
-    call("cm3p_attn_fwd_generic", ptr(qkv, torch.bfloat16), ptr(out), ptr(lse, torch.float32), ptr(key_mask, torch.uint8), B, S, nh, hd, window, scale, stream(),
-         **_attn_hd_prof(("attn_hd_fwd_kernel",), 2, B, S, nh, hd, window))
+    sfx, drop_args, _ = _drop_abi(drop)
+    prof = {} if drop is not None else _attn_hd_prof(("attn_hd_fwd_kernel",), 2, B, S, nh, hd, window)
+    call("cm3p_attn_fwd_generic" + sfx, ptr(qkv, torch.bfloat16), ptr(out), ptr(lse, torch.float32), ptr(key_mask, torch.uint8), B, S, nh, hd, window, scale,
+         *drop_args, stream(), **prof)
     return out, lse
 
 
@@ -396,14 +398,11 @@ def attn_bwd_generic(qkv: Tensor, out: Tensor, dout: Tensor, lse: Tensor, key_ma
     """-> dqkv with the q / k thirds still in the ROTATED frame (rope_apply_generic_(..., inverse=True) finishes them)."""
     dqkv = torch.empty_like(qkv)
     delta = torch.empty_like(lse)
-    if drop is not None:
-        thr, seed, layer = drop
-        call("cm3p_attn_bwd_generic_dropout", ptr(qkv, torch.bfloat16), ptr(out, torch.bfloat16), ptr(dout, torch.bfloat16), ptr(lse, torch.float32),
-             ptr(delta), ptr(dqkv), ptr(key_mask, torch.uint8), B, S, nh, hd, window, scale, layer, thr, seed, stream())
-        return dqkv
-    call("cm3p_attn_bwd_generic", ptr(qkv, torch.bfloat16), ptr(out, torch.bfloat16), ptr(dout, torch.bfloat16), ptr(lse, torch.float32), ptr(delta), ptr(dqkv),
-         ptr(key_mask, torch.uint8), B, S, nh, hd, window, scale, stream(),
-         **_attn_hd_prof(("attn_hd_dq_kernel", "attn_hd_dkv_kernel"), 4, B, S, nh, hd, window))  # one call, two kernels; attn_bwd's count: 2 x forward
+    sfx, drop_args, _ = _drop_abi(drop)
+    # one call, two kernels; attn_bwd's count: 2 x forward
+    prof = {} if drop is not None else _attn_hd_prof(("attn_hd_dq_kernel", "attn_hd_dkv_kernel"), 4, B, S, nh, hd, window)
+    call("cm3p_attn_bwd_generic" + sfx, ptr(qkv, torch.bfloat16), ptr(out, torch.bfloat16), ptr(dout, torch.bfloat16), ptr(lse, torch.float32), ptr(delta),
+         ptr(dqkv), ptr(key_mask, torch.uint8), B, S, nh, hd, window, scale, *drop_args, stream(), **prof)
     return dqkv
 
 
@@ -477,30 +476,21 @@ def attn_bwd(qkv: Tensor, out: Tensor, dout: Tensor, lse: Tensor, key_mask: Opti
              window: int, scale: float, rope: Optional[tuple] = None, per_batch: bool = False, prescaled: bool = False,
              drop: Optional[tuple] = None) -> Tensor:
     """rope = (cos, sin): also applies the inverse rotary rotation to dq / dk (backward of the fused Wqkv+RoPE GEMM).
-    Global layers (window < 0) run the five-product kernel of csrc/attention_bwd_fused.hip; sliding-window layers the band kernels
-    of csrc/attention.hip, issued as two C calls so that each has its own profiler tag (one rocprof row per tag).  `work` is the
-    algorithmic count of SURVEY.md section 8(d) (backward = 2 x forward = four matmuls: dQ is the dq kernel's, dP / dV / dK the
-    dkv kernel's); the scores each kernel recomputes are not credited."""
-    if drop is not None:
-        thr, seed, layer = drop
-        dqkv = torch.empty_like(qkv)
-        delta = torch.empty_like(lse)
-        cos, sin = rope if rope is not None else (None, None)
-        for stage, name in ((ATTN_BWD_DQ, "attn_bwd_dq_drop_kernel<%s>"), (ATTN_BWD_DKV, "attn_bwd_dkv_drop_kernel<%s>")):
-            call("cm3p_attn_bwd_dropout", ptr(qkv), ptr(out), ptr(dout), ptr(lse, torch.float32), ptr(delta), ptr(dqkv), ptr(key_mask, torch.uint8), B, S,
-                 nh, window, scale, ptr(cos, torch.float32), ptr(sin, torch.float32), S if per_batch else 0, stage, int(prescaled), layer, thr, seed,
-                 stream(), tag=_attn_tag(name, window, prescaled))
-        return dqkv
-    if window < 0:
+    Global layers (window < 0) run the five-product kernel of csrc/attention_bwd_fused.hip; sliding-window layers - and, with dropout,
+    every layer - the band kernels of csrc/attention.hip, issued as two C calls so that each has its own profiler tag (one rocprof row
+    per tag).  `work` is the algorithmic count of SURVEY.md section 8(d) (backward = 2 x forward = four matmuls: dQ is the dq kernel's,
+    dP / dV / dK the dkv kernel's); the scores each kernel recomputes are not credited."""
+    if drop is None and window < 0:
         return _attn_bwd_fused(qkv, out, dout, lse, key_mask, None, B, S, 0, nh, scale, rope, per_batch, prescaled)
     dqkv = torch.empty_like(qkv)
     delta = torch.empty_like(lse)
-    keys = min(S, 2 * window + 1)
+    keys = S if window < 0 else min(S, 2 * window + 1)
     cos, sin = rope if rope is not None else (None, None)
-    for stage, name, products in ((ATTN_BWD_DQ, "attn_bwd_dq_kernel<%s>", 1), (ATTN_BWD_DKV, "attn_bwd_dkv_kernel<%s>", 3)):
-        call("cm3p_attn_bwd", ptr(qkv), ptr(out), ptr(dout), ptr(lse, torch.float32), ptr(delta), ptr(dqkv), ptr(key_mask, torch.uint8), B, S, nh,
-             window, scale, ptr(cos, torch.float32), ptr(sin, torch.float32), S if per_batch else 0, stage, int(prescaled), stream(), tag=_attn_tag(name, window, prescaled),
-             work=2.0 * products * B * nh * S * keys * 64)
+    sfx, drop_args, targs_end = _drop_abi(drop)
+    for stage, name, products in ((ATTN_BWD_DQ, "attn_bwd_dq_kernel<%s", 1), (ATTN_BWD_DKV, "attn_bwd_dkv_kernel<%s", 3)):
+        call("cm3p_attn_bwd" + sfx, ptr(qkv), ptr(out), ptr(dout), ptr(lse, torch.float32), ptr(delta), ptr(dqkv), ptr(key_mask, torch.uint8), B, S, nh,
+             window, scale, ptr(cos, torch.float32), ptr(sin, torch.float32), S if per_batch else 0, stage, int(prescaled), *drop_args, stream(),
+             tag=_attn_tag(name + targs_end, window, prescaled), work=None if drop is not None else 2.0 * products * B * nh * S * keys * 64)
     return dqkv
 
 
@@ -510,38 +500,25 @@ def attn_fwd_varlen(qkv: Tensor, cu: Tensor, B: int, max_s: int, nh: int, window
     total = qkv.shape[0]
     out = torch.empty((total, nh * 64), dtype=torch.bfloat16, device=qkv.device)
     lse = torch.empty((nh, total), dtype=torch.float32, device=qkv.device)
-    if drop is not None:
-        thr, seed, layer = drop
-        call("cm3p_attn_fwd_dropout_varlen", ptr(qkv), ptr(out), ptr(lse, torch.float32), ptr(cu, torch.int32), B, max_s, total, nh, window, scale,
-             int(prescaled), layer, thr, seed, stream(),
-             tag=_attn_tag("attn_fwd_kernel<1, %s, " + ("true" if window >= 0 else "false") + ", DropCfg>", window, prescaled, True))
-        return out, lse
-    call("cm3p_attn_fwd_varlen", ptr(qkv), ptr(out), ptr(lse, torch.float32), ptr(cu, torch.int32), B, max_s, total, nh, window, scale, int(prescaled), stream(),
-         tag=_attn_tag(_attn_fwd_name(window, prescaled, False, max_s, nh), window, prescaled, True))
+    sfx, drop_args, targs_end = _drop_abi(drop)
+    call("cm3p_attn_fwd" + sfx + "_varlen", ptr(qkv), ptr(out), ptr(lse, torch.float32), ptr(cu, torch.int32), B, max_s, total, nh, window, scale,
+         int(prescaled), *drop_args, stream(), tag=_attn_tag(_attn_fwd_name(window, prescaled, False, max_s, nh, targs_end), window, prescaled, True))
     return out, lse
 
 
 def attn_bwd_varlen(qkv: Tensor, out: Tensor, dout: Tensor, lse: Tensor, cu: Tensor, B: int, max_s: int, nh: int, window: int,
                     scale: float, rope: Optional[tuple] = None, prescaled: bool = False, drop: Optional[tuple] = None) -> Tensor:
     """rope = (cos, sin) per packed token [total, 32]: also applies the inverse rotation to dq / dk."""
-    if drop is not None:
-        thr, seed, layer = drop
-        dqkv = torch.empty_like(qkv)
-        delta = torch.empty_like(lse)
-        cos, sin = rope if rope is not None else (None, None)
-        for stage, name in ((ATTN_BWD_DQ, "attn_bwd_dq_drop_kernel<%s>"), (ATTN_BWD_DKV, "attn_bwd_dkv_drop_kernel<%s>")):
-            call("cm3p_attn_bwd_dropout_varlen", ptr(qkv), ptr(out), ptr(dout), ptr(lse, torch.float32), ptr(delta), ptr(dqkv), ptr(cu, torch.int32), B,
-                 max_s, qkv.shape[0], nh, window, scale, ptr(cos, torch.float32), ptr(sin, torch.float32), stage, int(prescaled), layer, thr, seed,
-                 stream(), tag=_attn_tag(name, window, prescaled, True))
-        return dqkv
-    if window < 0:
+    if drop is None and window < 0:
         return _attn_bwd_fused(qkv, out, dout, lse, None, cu, B, max_s, qkv.shape[0], nh, scale, rope, False, prescaled)
     dqkv = torch.empty_like(qkv)
     delta = torch.empty_like(lse)
     cos, sin = rope if rope is not None else (None, None)
-    for stage, name in ((ATTN_BWD_DQ, "attn_bwd_dq_kernel<%s>"), (ATTN_BWD_DKV, "attn_bwd_dkv_kernel<%s>")):
-        call("cm3p_attn_bwd_varlen", ptr(qkv), ptr(out), ptr(dout), ptr(lse, torch.float32), ptr(delta), ptr(dqkv), ptr(cu, torch.int32), B, max_s,
-             qkv.shape[0], nh, window, scale, ptr(cos, torch.float32), ptr(sin, torch.float32), stage, int(prescaled), stream(), tag=_attn_tag(name, window, prescaled, True))
+    sfx, drop_args, targs_end = _drop_abi(drop)
+    for stage, name in ((ATTN_BWD_DQ, "attn_bwd_dq_kernel<%s"), (ATTN_BWD_DKV, "attn_bwd_dkv_kernel<%s")):
+        call("cm3p_attn_bwd" + sfx + "_varlen", ptr(qkv), ptr(out), ptr(dout), ptr(lse, torch.float32), ptr(delta), ptr(dqkv), ptr(cu, torch.int32), B,
+             max_s, qkv.shape[0], nh, window, scale, ptr(cos, torch.float32), ptr(sin, torch.float32), stage, int(prescaled), *drop_args, stream(),
+             tag=_attn_tag(name + targs_end, window, prescaled, True))
     return dqkv
 
 
