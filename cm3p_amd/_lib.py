@@ -15,6 +15,7 @@ import torch
 F32, BF16 = 0, 1
 ADD_A_BF16 = 16  # cm3p_add_f32: or-ed into b_dtype when the first operand (and the result) is bf16
 POOL_PACKED = 2  # cm3p_pool_fwd / cm3p_pool_bwd: or-ed into cls when the rows are packed and `mask` carries their int32 cu_seqlens
+GEMM_F32_TILED = 2  # cm3p_gemm_f32: or-ed into accumulate to run the register-tiled kernel (same bits; operands need a unit stride)
 EPI_BF16, EPI_F32, EPI_F32_RESID, EPI_F32_BIAS, EPI_BF16_RESID = 0, 1, 2, 5, 7
 ABI_VERSION = 19
 

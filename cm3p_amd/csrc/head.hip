@@ -5,6 +5,12 @@
 
 namespace {
 
+// The one store expression of both fp32 GEMM kernels: they share it so that hipcc contracts (or does not contract) c + alpha * acc
+// the same way in both, which keeps the two routes of cm3p_gemm_f32 bit-identical.  c_old is read only with `accumulate`.
+__device__ __forceinline__ float gemm_f32_result(float c_old, float alpha, float acc, int accumulate) {
+    return accumulate ? c_old + alpha * acc : alpha * acc;
+}
+
 // C[m, n] (+)= alpha * sum_k A[m*a_rs + k*a_cs] * B[n*b_rs + k*b_cs];  16 x 16 outputs per block, k tiled by 16 via LDS
 __global__ __launch_bounds__(256) void gemm_f32_kernel(const float* __restrict__ A, const float* __restrict__ B,
                                                        float* __restrict__ C, int M, int N, int K, int64_t a_rs, int64_t a_cs,
@@ -26,8 +32,272 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(const float* __restrict__
     const int m = m0 + ty, n = n0 + tx;
     if (m < M && n < N) {
         float* c = C + (int64_t)m * ldc + n;
-        *c = accumulate ? *c + alpha * acc : alpha * acc;
+        *c = gemm_f32_result(accumulate ? *c : 0.f, alpha, acc, accumulate);
     }
+}
+
+// ---- the register-tiled route of cm3p_gemm_f32 (CM3P_GEMM_F32_TILED) --------------------------------------------------------------
+// Same arithmetic per output as gemm_f32_kernel, bit for bit: acc = 0; for k ascending acc = fmaf(A[m,k], B[n,k], acc), k padded
+// with zero operands to a multiple of 16 (exact, but a -0 accumulator becomes +0, as there), then gemm_f32_result.  No split over k.
+// What differs is who computes what: 256 threads as 16 x 16 own a (16 TM) x (16 TN) tile, each thread TM x TN outputs in registers,
+// so one k step costs a thread TM + TN floats of LDS reads for TM * TN fmas (16 x 16 kernel: 2 for 1).
+//
+// Each operand has a unit stride along k (KUNIT) or along its rows.  Global loads go by chunks of four elements along that stride
+// (one 16-byte load where the operand is 16-byte aligned with a non-unit stride of a multiple of 4 and the chunk is inside; else
+// guarded scalar loads, zeros outside), consecutive lanes on consecutive chunks.  The LDS image is k-major, s[kk][row], with a
+// leading dimension of rows + 4: fragment reads are 16-byte reads at row 4 t (+ 64 g) of one k row, so the 16 lanes the LDS
+// serves together hit 16 x 4 distinct banks (tx) or broadcast (ty); the transposing b32 stores of a KUNIT operand are 2-way, which
+// a b32 store hides; the row-unit operand stores 16 bytes per lane along a k row.
+constexpr int kGtK = 16;
+
+template <int T>
+__device__ __forceinline__ int gt_row(int t, int i) {  // tile row (column) of a thread's i-th output row (column)
+    return T == 2 ? t * 2 + i : (i >> 2) * 64 + t * 4 + (i & 3);
+}
+
+template <int ROWS, bool KUNIT>
+struct GtStage {
+    static constexpr int CH = ROWS * kGtK / 4;  // chunks per tile
+    static constexpr int NCH = (CH + 255) / 256;  // per thread
+    float v[NCH][4];
+
+    __device__ __forceinline__ void load(const float* __restrict__ P, int rows, int K, int64_t ld, int row0, int k0, int vec) {
+#pragma unroll
+        for (int c = 0; c < NCH; ++c) {
+            const int i = threadIdx.x + c * 256;
+            if (CH % 256 != 0 && i >= CH) break;
+            int row, k;
+            if (KUNIT) {
+                row = row0 + (i >> 2);
+                k = k0 + (i & 3) * 4;
+            } else {
+                row = row0 + (i % (ROWS / 4)) * 4;
+                k = k0 + i / (ROWS / 4);
+            }
+            const int64_t off = KUNIT ? (int64_t)row * ld + k : (int64_t)k * ld + row;
+            const bool whole = KUNIT ? (row < rows && k + 3 < K) : (k < K && row + 3 < rows);
+            if (vec && whole) {
+                const float4 f = *reinterpret_cast<const float4*>(P + off);
+                v[c][0] = f.x, v[c][1] = f.y, v[c][2] = f.z, v[c][3] = f.w;
+            } else {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const bool in = KUNIT ? (row < rows && k + j < K) : (k < K && row + j < rows);
+                    v[c][j] = in ? P[off + j] : 0.f;
+                }
+            }
+        }
+    }
+
+    __device__ __forceinline__ void store(float* s) const {  // s[kGtK][ROWS + 4]
+#pragma unroll
+        for (int c = 0; c < NCH; ++c) {
+            const int i = threadIdx.x + c * 256;
+            if (CH % 256 != 0 && i >= CH) break;
+            if (KUNIT) {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) s[((i & 3) * 4 + j) * (ROWS + 4) + (i >> 2)] = v[c][j];
+            } else {
+                *reinterpret_cast<float4*>(s + (i / (ROWS / 4)) * (ROWS + 4) + (i % (ROWS / 4)) * 4) = make_float4(v[c][0], v[c][1], v[c][2], v[c][3]);
+            }
+        }
+    }
+};
+
+template <int T>
+__device__ __forceinline__ void gt_frag(const float* s, int t, float (&f)[T]) {  // s: one k row of the LDS image
+    if (T == 2) {
+        const float2 x = *reinterpret_cast<const float2*>(s + t * 2);
+        f[0] = x.x, f[1] = x.y;
+    } else {
+#pragma unroll
+        for (int g = 0; g < T / 4; ++g) {
+            const float4 x = *reinterpret_cast<const float4*>(s + g * 64 + t * 4);
+            f[g * 4] = x.x, f[g * 4 + 1] = x.y, f[g * 4 + 2] = x.z, f[g * 4 + 3] = x.w;
+        }
+    }
+}
+
+// a_ld / b_ld: the operand's non-unit stride; a_vec / b_vec / c_vec: 16-byte accesses are aligned (decided on the host)
+template <int TM, int TN, bool A_KUNIT, bool B_KUNIT>
+__global__ __launch_bounds__(256) void gemm_f32_tiled_kernel(const float* __restrict__ A, const float* __restrict__ B,
+                                                             float* __restrict__ C, int M, int N, int K, int64_t a_ld, int64_t b_ld,
+                                                             int64_t ldc, float alpha, int accumulate, int a_vec, int b_vec, int c_vec) {
+    static_assert((TM == 2 || TM == 4 || TM == 8) && (TN == 4 || TN == 8), "tile instances");
+    constexpr int BM = 16 * TM, BN = 16 * TN;
+    __shared__ __attribute__((aligned(16))) float sa[kGtK * (BM + 4)];
+    __shared__ __attribute__((aligned(16))) float sb[kGtK * (BN + 4)];
+    const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;
+    const int m0 = blockIdx.y * BM, n0 = blockIdx.x * BN;
+    float acc[TM][TN];
+#pragma unroll
+    for (int i = 0; i < TM; ++i)
+#pragma unroll
+        for (int j = 0; j < TN; ++j) acc[i][j] = 0.f;
+    GtStage<BM, A_KUNIT> ga;
+    GtStage<BN, B_KUNIT> gb;
+    ga.load(A, M, K, a_ld, m0, 0, a_vec);
+    gb.load(B, N, K, b_ld, n0, 0, b_vec);
+    for (int k0 = 0; k0 < K; k0 += kGtK) {
+        ga.store(sa);
+        gb.store(sb);
+        __syncthreads();
+        if (k0 + kGtK < K) {  // the next k tile travels while this one is multiplied
+            ga.load(A, M, K, a_ld, m0, k0 + kGtK, a_vec);
+            gb.load(B, N, K, b_ld, n0, k0 + kGtK, b_vec);
+        }
+#pragma unroll
+        for (int kk = 0; kk < kGtK; ++kk) {
+            float a[TM], b[TN];
+            gt_frag<TM>(sa + kk * (BM + 4), ty, a);
+            gt_frag<TN>(sb + kk * (BN + 4), tx, b);
+#pragma unroll
+            for (int i = 0; i < TM; ++i)
+#pragma unroll
+                for (int j = 0; j < TN; ++j) acc[i][j] = fmaf(a[i], b[j], acc[i][j]);
+        }
+        __syncthreads();
+    }
+#pragma unroll
+    for (int i = 0; i < TM; ++i) {
+        const int m = m0 + gt_row<TM>(ty, i);
+        if (m >= M) continue;
+#pragma unroll
+        for (int g = 0; g < TN / 4; ++g) {
+            const int n = n0 + g * 64 + tx * 4;
+            float* c = C + (int64_t)m * ldc + n;
+            if (c_vec && n + 3 < N) {
+                float4 o = accumulate ? *reinterpret_cast<const float4*>(c) : make_float4(0.f, 0.f, 0.f, 0.f);
+                o.x = gemm_f32_result(o.x, alpha, acc[i][g * 4], accumulate);
+                o.y = gemm_f32_result(o.y, alpha, acc[i][g * 4 + 1], accumulate);
+                o.z = gemm_f32_result(o.z, alpha, acc[i][g * 4 + 2], accumulate);
+                o.w = gemm_f32_result(o.w, alpha, acc[i][g * 4 + 3], accumulate);
+                *reinterpret_cast<float4*>(c) = o;
+            } else {
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+                    if (n + j < N) c[j] = gemm_f32_result(accumulate ? c[j] : 0.f, alpha, acc[i][g * 4 + j], accumulate);
+            }
+        }
+    }
+}
+
+// ---- the few-outputs instance of the tiled route ---------------------------------------------------------------------------------
+// k is never split, so a problem with few outputs cannot fill the chip with large tiles: it keeps gemm_f32_kernel's 16 x 16 outputs
+// per workgroup, one per thread.  What such a problem pays for is its number of k tiles, each a round trip global memory -> LDS ->
+// barrier -> multiply -> barrier.  This instance takes k in tiles of 64 (a quarter of the barriers), has the next tile's loads in
+// flight while it multiplies, and reads the LDS 16 bytes at a time.  The chain per output is the same: k ascending, padded with zero
+// operands to a multiple of 16 (the multiply stops at the padded K, not at the end of the 64-tile).
+// LDS image: row-major s[row][k] with a leading dimension of 68, so the 16-byte reads of 16 rows at one k cover all 64 banks; an
+// operand with its unit stride along k is copied 16 bytes per lane, the other kind is transposed by b32 stores (2-way, hidden).
+constexpr int kGlK = 64;
+constexpr int kGlLd = kGlK + 4;
+
+template <bool KUNIT>
+struct GlStage {  // one thread's chunk (four elements along the unit stride) of a [16 x 64] operand tile
+    float v[4];
+
+    __device__ __forceinline__ void load(const float* __restrict__ P, int rows, int K, int64_t ld, int row0, int k0, int vec) {
+        const int i = threadIdx.x;
+        const int row = row0 + (KUNIT ? i >> 4 : (i & 3) * 4), k = k0 + (KUNIT ? (i & 15) * 4 : i >> 2);
+        const int64_t off = KUNIT ? (int64_t)row * ld + k : (int64_t)k * ld + row;
+        const bool whole = KUNIT ? (row < rows && k + 3 < K) : (k < K && row + 3 < rows);
+        if (vec && whole) {
+            const float4 f = *reinterpret_cast<const float4*>(P + off);
+            v[0] = f.x, v[1] = f.y, v[2] = f.z, v[3] = f.w;
+        } else {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const bool in = KUNIT ? (row < rows && k + j < K) : (k < K && row + j < rows);
+                v[j] = in ? P[off + j] : 0.f;
+            }
+        }
+    }
+
+    __device__ __forceinline__ void store(float* s) const {  // s[16][kGlLd]
+        const int i = threadIdx.x;
+        if (KUNIT) {
+            *reinterpret_cast<float4*>(s + (i >> 4) * kGlLd + (i & 15) * 4) = make_float4(v[0], v[1], v[2], v[3]);
+        } else {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) s[((i & 3) * 4 + j) * kGlLd + (i >> 2)] = v[j];
+        }
+    }
+};
+
+template <bool A_KUNIT, bool B_KUNIT>
+__global__ __launch_bounds__(256) void gemm_f32_tiled_k64_kernel(const float* __restrict__ A, const float* __restrict__ B,
+                                                                 float* __restrict__ C, int M, int N, int K, int64_t a_ld, int64_t b_ld,
+                                                                 int64_t ldc, float alpha, int accumulate, int a_vec, int b_vec) {
+    __shared__ __attribute__((aligned(16))) float sa[16 * kGlLd];
+    __shared__ __attribute__((aligned(16))) float sb[16 * kGlLd];
+    const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;
+    const int m0 = blockIdx.y * 16, n0 = blockIdx.x * 16;
+    float acc = 0.f;
+    GlStage<A_KUNIT> ga;
+    GlStage<B_KUNIT> gb;
+    ga.load(A, M, K, a_ld, m0, 0, a_vec);
+    gb.load(B, N, K, b_ld, n0, 0, b_vec);
+    for (int k0 = 0; k0 < K; k0 += kGlK) {
+        ga.store(sa);
+        gb.store(sb);
+        __syncthreads();
+        if (k0 + kGlK < K) {
+            ga.load(A, M, K, a_ld, m0, k0 + kGlK, a_vec);
+            gb.load(B, N, K, b_ld, n0, k0 + kGlK, b_vec);
+        }
+        const int kend = K - k0 < kGlK ? (K - k0 + 15) / 16 * 16 : kGlK;  // the zero padding of the 16 x 16 kernel, no further
+        for (int kc = 0; kc < kend; kc += 16) {
+#pragma unroll
+            for (int kk = 0; kk < 16; kk += 4) {
+                const float4 a = *reinterpret_cast<const float4*>(sa + ty * kGlLd + kc + kk);
+                const float4 b = *reinterpret_cast<const float4*>(sb + tx * kGlLd + kc + kk);
+                acc = fmaf(a.x, b.x, acc);
+                acc = fmaf(a.y, b.y, acc);
+                acc = fmaf(a.z, b.z, acc);
+                acc = fmaf(a.w, b.w, acc);
+            }
+        }
+        __syncthreads();
+    }
+    const int m = m0 + ty, n = n0 + tx;
+    if (m < M && n < N) {
+        float* c = C + (int64_t)m * ldc + n;
+        *c = gemm_f32_result(accumulate ? *c : 0.f, alpha, acc, accumulate);
+    }
+}
+
+// fewer outputs than this: the 16 x 16-output instance (the large tiles would leave most of the chip idle)
+constexpr int64_t kGemmF32LargeTileOutputs = 1 << 20;
+
+void gemm_f32_tiled_k64_launch(const float* A, const float* B, float* C, int M, int N, int K, int64_t a_rs, int64_t a_cs, int64_t b_rs,
+                               int64_t b_cs, int64_t ldc, float alpha, int accumulate, hipStream_t s) {
+    const bool a_k = a_cs == 1, b_k = b_cs == 1;
+    const int64_t a_ld = a_k ? a_rs : a_cs, b_ld = b_k ? b_rs : b_cs;
+    const int a_vec = cm3p_aligned16(A) && a_ld % 4 == 0, b_vec = cm3p_aligned16(B) && b_ld % 4 == 0;
+    const dim3 grid((N + 15) / 16, (M + 15) / 16);
+#define CM3P_GL_LAUNCH(AK, BK) gemm_f32_tiled_k64_kernel<AK, BK><<<grid, 256, 0, s>>>(A, B, C, M, N, K, a_ld, b_ld, ldc, alpha, accumulate, a_vec, b_vec)
+    if (a_k && b_k) CM3P_GL_LAUNCH(true, true);
+    else if (a_k) CM3P_GL_LAUNCH(true, false);
+    else if (b_k) CM3P_GL_LAUNCH(false, true);
+    else CM3P_GL_LAUNCH(false, false);
+#undef CM3P_GL_LAUNCH
+}
+
+template <int TM, int TN>
+void gemm_f32_tiled_launch(const float* A, const float* B, float* C, int M, int N, int K, int64_t a_rs, int64_t a_cs, int64_t b_rs,
+                           int64_t b_cs, int64_t ldc, float alpha, int accumulate, hipStream_t s) {
+    const bool a_k = a_cs == 1, b_k = b_cs == 1;  // (the caller checked that the other stride is 1 where this one is not)
+    const int64_t a_ld = a_k ? a_rs : a_cs, b_ld = b_k ? b_rs : b_cs;
+    const int a_vec = cm3p_aligned16(A) && a_ld % 4 == 0, b_vec = cm3p_aligned16(B) && b_ld % 4 == 0, c_vec = cm3p_aligned16(C) && ldc % 4 == 0;
+    const dim3 grid((N + 16 * TN - 1) / (16 * TN), (M + 16 * TM - 1) / (16 * TM));
+#define CM3P_GT_LAUNCH(AK, BK) \
+    gemm_f32_tiled_kernel<TM, TN, AK, BK><<<grid, 256, 0, s>>>(A, B, C, M, N, K, a_ld, b_ld, ldc, alpha, accumulate, a_vec, b_vec, c_vec)
+    if (a_k && b_k) CM3P_GT_LAUNCH(true, true);
+    else if (a_k) CM3P_GT_LAUNCH(true, false);
+    else if (b_k) CM3P_GT_LAUNCH(false, true);
+    else CM3P_GT_LAUNCH(false, false);
+#undef CM3P_GT_LAUNCH
 }
 
 __global__ __launch_bounds__(256) void l2norm_fwd_kernel(const float* __restrict__ x, float* __restrict__ y,
@@ -424,8 +694,21 @@ int cm3p_pointwise_loss(const float* x, const float* y, float* out, float* dx, i
 int cm3p_gemm_f32(const float* A, const float* B, float* C, int M, int N, int K, int64_t a_rs, int64_t a_cs, int64_t b_rs,
                   int64_t b_cs, int64_t ldc, float alpha, int accumulate, void* stream) {
     CM3P_REQUIRE(A && B && C && M > 0 && N > 0 && K > 0 && ldc >= N);
+    CM3P_REQUIRE((accumulate & ~(1 | CM3P_GEMM_F32_TILED)) == 0);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (accumulate & CM3P_GEMM_F32_TILED) {
+        CM3P_REQUIRE((a_rs == 1 || a_cs == 1) && (b_rs == 1 || b_cs == 1));
+        // which instance runs changes no bit of the result.  Few outputs: 16 x 16 per workgroup, k by 64; else the tile follows M
+        // (N is the long side of the shapes with few rows)
+        if ((int64_t)M * N < kGemmF32LargeTileOutputs) gemm_f32_tiled_k64_launch(A, B, C, M, N, K, a_rs, a_cs, b_rs, b_cs, ldc, alpha, accumulate & 1, s);
+        else if (M <= 32) gemm_f32_tiled_launch<2, 8>(A, B, C, M, N, K, a_rs, a_cs, b_rs, b_cs, ldc, alpha, accumulate & 1, s);
+        else if (M <= 64) gemm_f32_tiled_launch<4, 4>(A, B, C, M, N, K, a_rs, a_cs, b_rs, b_cs, ldc, alpha, accumulate & 1, s);
+        else gemm_f32_tiled_launch<8, 4>(A, B, C, M, N, K, a_rs, a_cs, b_rs, b_cs, ldc, alpha, accumulate & 1, s);
+        CM3P_LAUNCH_CHECK();
+        return CM3P_OK;
+    }
     const dim3 grid((N + 15) / 16, (M + 15) / 16);
-    gemm_f32_kernel<<<grid, 256, 0, static_cast<hipStream_t>(stream)>>>(A, B, C, M, N, K, a_rs, a_cs, b_rs, b_cs, ldc, alpha, accumulate);
+    gemm_f32_kernel<<<grid, 256, 0, s>>>(A, B, C, M, N, K, a_rs, a_cs, b_rs, b_cs, ldc, alpha, accumulate);
     CM3P_LAUNCH_CHECK();
     return CM3P_OK;
 }

@@ -214,7 +214,27 @@ def check_attention_hd(isa: str):
         _need("v_mfma_f32_32x32x16_bf16" in next(iter(body.values())), f"{sym}: no v_mfma_f32_32x32x16_bf16")
 
 
-CHECKS = {"gemm8p.hip": check_gemm8p, "attention_fwd.hip": check_attention_fwd, "attention_bwd_fused.hip": check_attention_bwd_fused,
+# ------------------------------------------------------------------------------------------------ head.hip
+def check_head(isa: str):
+    """The tiled fp32 GEMMs of head.hip.  gemm_f32_tiled_kernel keeps a thread's TM x TN accumulators, its operand fragments and the
+    next k tile's staged loads in registers; gemm_f32_tiled_k64_kernel its staged loads.  A spill would put scratch traffic into the
+    fma loop.  Nothing in them counts on an instruction pattern, so only these figures are checked: all sixteen instances (three
+    tiles and the 16 x 16-output, k-by-64 form, each in four operand forms) exist and are built without a spill or a private segment."""
+    descs = {}
+    for m in re.finditer(r"^\s*\.name:\s*(\S*gemm_f32_tiled_(?:kernelILi(\d+)ELi(\d+)E|k64_kernelI)Lb([01])ELb([01])E\S*)\s*$", isa, re.M):
+        start = isa.rfind("\n  - ", 0, m.start())
+        end = isa.find("\n  - ", m.end())
+        descs[tuple(int(g or 1) for g in m.groups()[1:])] = (m.group(1), isa[start:end if end >= 0 else len(isa)])
+    want = {(tm, tn, a, b) for tm, tn in ((1, 1), (2, 8), (4, 4), (8, 4)) for a in (0, 1) for b in (0, 1)}  # (1, 1): the k-by-64 form
+    _need(set(descs) == want, f"head.hip: tiled fp32 GEMM descriptors found for {sorted(descs)}, expected {sorted(want)}")
+    for (tm, tn, _, _), (sym, desc) in sorted(descs.items()):
+        for key in ("vgpr_spill_count", "private_segment_fixed_size"):
+            m = re.search(r"\." + key + r":\s*(\d+)", desc)
+            _need(m is not None, f"{sym}: no .{key} in the kernel descriptor")
+            _need(int(m.group(1)) == 0, f"{sym}: {key} = {m.group(1)} (the {tm} x {tn} outputs of a thread and its staged loads must stay in registers)")
+
+
+CHECKS = {"head.hip": check_head, "gemm8p.hip": check_gemm8p, "attention_fwd.hip": check_attention_fwd, "attention_bwd_fused.hip": check_attention_bwd_fused,
           "attention_hd.hip": check_attention_hd}
 
 

@@ -11,7 +11,7 @@ from typing import Optional
 import torch
 
 from . import _lib
-from ._lib import ADD_A_BF16, BF16, POOL_PACKED, EPI_BF16, EPI_BF16_RESID, EPI_F32, EPI_F32_RESID, F32, call, dt, ptr, query, stream
+from ._lib import ADD_A_BF16, BF16, GEMM_F32_TILED, POOL_PACKED, EPI_BF16, EPI_BF16_RESID, EPI_F32, EPI_F32_RESID, F32, call, dt, ptr, query, stream
 
 Tensor = torch.Tensor
 
@@ -747,12 +747,31 @@ def pool_bwd(dpooled: Tensor, mask: Optional[Tensor], count: Optional[Tensor], B
 
 
 # ------------------------------------------------------------------------------------------------ fp32 head
+# Route of cm3p_gemm_f32 (both give the same bits, so this is a choice of speed alone): the tiled kernels from
+# GEMM_F32_TILED_MIN_OUTPUTS outputs (M * N) on, the 16 x 16 kernel below.  Measured on one MI355X (profiles/gemm_f32_tiled.txt) the
+# tiled route was faster or equal at every shape of the head, down to the 32 x 32 local head and 8 x 2048 logits, and found no
+# crossover: behind the flag the entry point itself takes 16 x 16 outputs per workgroup with k in tiles of 64 for problems of fewer
+# than 2^20 outputs (k is never split, so those cannot fill the chip with large tiles) and 32..128 x 64..128 register tiles from
+# there on.  1024 outputs is the local head at b = 32; smaller, launch-bound calls (probes at 8 x 8 and 16 x 16 were 5-8 us faster on
+# the tiled route too) stay on the kernel they have always run on.
+# Tests set the constant to 0 (tiled wherever the operands allow it) or to a huge value (never).
+GEMM_F32_TILED_MIN_OUTPUTS = 1024
+GEMM_F32_TAGS = {False: "cm3p_gemm_f32 [16x16]", True: "cm3p_gemm_f32 [tiled]"}
+
+
+def gemm_f32_route(M: int, N: int, a_strides, b_strides) -> bool:
+    """True: the tiled kernel.  Decided from the shape and the strides only, never from the data."""
+    unit = 1 in tuple(a_strides) and 1 in tuple(b_strides)  # the tiled kernel needs a unit stride in each operand
+    return unit and M * N >= GEMM_F32_TILED_MIN_OUTPUTS
+
+
 def gemm_f32(a: Tensor, b: Tensor, M: int, N: int, K: int, a_strides, b_strides, alpha: float = 1.0,
              out: Optional[Tensor] = None, accumulate: bool = False) -> Tensor:
     if out is None:
         out = torch.empty((M, N), dtype=torch.float32, device=a.device)
+    tiled = gemm_f32_route(M, N, a_strides, b_strides)
     call("cm3p_gemm_f32", ptr(a), ptr(b), ptr(out), M, N, K, a_strides[0], a_strides[1], b_strides[0], b_strides[1], N, alpha,
-         int(accumulate), stream())
+         int(bool(accumulate)) | (GEMM_F32_TILED if tiled else 0), stream(), tag=GEMM_F32_TAGS[tiled], work=2.0 * M * N * K)
     return out
 
 

@@ -412,7 +412,15 @@ int cm3p_pool_bwd(const float* dpooled, const int64_t* mask, const float* count,
 /* ---------------------------------------------------------------------------------------------------------------
  * Contrastive head, fp32 throughout (ref:cm3p/modeling_cm3p.py:27-62, 958-985).
  */
-/* C[m, n] (+)= alpha * sum_k A[m*a_rs + k*a_cs] * B[n*b_rs + k*b_cs]; generic strides, small problems only. */
+/* C[m, n] (+)= alpha * sum_k A[m*a_rs + k*a_cs] * B[n*b_rs + k*b_cs], the sum as one chain of fmaf in ascending k (k padded with
+ * zero operands to a multiple of 16), C[m, n] = accumulate ? C[m, n] + alpha * sum : alpha * sum; columns N .. ldc-1 are not touched.
+ * `accumulate`: bit 0 = add to C.  Bit 1 = CM3P_GEMM_F32_TILED selects the kernel: without it 16 x 16 outputs per workgroup, one per
+ * thread, k in tiles of 16, any strides.  With it the tiled kernels, written for the variation-sized problems of the head: from
+ * 2^20 outputs on a register-tiled kernel (up to 128 x 64 outputs per workgroup, up to 8 x 4 per thread), below that 16 x 16
+ * outputs per workgroup with k in tiles of 64 and the next tile in flight (k is never split, so few outputs cannot fill the chip
+ * with large tiles).  They need every operand to have a unit stride (a_rs == 1 or a_cs == 1, b_rs == 1 or b_cs == 1; else
+ * CM3P_ERR_INVALID).  All kernels give the same bits on the same arguments.  Any other bit of `accumulate`: CM3P_ERR_INVALID. */
+#define CM3P_GEMM_F32_TILED 2
 int cm3p_gemm_f32(const float* A, const float* B, float* C, int M, int N, int K, int64_t a_rs, int64_t a_cs, int64_t b_rs,
                   int64_t b_cs, int64_t ldc, float alpha, int accumulate, void* stream);
 /* y = x / sqrt(sum x^2) per row, no eps (_get_vector_norm, ref:cm3p/modeling_cm3p.py:54-62,960,972); norm[rows] saved. */
