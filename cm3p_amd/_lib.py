@@ -17,7 +17,7 @@ ADD_A_BF16 = 16  # cm3p_add_f32: or-ed into b_dtype when the first operand (and 
 POOL_PACKED = 2  # cm3p_pool_fwd / cm3p_pool_bwd: or-ed into cls when the rows are packed and `mask` carries their int32 cu_seqlens
 GEMM_F32_TILED = 2  # cm3p_gemm_f32: or-ed into accumulate to run the register-tiled kernel (same bits; operands need a unit stride)
 EPI_BF16, EPI_F32, EPI_F32_RESID, EPI_F32_BIAS, EPI_BF16_RESID = 0, 1, 2, 5, 7
-ABI_VERSION = 19
+ABI_VERSION = 20
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("CM3P_HIP_LIB") or os.path.join(_HERE, "csrc", "libcm3p_hip.so")  # env override: kernel experiments
@@ -41,6 +41,7 @@ SIGNATURES = {
     "cm3p_gemm_bf16": [_P, _P, _P, _P, _L, _L, _L, _L, _L, _L, _I, _I, _I, _I, _P, _P],
     "cm3p_qkv_gemm_rope": [_P, _P, _P, _L, _L, _L, _P, _P, _I, _I, _I, _F, _P],
     "cm3p_gemm_wgrad_splits": [_L, _L, _L],
+    "cm3p_gemm_route": [_L, _L, _L, _L, _L, _I, _I, _I, _I, _I, _I],
     "cm3p_gemm8p_set_grid": [_I],
     "cm3p_gemm8p_get_grid": [],
     "cm3p_build_ablation_flags": [],
@@ -150,7 +151,8 @@ def load() -> ctypes.CDLL:
 
 def _check(rc: int, name: str):
     if rc != 0:
-        raise Cm3pHipError(f"{name} failed with code {rc} ({'invalid argument' if rc == -1 else 'launch failure'})")
+        what = {-1: "invalid argument", -2: "launch failure"}.get(rc, "internal dispatch error")
+        raise Cm3pHipError(f"{name} failed with code {rc} ({what})")
 
 
 class _DevPtr(int):

@@ -6,6 +6,7 @@
 #include <atomic>
 #include <initializer_list>
 #include <mutex>
+#include <type_traits>
 
 #include "../../include/cm3p_hip.h"
 
@@ -259,6 +260,58 @@ struct RopeArgs {
     int q_cols = 0;
     float q_scale = 1.f;
 };
+
+// ---- the bf16 GEMM family on the host: one call, one route, one instance -------------------------------------------------------
+// Where a call lands: decided once by cm3p_gemm_route_of (gemm.hip, the only statement of the rule) and carried to the launchers.
+enum { CM3P_GEMM_128 = 0, CM3P_GEMM_256 = 1, CM3P_GEMM_RING = 2 };  // gemm_bf16_kernel, gemm256_kernel, gemm8p_kernel
+struct GemmRoute {
+    int kernel;      // CM3P_GEMM_*; negative: the entry point refuses the call
+    bool rebal;      // 256 x 256 routes: every work item has an even number of k-tiles (the ring's REBAL instances)
+    int splits;      // the k-split count the library uses (recomputed from the one requested)
+    int64_t kchunk;  // contraction length of one split (K when splits == 1)
+};
+// What an entry point hands to a launcher; the pointers are never read on the host.
+struct GemmCall {
+    const void* A;
+    const void* B;
+    void* C;
+    const float* R;
+    int64_t M, N, K, lda, ldb, ldc;
+    int a_kc, b_kc, epi;
+    int64_t c_split_stride = 0;  // elements between the fp32 partial slabs of a k-split
+    RopeArgs rope = RopeArgs{};
+    BatchArgs bt = BatchArgs{};
+    int batch = 0;  // > 0: a strided batch of that many matrices (CM3P_EPI_BF16_AXPBY)
+};
+// A run-time flag or epilogue number as a compile-time constant handed to a callable that returns an error code.  Each kernel file
+// states which (layout, epilogue) pairs it instantiates (its has_instance) and answers CM3P_ERR_INTERNAL for the others.
+template <class F>
+int cm3p_with_flag(bool v, F&& f) {
+    return v ? f(std::true_type{}) : f(std::false_type{});
+}
+template <class F>
+int cm3p_with_layout(bool a_kc, bool b_kc, F&& f) {
+    return cm3p_with_flag(a_kc, [&](auto ak) { return cm3p_with_flag(b_kc, [&](auto bk) { return f(ak, bk); }); });
+}
+template <class F>
+int cm3p_with_epilogue(int epi, F&& f) {
+    switch (epi) {
+        case CM3P_EPI_BF16: return f(std::integral_constant<int, CM3P_EPI_BF16>{});
+        case CM3P_EPI_F32: return f(std::integral_constant<int, CM3P_EPI_F32>{});
+        case CM3P_EPI_F32_RESID: return f(std::integral_constant<int, CM3P_EPI_F32_RESID>{});
+        case CM3P_EPI_BF16_ROPE: return f(std::integral_constant<int, CM3P_EPI_BF16_ROPE>{});
+        case CM3P_EPI_BF16_AXPBY: return f(std::integral_constant<int, CM3P_EPI_BF16_AXPBY>{});
+        case CM3P_EPI_F32_BIAS: return f(std::integral_constant<int, CM3P_EPI_F32_BIAS>{});
+        case CM3P_EPI_BF16_GEGLU: return f(std::integral_constant<int, CM3P_EPI_BF16_GEGLU>{});
+        case CM3P_EPI_BF16_RESID: return f(std::integral_constant<int, CM3P_EPI_BF16_RESID>{});
+        default: return CM3P_ERR_INTERNAL;
+    }
+}
+// (layout, epilogue) pairs that exist in all three kernels or in none: the rotary, bias and GeGLU epilogues are written for the
+// forward orientation only
+constexpr bool cm3p_gemm_pair_exists(bool a_kc, bool b_kc, int epi) {
+    return (epi != CM3P_EPI_BF16_ROPE && epi != CM3P_EPI_F32_BIAS && epi != CM3P_EPI_BF16_GEGLU) || (a_kc && b_kc);
+}
 
 // a = head dims [d, d+3], b = head dims [d+32, d+35] of one token (d < 32): rotate_half convention
 // (TF:models/modernbert/modeling_modernbert.py:188-219).  INVERSE applies the transpose (backward pass).

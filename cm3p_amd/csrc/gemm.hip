@@ -16,6 +16,13 @@
 //                            ds_read_b64_tr_b16 (hardware transpose), conflict free per 32-lane half.
 // The MFMA takes the B fragment as its first operand, so an accumulator lane holds 4 consecutive n of one m:
 // C is written with 8-byte (bf16) / 16-byte (fp32) stores and the residual R is read the same way.
+//
+// This file also holds the family's four launching entry points (cm3p_gemm_bf16, cm3p_qkv_gemm_rope, cm3p_gemm_geglu,
+// cm3p_gemm_bf16_batched) and the one routing rule they share, cm3p_gemm_route_of: it decides between this kernel, gemm256.hip
+// and gemm8p.hip (and the ring's instance) and is the only reader of CM3P_GEMM_IMPL and CM3P_G8P_REBAL.  An entry point checks its
+// arguments, computes the route and launches what it says; no launcher refuses a shape and nothing falls back.
+#include <stdlib.h>
+
 #include "common.h"
 
 namespace {
@@ -224,85 +231,109 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restr
     }
 }
 
-template <bool A_KC, bool B_KC>
-int launch(const void* A, const void* B, void* C, const float* R, int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb,
-           int64_t ldc, int epi, int splits, int64_t kchunk, int64_t c_split_stride, hipStream_t s, RopeArgs rope = RopeArgs{},
-           BatchArgs bt = BatchArgs{}, int batch = 1) {
-    const int tiles_m = (int)((M + BM - 1) / BM), tiles_n = (int)((N + BN - 1) / BN);
-    const dim3 grid(tiles_m * tiles_n, batch, splits);
+// the pairs this file instantiates: every layout with the plain and AXPBY epilogues, the forward layout with the rotary and bias ones
+template <bool A_KC, bool B_KC, int EPI>
+constexpr bool has_instance = cm3p_gemm_pair_exists(A_KC, B_KC, EPI) && EPI != CM3P_EPI_BF16_GEGLU;
+
+int launch128(const GemmRoute& r, const GemmCall& g, hipStream_t s) {
+    const int tiles_m = (int)((g.M + BM - 1) / BM), tiles_n = (int)((g.N + BN - 1) / BN);
+    const dim3 grid(tiles_m * tiles_n, g.batch > 0 ? g.batch : 1, r.splits);
     const size_t lds = 4 * kStageBytes;
-    const uint16_t* a = static_cast<const uint16_t*>(A);
-    const uint16_t* b = static_cast<const uint16_t*>(B);
-    switch (epi) {
-        case CM3P_EPI_BF16:
-            gemm_bf16_kernel<A_KC, B_KC, CM3P_EPI_BF16><<<grid, 256, lds, s>>>(a, b, C, R, M, N, K, lda, ldb, ldc, tiles_n, kchunk, c_split_stride, rope, bt);
-            break;
-        case CM3P_EPI_F32:
-            gemm_bf16_kernel<A_KC, B_KC, CM3P_EPI_F32><<<grid, 256, lds, s>>>(a, b, C, R, M, N, K, lda, ldb, ldc, tiles_n, kchunk, c_split_stride, rope, bt);
-            break;
-        case CM3P_EPI_F32_RESID:
-            gemm_bf16_kernel<A_KC, B_KC, CM3P_EPI_F32_RESID><<<grid, 256, lds, s>>>(a, b, C, R, M, N, K, lda, ldb, ldc, tiles_n, kchunk, c_split_stride, rope, bt);
-            break;
-        case CM3P_EPI_BF16_RESID:
-            gemm_bf16_kernel<A_KC, B_KC, CM3P_EPI_BF16_RESID><<<grid, 256, lds, s>>>(a, b, C, R, M, N, K, lda, ldb, ldc, tiles_n, kchunk, c_split_stride, rope, bt);
-            break;
-        case CM3P_EPI_BF16_ROPE:
-            if constexpr (A_KC && B_KC) {
-                gemm_bf16_kernel<true, true, CM3P_EPI_BF16_ROPE><<<grid, 256, lds, s>>>(a, b, C, R, M, N, K, lda, ldb, ldc, tiles_n, kchunk, c_split_stride, rope, bt);
-                break;
+    const uint16_t* a = static_cast<const uint16_t*>(g.A);
+    const uint16_t* b = static_cast<const uint16_t*>(g.B);
+    return cm3p_with_layout(g.a_kc, g.b_kc, [&](auto ak, auto bk) {
+        return cm3p_with_epilogue(g.epi, [&](auto e) {
+            constexpr bool AK = decltype(ak)::value, BK = decltype(bk)::value;
+            constexpr int E = decltype(e)::value;
+            if constexpr (has_instance<AK, BK, E>) {
+                gemm_bf16_kernel<AK, BK, E><<<grid, 256, lds, s>>>(a, b, g.C, g.R, g.M, g.N, g.K, g.lda, g.ldb, g.ldc, tiles_n, r.kchunk,
+                                                                 g.c_split_stride, g.rope, g.bt);
+                return CM3P_OK;
+            } else {
+                return CM3P_ERR_INTERNAL;
             }
-            return CM3P_ERR_INVALID;
-        case CM3P_EPI_F32_BIAS:
-            if constexpr (A_KC && B_KC) {
-                gemm_bf16_kernel<true, true, CM3P_EPI_F32_BIAS><<<grid, 256, lds, s>>>(a, b, C, R, M, N, K, lda, ldb, ldc, tiles_n, kchunk, c_split_stride, rope, bt);
-                break;
-            }
-            return CM3P_ERR_INVALID;
-        case CM3P_EPI_BF16_AXPBY:
-            gemm_bf16_kernel<A_KC, B_KC, CM3P_EPI_BF16_AXPBY><<<grid, 256, lds, s>>>(a, b, C, R, M, N, K, lda, ldb, ldc, tiles_n, kchunk, c_split_stride, rope, bt);
-            break;
-        default:
-            return CM3P_ERR_INVALID;
-    }
-    return CM3P_OK;
+        });
+    });
 }
 
 }  // namespace
 
-// gemm256.hip: the 256 x 256 LDS-DMA kernel for the big shapes
-int cm3p_gemm256_dispatch(const void* A, const void* B, void* C, const float* R, int64_t M, int64_t N, int64_t K, int64_t lda,
-                          int64_t ldb, int64_t ldc, int a_kc, int b_kc, int epi, int splits, int64_t kchunk,
-                          int64_t c_split_stride, hipStream_t s, RopeArgs rope);
-
-// gemm8p.hip: the same tile on the half-tile ring ("8-phase" schedule); CM3P_ERR_INVALID = shape / layout not covered
-int cm3p_gemm8p_dispatch(const void* A, const void* B, void* C, const float* R, int64_t M, int64_t N, int64_t K, int64_t lda,
-                         int64_t ldb, int64_t ldc, int a_kc, int b_kc, int epi, int splits, int64_t kchunk,
-                         int64_t c_split_stride, hipStream_t s, RopeArgs rope, BatchArgs bt = BatchArgs{}, int batch = 0);
-
-// Development switch (read per call so that one process can A/B): CM3P_GEMM_IMPL=256 keeps the r01 kernel for every big shape.
-static inline bool use_8p() {
-    const char* e = getenv("CM3P_GEMM_IMPL");
-    return !(e && e[0] == '2');
-}
-
-// CM3P_GEMM_IMPL=128: the 128 x 128 kernel (two to three workgroups per CU) for every shape - an A/B partner for shapes whose
-// epilogue dominates (tools/gemm_ab.py)
-static inline bool use_small_only() {
-    const char* e = getenv("CM3P_GEMM_IMPL");
-    return e && e[0] == '1';
-}
-
-static inline int big_gemm(const void* A, const void* B, void* C, const float* R, int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb,
-                           int64_t ldc, int a_kc, int b_kc, int epi, int splits, int64_t kchunk, int64_t c_split_stride, hipStream_t s,
-                           RopeArgs rope) {
-    if (use_8p()) {
-        const int rc = cm3p_gemm8p_dispatch(A, B, C, R, M, N, K, lda, ldb, ldc, a_kc, b_kc, epi, splits, kchunk, c_split_stride, s, rope);
-        if (rc != CM3P_ERR_INVALID) return rc;
-    }
-    return cm3p_gemm256_dispatch(A, B, C, R, M, N, K, lda, ldb, ldc, a_kc, b_kc, epi, splits, kchunk, c_split_stride, s, rope);
-}
+// gemm256.hip: the 256 x 256 LDS-DMA kernel; gemm8p.hip: the same tile on the half-tile ring ("8-phase" schedule).  Both launch the
+// instance the route names and decide nothing themselves.
+int cm3p_gemm256_dispatch(const GemmRoute& r, const GemmCall& g, hipStream_t s);
+int cm3p_gemm8p_dispatch(const GemmRoute& r, const GemmCall& g, hipStream_t s);
 
 static inline int64_t tiles_of(int64_t M, int64_t N, int t) { return ((M + t - 1) / t) * ((N + t - 1) / t); }
+// work items of 256 x 256 from which a call occupies the chip: (tile, k-split) items of a plain call, (matrix, tile) items of a batch
+constexpr int64_t kBigItems = 200, kBigBatchItems = 128;
+
+// THE routing rule of the bf16 GEMM family: which kernel and instance a call lands on, from its shape facts alone (no HIP call, no
+// pointer).  Every launching entry point below computes it and launches what it says; cm3p_gemm_route reports it (profiler tags,
+// tests).  `epi` is the internal epilogue number; rope_cols belongs to CM3P_EPI_BF16_ROPE, batch > 0 to CM3P_EPI_BF16_AXPBY.
+//   128 x 128 (gemm_bf16_kernel): every shape no rule below sends elsewhere.
+//   256 x 256: K and the k-split length multiples of 64 and enough work items to occupy the chip - 200 (tile, split) items of a plain
+//     call, 128 (matrix, tile) items of a batch whose tiles are at least 0.7 full (edge tiles compute their padding: [520 x 264] x 30
+//     ran at 0.59 of the small kernel).  The rotary epilogue decides per tile whether its columns are rotated, so the rotated range
+//     must end on a tile boundary, and its table row arithmetic is 32-bit (M < 2^31).
+//   of the two 256 x 256 kernels the ring (gemm8p_kernel) where it can run: M and N multiples of 8 (it clamps whole 16-byte pieces)
+//     and 16 rows of either operand inside its 32-bit lane offsets; gemm256_kernel otherwise.  A batch has the ring only (in the three
+//     layouts of the Muon step) and the GeGLU epilogue has the ring only: a call outside cm3p_gemm_geglu's shapes is refused.
+//   REBAL (the ring's instances that read B-lo one phase early): every work item has an even number of 64-deep k-tiles.
+// Development switches.  CM3P_GEMM_IMPL, read on every call so that one process can A/B: 256 = gemm256_kernel (the r01 kernel) in
+// place of the ring - a batch then runs on the 128 x 128 kernel and a GeGLU route names gemm256_kernel, which tells the caller to
+// keep its two-kernel path; 128 = the 128 x 128 kernel for every plain and rotary call (an A/B partner for shapes whose epilogue
+// dominates, tools/gemm_ab.py).  CM3P_G8P_REBAL=0, read once per process: the plain ring instances only.
+static GemmRoute cm3p_gemm_route_of(int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb, bool a_kc, bool b_kc, int epi,
+                                    int split_k, int rope_cols, int batch) {
+    GemmRoute r{CM3P_GEMM_128, false, 1, K};
+    const bool batched = epi == CM3P_EPI_BF16_AXPBY;
+    if (M <= 0 || N <= 0 || K <= 0 || split_k < 1 || epi < 0 || epi > CM3P_EPI_BF16_RESID || batched != (batch > 0) ||
+        !cm3p_gemm_pair_exists(a_kc, b_kc, epi)) {
+        r.kernel = CM3P_ERR_INVALID;
+        return r;
+    }
+    const char* impl = getenv("CM3P_GEMM_IMPL");
+    const bool no_ring = impl && impl[0] == '2', small_only = impl && impl[0] == '1';
+    static const bool no_rebal = [] { const char* e = getenv("CM3P_G8P_REBAL"); return e && e[0] == '0'; }();
+    if (split_k > 1) {
+        // k-split length: a multiple of 128 where K allows it, so that every work item has an even number of 64-deep k-tiles
+        // (REBAL needs that) - the last split absorbs the remainder, itself a multiple of 128 then
+        const int64_t q = (K % 128 == 0) ? 128 : 64;
+        r.kchunk = ((K + split_k - 1) / split_k + q - 1) / q * q;
+        r.splits = (int)((K + r.kchunk - 1) / r.kchunk);
+    }
+    const int64_t items = tiles_of(M, N, 256) * (batched ? batch : r.splits);
+    const bool ring_ok = M % 8 == 0 && N % 8 == 0 && lda * 16 < (int64_t(1) << 31) && ldb * 16 < (int64_t(1) << 31);
+    bool big = K % 64 == 0 && r.kchunk % 64 == 0 && items >= (batched ? kBigBatchItems : kBigItems);
+    if (epi == CM3P_EPI_BF16_GEGLU) {
+        if (!(big && N % 64 == 0 && ring_ok)) r.kernel = CM3P_ERR_INVALID;  // (N = 2 I, I a multiple of 32)
+        else r.kernel = no_ring ? CM3P_GEMM_256 : CM3P_GEMM_RING;
+    } else if (batched) {
+        const bool filled = M * N * batch * 10 >= items * 65536 * 7;
+        big = big && filled && (a_kc || !b_kc) && ring_ok && !no_ring;
+        if (big) r.kernel = CM3P_GEMM_RING;
+    } else {
+        big = big && !small_only;
+        if (epi == CM3P_EPI_BF16_ROPE) big = big && rope_cols % 256 == 0 && M < (int64_t(1) << 31);
+        if (big) r.kernel = (ring_ok && !no_ring) ? CM3P_GEMM_RING : CM3P_GEMM_256;
+    }
+    if (r.kernel > CM3P_GEMM_128) {
+        const int64_t last = K - (int64_t)(r.splits - 1) * r.kchunk;  // (the last k-split may be shorter)
+        r.rebal = !no_rebal && (r.kchunk / 64) % 2 == 0 && (last / 64) % 2 == 0;
+    }
+    return r;
+}
+
+// route, then launch exactly what it says (the route of a GeGLU call under CM3P_GEMM_IMPL=256 excepted: see cm3p_gemm_geglu)
+static int run_routed(const GemmRoute& r, const GemmCall& g, hipStream_t s) {
+    int rc = CM3P_ERR_INVALID;
+    if (r.kernel == CM3P_GEMM_RING) rc = cm3p_gemm8p_dispatch(r, g, s);
+    else if (r.kernel == CM3P_GEMM_256) rc = cm3p_gemm256_dispatch(r, g, s);
+    else if (r.kernel == CM3P_GEMM_128) rc = launch128(r, g, s);
+    if (rc != CM3P_OK) return rc;
+    CM3P_LAUNCH_CHECK();
+    return CM3P_OK;
+}
 
 int cm3p_ablation_flags_attention();
 int cm3p_ablation_flags_attention_bwd_fused();
@@ -346,7 +377,7 @@ int cm3p_gemm_wgrad_splits(int64_t M, int64_t N, int64_t K) {
         int64_t s = 256 / t256;  // one 512-thread workgroup per CU, all resident in a single wave of the grid
         if (s > K / 2048) s = K / 2048;
         if (s < 1) s = 1;
-        if (t256 * s >= 200) return (int)s;
+        if (t256 * s >= kBigItems) return (int)s;
     }
     const int64_t t128 = tiles_of(M, N, 128);
     if (t128 >= 512 || K <= 1024) return 1;
@@ -355,30 +386,30 @@ int cm3p_gemm_wgrad_splits(int64_t M, int64_t N, int64_t K) {
     return (int)(s < 1 ? 1 : s);
 }
 
+int cm3p_gemm_route(int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb, int a_kc, int b_kc, int epilogue, int split_k,
+                    int rope_cols, int batch) {
+    const GemmRoute r = cm3p_gemm_route_of(M, N, K, lda, ldb, a_kc != 0, b_kc != 0, epilogue, split_k, rope_cols, batch);
+    return r.kernel < 0 ? CM3P_ERR_INVALID : (r.kernel | (r.rebal ? 4 : 0) | r.splits << 3);
+}
+
 int cm3p_qkv_gemm_rope(const void* x, const void* Wqkv, void* qkv, int64_t M, int64_t N, int64_t K, const float* cos_tab,
                        const float* sin_tab, int S, int per_batch, int rope_cols, float q_scale, void* stream) {
     CM3P_REQUIRE(x && Wqkv && qkv && cos_tab && sin_tab && M > 0 && N > 0 && K > 0 && S > 0);
     CM3P_REQUIRE(cm3p_aligned16(x) && cm3p_aligned16(Wqkv) && cm3p_aligned16(qkv) && cm3p_aligned16(cos_tab) && cm3p_aligned16(sin_tab));
     CM3P_REQUIRE(K % 8 == 0 && N % 64 == 0 && rope_cols % 64 == 0 && rope_cols >= 0 && rope_cols <= N);
     CM3P_REQUIRE(per_batch || M % S == 0);
-    hipStream_t s = static_cast<hipStream_t>(stream);
     CM3P_REQUIRE(q_scale > 0.f && rope_cols % 2 == 0);
-    const RopeArgs rope{cos_tab, sin_tab, S, per_batch, rope_cols, rope_cols / 2, q_scale};
-    // (the 256 x 256 kernel decides per tile whether its columns are rotated: the rotated range must end on a tile boundary)
-    const bool big = (K % 64 == 0) && (rope_cols % 256 == 0) && M < (int64_t(1) << 31) && tiles_of(M, N, 256) >= 200 && !use_small_only();
-    int rc;
-    if (big) rc = big_gemm(x, Wqkv, qkv, nullptr, M, N, K, K, K, N, 1, 1, CM3P_EPI_BF16_ROPE, 1, K, 0, s, rope);
-    else rc = launch<true, true>(x, Wqkv, qkv, nullptr, M, N, K, K, K, N, CM3P_EPI_BF16_ROPE, 1, K, 0, s, rope);
-    if (rc != CM3P_OK) return rc;
-    CM3P_LAUNCH_CHECK();
-    return CM3P_OK;
+    const GemmRoute r = cm3p_gemm_route_of(M, N, K, K, K, true, true, CM3P_EPI_BF16_ROPE, 1, rope_cols, 0);
+    CM3P_REQUIRE(r.kernel >= 0);
+    GemmCall g{x, Wqkv, qkv, nullptr, M, N, K, K, K, N, 1, 1, CM3P_EPI_BF16_ROPE};
+    g.rope = RopeArgs{cos_tab, sin_tab, S, per_batch, rope_cols, rope_cols / 2, q_scale};
+    return run_routed(r, g, static_cast<hipStream_t>(stream));
 }
 
 int cm3p_gemm_bf16(const void* A, const void* B, void* C, const float* R, int64_t M, int64_t N, int64_t K, int64_t lda,
                    int64_t ldb, int64_t ldc, int a_kc, int b_kc, int epilogue, int split_k, float* workspace, void* stream) {
     CM3P_REQUIRE(A && B && C && M > 0 && N > 0 && K > 0);
-    CM3P_REQUIRE((epilogue >= CM3P_EPI_BF16 && epilogue <= CM3P_EPI_F32_RESID) || (epilogue == CM3P_EPI_F32_BIAS && a_kc && b_kc) ||
-                 epilogue == CM3P_EPI_BF16_RESID);
+    CM3P_REQUIRE((epilogue >= CM3P_EPI_BF16 && epilogue <= CM3P_EPI_F32_RESID) || epilogue == CM3P_EPI_F32_BIAS || epilogue == CM3P_EPI_BF16_RESID);
     CM3P_REQUIRE(cm3p_aligned16(A) && cm3p_aligned16(B) && cm3p_aligned16(C));
     CM3P_REQUIRE(lda % 8 == 0 && ldb % 8 == 0 && ldc % 4 == 0 && N % 4 == 0);
     CM3P_REQUIRE(a_kc ? (K % 8 == 0 && lda >= K) : (M % 8 == 0 && lda >= M));
@@ -387,35 +418,21 @@ int cm3p_gemm_bf16(const void* A, const void* B, void* C, const float* R, int64_
     CM3P_REQUIRE((epilogue != CM3P_EPI_F32_RESID && epilogue != CM3P_EPI_F32_BIAS && epilogue != CM3P_EPI_BF16_RESID) || (R && cm3p_aligned16(R)));
     CM3P_REQUIRE(epilogue != CM3P_EPI_BF16_RESID || (N % 8 == 0 && ldc % 8 == 0));  // (16-byte bf16 row chunks in the 256 x 256 kernels)
     CM3P_REQUIRE(split_k >= 1 && (split_k == 1 || (epilogue == CM3P_EPI_F32 && workspace && cm3p_aligned16(workspace) && ldc == N)));
+    const GemmRoute r = cm3p_gemm_route_of(M, N, K, lda, ldb, a_kc != 0, b_kc != 0, epilogue, split_k, 0, 0);
+    CM3P_REQUIRE(r.kernel >= 0);  // (the bias epilogue exists in the forward layout only)
     hipStream_t s = static_cast<hipStream_t>(stream);
-    int64_t kchunk = K;
-    void* out = C;
-    int64_t split_stride = 0;
-    if (split_k > 1) {
-        // k-split length: a multiple of 128 where K allows it, so that every work item has an even number of 64-deep k-tiles
-        // (gemm8p.hip's REBAL instances need that) - the last split absorbs the remainder, itself a multiple of 128 then
-        const int64_t q = (K % 128 == 0) ? 128 : BK;
-        kchunk = ((K + split_k - 1) / split_k + q - 1) / q * q;
-        split_k = (int)((K + kchunk - 1) / kchunk);
+    GemmCall g{A, B, C, R, M, N, K, lda, ldb, ldc, a_kc != 0, b_kc != 0, epilogue};
+    if (r.splits > 1) {
+        g.C = workspace;
+        g.c_split_stride = M * N;
     }
-    if (split_k > 1) {
-        out = workspace;
-        split_stride = M * N;
-    }
-    int rc;
-    const bool big = (K % 64 == 0) && (kchunk % 64 == 0) && tiles_of(M, N, 256) * split_k >= 200 && !use_small_only();
-    if (big) rc = big_gemm(A, B, out, R, M, N, K, lda, ldb, ldc, a_kc, b_kc, epilogue, split_k, kchunk, split_stride, s, RopeArgs{});
-    else if (a_kc && b_kc) rc = launch<true, true>(A, B, out, R, M, N, K, lda, ldb, ldc, epilogue, split_k, kchunk, split_stride, s);
-    else if (a_kc) rc = launch<true, false>(A, B, out, R, M, N, K, lda, ldb, ldc, epilogue, split_k, kchunk, split_stride, s);
-    else if (b_kc) rc = launch<false, true>(A, B, out, R, M, N, K, lda, ldb, ldc, epilogue, split_k, kchunk, split_stride, s);
-    else rc = launch<false, false>(A, B, out, R, M, N, K, lda, ldb, ldc, epilogue, split_k, kchunk, split_stride, s);
+    const int rc = run_routed(r, g, s);
     if (rc != CM3P_OK) return rc;
-    CM3P_LAUNCH_CHECK();
-    if (split_k > 1) {
+    if (r.splits > 1) {
         const int64_t n4 = M * N / 4;
         int64_t blocks = (n4 + 255) / 256;
         if (blocks > 2048) blocks = 2048;
-        splitk_reduce_kernel<<<(int)blocks, 256, 0, s>>>(workspace, static_cast<float*>(C), n4, split_k, n4);
+        splitk_reduce_kernel<<<(int)blocks, 256, 0, s>>>(workspace, static_cast<float*>(C), n4, r.splits, n4);
         CM3P_LAUNCH_CHECK();
     }
     return CM3P_OK;
@@ -424,13 +441,13 @@ int cm3p_gemm_bf16(const void* A, const void* B, void* C, const float* R, int64_
 int cm3p_gemm_geglu(const void* x, const void* w_interleaved, void* a, int64_t T, int64_t I, int64_t K, void* stream) {
     CM3P_REQUIRE(x && w_interleaved && a && T > 0 && I > 0 && K > 0);
     CM3P_REQUIRE(cm3p_aligned16(x) && cm3p_aligned16(w_interleaved) && cm3p_aligned16(a));
-    // the half-tile-ring kernel's shapes only (the caller keeps the two-kernel path for everything else)
-    CM3P_REQUIRE(K % 64 == 0 && I % 32 == 0 && T % 8 == 0 && tiles_of(T, 2 * I, 256) >= 200);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const int rc = cm3p_gemm8p_dispatch(x, w_interleaved, a, nullptr, T, 2 * I, K, K, K, I, 1, 1, CM3P_EPI_BF16_GEGLU, 1, K, 0, s, RopeArgs{});
-    if (rc != CM3P_OK) return rc;
-    CM3P_LAUNCH_CHECK();
-    return CM3P_OK;
+    // the ring's big shapes only (the caller keeps the two-kernel path for everything else); no other kernel has this epilogue, so a
+    // call made under CM3P_GEMM_IMPL=256 runs on the ring as well - the switch steers the caller through cm3p_gemm_route
+    GemmRoute r = cm3p_gemm_route_of(T, 2 * I, K, K, K, true, true, CM3P_EPI_BF16_GEGLU, 1, 0, 0);
+    CM3P_REQUIRE(r.kernel >= 0);
+    r.kernel = CM3P_GEMM_RING;
+    const GemmCall g{x, w_interleaved, a, nullptr, T, 2 * I, K, K, K, I, 1, 1, CM3P_EPI_BF16_GEGLU};
+    return run_routed(r, g, static_cast<hipStream_t>(stream));
 }
 
 int cm3p_gemm_bf16_batched(const void* A, const void* B, void* C, const void* R, int batch, int64_t M, int64_t N, int64_t K,
@@ -442,28 +459,13 @@ int cm3p_gemm_bf16_batched(const void* A, const void* B, void* C, const void* R,
     CM3P_REQUIRE(stride_a % 8 == 0 && stride_b % 8 == 0 && stride_c % 8 == 0 && stride_r % 8 == 0);
     CM3P_REQUIRE(a_kc ? (K % 8 == 0 && lda >= K) : (M % 8 == 0 && lda >= M));
     CM3P_REQUIRE(b_kc ? (K % 8 == 0 && ldb >= K) : (N % 8 == 0 && ldb >= N));
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const BatchArgs bt{stride_a, stride_b, stride_c, stride_r, static_cast<const uint16_t*>(R), alpha, beta};
-    int rc;
-    // enough 256 x 256 tiles to occupy the chip (the 768- to 2304-wide weight groups of the Muon step: 198 to 1188): the half-tile
-    // ring kernel, one work item per (matrix, tile); everything else (and what it does not cover) on the 128 x 128 kernel
-    const int64_t tiles256 = ((M + 255) / 256) * ((N + 255) / 256) * batch;
-    const bool filled = M * N * batch * 10 >= tiles256 * 65536 * 7;  // (edge tiles compute their padding: [520 x 264] x 30 ran at 0.59 of the small kernel)
-    if (tiles256 >= 128 && filled && K % 64 == 0 && M % 8 == 0 && (a_kc || !b_kc) && use_8p()) {
-        rc = cm3p_gemm8p_dispatch(A, B, C, nullptr, M, N, K, lda, ldb, ldc, a_kc, b_kc, CM3P_EPI_BF16_AXPBY, 1, K, 0, s, RopeArgs{}, bt, batch);
-        if (rc == CM3P_OK) {
-            CM3P_LAUNCH_CHECK();
-            return CM3P_OK;
-        }
-        if (rc != CM3P_ERR_INVALID) return rc;
-    }
-    if (a_kc && b_kc) rc = launch<true, true>(A, B, C, nullptr, M, N, K, lda, ldb, ldc, CM3P_EPI_BF16_AXPBY, 1, K, 0, s, RopeArgs{}, bt, batch);
-    else if (a_kc) rc = launch<true, false>(A, B, C, nullptr, M, N, K, lda, ldb, ldc, CM3P_EPI_BF16_AXPBY, 1, K, 0, s, RopeArgs{}, bt, batch);
-    else if (b_kc) rc = launch<false, true>(A, B, C, nullptr, M, N, K, lda, ldb, ldc, CM3P_EPI_BF16_AXPBY, 1, K, 0, s, RopeArgs{}, bt, batch);
-    else rc = launch<false, false>(A, B, C, nullptr, M, N, K, lda, ldb, ldc, CM3P_EPI_BF16_AXPBY, 1, K, 0, s, RopeArgs{}, bt, batch);
-    if (rc != CM3P_OK) return rc;
-    CM3P_LAUNCH_CHECK();
-    return CM3P_OK;
+    // (the 768- to 2304-wide weight groups of the Muon step are 198 to 1188 tiles of 256 x 256: one ring work item per (matrix, tile))
+    const GemmRoute r = cm3p_gemm_route_of(M, N, K, lda, ldb, a_kc != 0, b_kc != 0, CM3P_EPI_BF16_AXPBY, 1, 0, batch);
+    CM3P_REQUIRE(r.kernel >= 0);
+    GemmCall g{A, B, C, nullptr, M, N, K, lda, ldb, ldc, a_kc != 0, b_kc != 0, CM3P_EPI_BF16_AXPBY};
+    g.bt = BatchArgs{stride_a, stride_b, stride_c, stride_r, static_cast<const uint16_t*>(R), alpha, beta};
+    g.batch = batch;
+    return run_routed(r, g, static_cast<hipStream_t>(stream));
 }
 
 }  // extern "C"

@@ -411,61 +411,38 @@ __global__ __launch_bounds__(kThreads, kWN == 4 ? 2 : 1) void gemm256_kernel(con
     }
 }
 
-template <bool A_KC, bool B_KC>
-int launch256(const uint16_t* a, const uint16_t* b, void* C, const float* R, int64_t M, int64_t N, int64_t K, int64_t lda,
-              int64_t ldb, int64_t ldc, int epi, int splits, int64_t kchunk, int64_t c_split_stride, hipStream_t s, RopeArgs rope) {
-    const int tiles_m = (int)((M + TM - 1) / TM), tiles_n = (int)((N + TN - 1) / TN);
-    const int ntiles = tiles_m * tiles_n, total = ntiles * splits;
-    const int num_cu = cm3p_num_cu();
-    const dim3 grid(total < num_cu ? total : num_cu);  // one persistent 512-thread workgroup per CU
-    const size_t lds = 2 * kStage;
-#define CM3P_G256(E)                                                                                                     \
-    {                                                                                                                    \
-        static Cm3pDevOnce once;                                                                                         \
-        const int rc_once = once.run([&] {                                                                               \
-            return hipFuncSetAttribute((const void*)gemm256_kernel<A_KC, B_KC, E>, hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                       (int)lds) == hipSuccess                                                           \
-                       ? CM3P_OK                                                                                         \
-                       : CM3P_ERR_LAUNCH;                                                                                \
-        });                                                                                                              \
-        if (rc_once != CM3P_OK) return rc_once;                                                                          \
-        gemm256_kernel<A_KC, B_KC, E><<<grid, kThreads, lds, s>>>(a, b, C, R, M, N, K, lda, ldb, ldc, tiles_n, ntiles, total, kchunk, c_split_stride, rope); \
-    }
-    switch (epi) {
-        case CM3P_EPI_BF16: CM3P_G256(CM3P_EPI_BF16) break;
-        case CM3P_EPI_F32: CM3P_G256(CM3P_EPI_F32) break;
-        case CM3P_EPI_F32_RESID: CM3P_G256(CM3P_EPI_F32_RESID) break;
-        case CM3P_EPI_BF16_RESID: CM3P_G256(CM3P_EPI_BF16_RESID) break;
-        case CM3P_EPI_BF16_ROPE:
-            if constexpr (A_KC && B_KC) {
-                CM3P_G256(CM3P_EPI_BF16_ROPE)
-                break;
-            }
-            return CM3P_ERR_INVALID;
-        case CM3P_EPI_F32_BIAS:
-            if constexpr (A_KC && B_KC) {
-                CM3P_G256(CM3P_EPI_F32_BIAS)
-                break;
-            }
-            return CM3P_ERR_INVALID;
-        default: return CM3P_ERR_INVALID;
-    }
-#undef CM3P_G256
-    return CM3P_OK;
-}
+// the pairs this file instantiates: every layout with the plain epilogues, the forward layout with the rotary and bias ones
+template <bool A_KC, bool B_KC, int EPI>
+constexpr bool has_instance = cm3p_gemm_pair_exists(A_KC, B_KC, EPI) && EPI != CM3P_EPI_BF16_GEGLU && EPI != CM3P_EPI_BF16_AXPBY;
 
 }  // namespace
 
-// Internal entry used by cm3p_gemm_bf16 (gemm.hip) when the shape qualifies; not part of the public header.
-int cm3p_gemm256_dispatch(const void* A, const void* B, void* C, const float* R, int64_t M, int64_t N, int64_t K, int64_t lda,
-                          int64_t ldb, int64_t ldc, int a_kc, int b_kc, int epi, int splits, int64_t kchunk,
-                          int64_t c_split_stride, hipStream_t s, RopeArgs rope) {
-    const uint16_t* a = static_cast<const uint16_t*>(A);
-    const uint16_t* b = static_cast<const uint16_t*>(B);
-    if (a_kc && b_kc) return launch256<true, true>(a, b, C, R, M, N, K, lda, ldb, ldc, epi, splits, kchunk, c_split_stride, s, rope);
-    if (a_kc) return launch256<true, false>(a, b, C, R, M, N, K, lda, ldb, ldc, epi, splits, kchunk, c_split_stride, s, rope);
-    if (b_kc) return launch256<false, true>(a, b, C, R, M, N, K, lda, ldb, ldc, epi, splits, kchunk, c_split_stride, s, rope);
-    return launch256<false, false>(a, b, C, R, M, N, K, lda, ldb, ldc, epi, splits, kchunk, c_split_stride, s, rope);
+// Internal entry of gemm.hip's entry points: launches the instance of a call the route (cm3p_gemm_route_of) sent here; no shape
+// decision is made in this file.
+int cm3p_gemm256_dispatch(const GemmRoute& r, const GemmCall& g, hipStream_t s) {
+    const int tiles_m = (int)((g.M + TM - 1) / TM), tiles_n = (int)((g.N + TN - 1) / TN);
+    const int ntiles = tiles_m * tiles_n, total = ntiles * r.splits;
+    const int num_cu = cm3p_num_cu();
+    const dim3 grid(total < num_cu ? total : num_cu);  // one persistent 512-thread workgroup per CU
+    const size_t lds = 2 * kStage;
+    const uint16_t* a = static_cast<const uint16_t*>(g.A);
+    const uint16_t* b = static_cast<const uint16_t*>(g.B);
+    return cm3p_with_layout(g.a_kc, g.b_kc, [&](auto ak, auto bk) {
+        return cm3p_with_epilogue(g.epi, [&](auto e) {
+            constexpr bool AK = decltype(ak)::value, BK = decltype(bk)::value;
+            constexpr int E = decltype(e)::value;
+            if constexpr (has_instance<AK, BK, E>) {
+                static Cm3pDevOnce once;
+                const int rc_once = once.run([&] { return cm3p_set_max_lds({(const void*)gemm256_kernel<AK, BK, E>}, (int)lds); });
+                if (rc_once != CM3P_OK) return rc_once;
+                gemm256_kernel<AK, BK, E><<<grid, kThreads, lds, s>>>(a, b, g.C, g.R, g.M, g.N, g.K, g.lda, g.ldb, g.ldc, tiles_n, ntiles, total,
+                                                                    r.kchunk, g.c_split_stride, g.rope);
+                return CM3P_OK;
+            } else {
+                return CM3P_ERR_INTERNAL;
+            }
+        });
+    });
 }
 
 // timing-only ablation switches this object was built with (0 in every shipped build: cm3p_build_ablation_flags, tests/test_cabi.py)

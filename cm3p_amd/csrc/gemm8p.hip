@@ -160,7 +160,7 @@ struct Operand {
 // REBAL: the B-lo fragments of k-tile t+1 are read in phase 4 of k-tile t (which has no fragment reads of its own) instead of in
 // phase 1 of t+1, the longest memory section (12 reads + DMA + the B-lo retire wait): r03 probe, -7 % on the long-K shapes with those
 // reads gone.  The two B register sets then swap roles every k-tile, so the k-loop is unrolled by two and every work item must
-// have an even number of k-tiles (the dispatcher sends other shapes to the plain instance).
+// have an even number of k-tiles (the route, cm3p_gemm_route_of in gemm.hip, sends other shapes to the plain instance).
 template <bool A_KC, bool B_KC, int EPI, bool REBAL>
 __global__ __launch_bounds__(512, 2) void gemm8p_kernel(const uint16_t* __restrict__ A, const uint16_t* __restrict__ B, void* __restrict__ Cv,
                                                         const float* R, int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb,
@@ -623,7 +623,7 @@ __global__ __launch_bounds__(512, 2) void gemm8p_kernel(const uint16_t* __restri
         decode(v, m0, n0, z);
         const int64_t kbeg = batched ? 0 : (int64_t)z * kchunk;
         const int nk = (int)((min(K, kbeg + kchunk) - kbeg) / 64);
-        if constexpr (REBAL) {  // nk even (checked by the dispatcher): the register sets swap roles every k-tile
+        if constexpr (REBAL) {  // nk even (the route's REBAL condition): the register sets swap roles every k-tile
             ktile(par, std::true_type{}, fbP, fbQ);
             ktile(par ^ 1, std::false_type{}, fbQ, fbP);
             for (int kt = 2; kt < nk; kt += 2) {
@@ -645,12 +645,20 @@ __global__ __launch_bounds__(512, 2) void gemm8p_kernel(const uint16_t* __restri
     G8P_WAIT_VM(0);                             // no LDS-DMA may outlive the workgroup's LDS allocation
 }
 
-template <bool A_KC, bool B_KC, bool REBAL>
-int launch8p(const uint16_t* a, const uint16_t* b, void* C, const float* R, int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb,
-             int64_t ldc, int epi, int splits, int64_t kchunk, int64_t c_split_stride, hipStream_t s, RopeArgs rope, BatchArgs bt,
-             int batch) {
-    const int tiles_m = (int)((M + 255) / 256), tiles_n = (int)((N + 255) / 256);
-    const int ntiles = tiles_m * tiles_n, total = ntiles * (batch > 0 ? batch : splits);
+// the pairs this file instantiates (each with and without REBAL): every layout with the plain epilogues, the forward layout with the
+// rotary, bias and GeGLU ones, the Muon step's three layouts with AXPBY
+template <bool A_KC, bool B_KC, int EPI>
+constexpr bool has_instance = cm3p_gemm_pair_exists(A_KC, B_KC, EPI) && (EPI != CM3P_EPI_BF16_AXPBY || A_KC || !B_KC);
+
+}  // namespace
+
+// Internal entry of gemm.hip's entry points: launches the instance of a call the route (cm3p_gemm_route_of) sent here.  What this
+// kernel cannot run - M or N no multiple of 8, K or a k-split no multiple of 64, an odd k-tile count on a REBAL instance, operand
+// rows past the 32-bit lane offsets - the route has kept away; no shape decision is made in this file.
+// g.batch > 0: a strided batch (the work item's z is the matrix instead of the k-split), bf16 a x + b y epilogue.
+int cm3p_gemm8p_dispatch(const GemmRoute& r, const GemmCall& g, hipStream_t s) {
+    const int tiles_m = (int)((g.M + 255) / 256), tiles_n = (int)((g.N + 255) / 256);
+    const int ntiles = tiles_m * tiles_n, total = ntiles * (g.batch > 0 ? g.batch : r.splits);
     const int num_cu = cm3p_num_cu();
     // cm3p_gemm8p_set_grid / CM3P_G8P_GRID: fewer workgroups leave CUs to a kernel on another stream (tools/overlap_ab.py), more than CUs
     // are dispatched as CUs come free (tools/blocker_probe.py: what to run beside RCCL).  Any value is safe: a workgroup of this kernel
@@ -659,76 +667,26 @@ int launch8p(const uint16_t* a, const uint16_t* b, void* C, const float* R, int6
     const int set = cm3p_gemm8p_get_grid();
     const int want = set > 0 ? set : num_cu;
     const dim3 grid(total < want ? total : want);
-#define CM3P_G8P(E)                                                                                                               \
-    {                                                                                                                             \
-        static Cm3pDevOnce once;                                                                                                  \
-        const int rc_once = once.run([&] {                                                                                        \
-            return hipFuncSetAttribute((const void*)gemm8p_kernel<A_KC, B_KC, E, REBAL>, hipFuncAttributeMaxDynamicSharedMemorySize, kLds8p) == hipSuccess \
-                       ? CM3P_OK                                                                                                  \
-                       : CM3P_ERR_LAUNCH;                                                                                         \
-        });                                                                                                                       \
-        if (rc_once != CM3P_OK) return rc_once;                                                                                   \
-        gemm8p_kernel<A_KC, B_KC, E, REBAL><<<grid, 512, kLds8p, s>>>(a, b, C, R, M, N, K, lda, ldb, ldc, tiles_n, ntiles, total, kchunk, c_split_stride, rope, bt, batch > 0 ? 1 : 0); \
-    }
-    switch (epi) {
-        case CM3P_EPI_BF16: CM3P_G8P(CM3P_EPI_BF16) break;
-        case CM3P_EPI_F32: CM3P_G8P(CM3P_EPI_F32) break;
-        case CM3P_EPI_F32_RESID: CM3P_G8P(CM3P_EPI_F32_RESID) break;
-        case CM3P_EPI_BF16_RESID: CM3P_G8P(CM3P_EPI_BF16_RESID) break;
-        case CM3P_EPI_BF16_ROPE:
-            if constexpr (A_KC && B_KC) {
-                CM3P_G8P(CM3P_EPI_BF16_ROPE)
-                break;
-            }
-            return CM3P_ERR_INVALID;
-        case CM3P_EPI_F32_BIAS:
-            if constexpr (A_KC && B_KC) {
-                CM3P_G8P(CM3P_EPI_F32_BIAS)
-                break;
-            }
-            return CM3P_ERR_INVALID;
-        case CM3P_EPI_BF16_GEGLU:
-            if constexpr (A_KC && B_KC) {
-                CM3P_G8P(CM3P_EPI_BF16_GEGLU)
-                break;
-            }
-            return CM3P_ERR_INVALID;
-        case CM3P_EPI_BF16_AXPBY:
-            if constexpr (A_KC || !B_KC) {  // (the Muon step's three layouts)
-                CM3P_G8P(CM3P_EPI_BF16_AXPBY)
-                break;
-            }
-            return CM3P_ERR_INVALID;
-        default: return CM3P_ERR_INVALID;
-    }
-#undef CM3P_G8P
-    return CM3P_OK;
-}
-
-}  // namespace
-
-// Internal entry used by gemm.hip; returns CM3P_ERR_INVALID for what this kernel does not cover (the caller then falls back).
-int cm3p_gemm8p_dispatch(const void* A, const void* B, void* C, const float* R, int64_t M, int64_t N, int64_t K, int64_t lda,
-                         int64_t ldb, int64_t ldc, int a_kc, int b_kc, int epi, int splits, int64_t kchunk, int64_t c_split_stride,
-                         hipStream_t s, RopeArgs rope, BatchArgs bt, int batch) {
-    // batch > 0: a strided batch of `batch` matrices (the work item's z is the matrix instead of the k-split), bf16 a x + b y epilogue
-    if ((batch > 0) != (epi == CM3P_EPI_BF16_AXPBY) || (batch > 0 && (splits != 1 || kchunk != K))) return CM3P_ERR_INVALID;
-    if (M % 8 != 0 || N % 8 != 0 || K % 64 != 0 || kchunk % 64 != 0) return CM3P_ERR_INVALID;
-    if (lda * 2 * 8 >= (int64_t(1) << 31) || ldb * 2 * 8 >= (int64_t(1) << 31)) return CM3P_ERR_INVALID;  // 32-bit lane offsets
-    const uint16_t* a = static_cast<const uint16_t*>(A);
-    const uint16_t* b = static_cast<const uint16_t*>(B);
-    // every work item's k-tile count even (the last k-split may be shorter): the instance whose B register sets swap roles
-    const int64_t last = K - (int64_t)(splits - 1) * kchunk;
-    static const bool no_rebal = [] { const char* e = getenv("CM3P_G8P_REBAL"); return e && e[0] == '0'; }();
-    const bool rebal = !no_rebal && (kchunk / 64) % 2 == 0 && (splits == 1 ? (K / 64) % 2 == 0 : (last > 0 && (last / 64) % 2 == 0));
-#define CM3P_G8P_GO(AK, BK)                                                                                                      \
-    return rebal ? launch8p<AK, BK, true>(a, b, C, R, M, N, K, lda, ldb, ldc, epi, splits, kchunk, c_split_stride, s, rope, bt, batch)  \
-                 : launch8p<AK, BK, false>(a, b, C, R, M, N, K, lda, ldb, ldc, epi, splits, kchunk, c_split_stride, s, rope, bt, batch)
-    if (a_kc && b_kc) CM3P_G8P_GO(true, true);
-    if (a_kc) CM3P_G8P_GO(true, false);
-    if (b_kc) CM3P_G8P_GO(false, true);
-    CM3P_G8P_GO(false, false);
-#undef CM3P_G8P_GO
+    const uint16_t* a = static_cast<const uint16_t*>(g.A);
+    const uint16_t* b = static_cast<const uint16_t*>(g.B);
+    return cm3p_with_layout(g.a_kc, g.b_kc, [&](auto ak, auto bk) {
+        return cm3p_with_epilogue(g.epi, [&](auto e) {
+            return cm3p_with_flag(r.rebal, [&](auto rebal) {
+                constexpr bool AK = decltype(ak)::value, BK = decltype(bk)::value, REBAL = decltype(rebal)::value;
+                constexpr int E = decltype(e)::value;
+                if constexpr (has_instance<AK, BK, E>) {
+                    static Cm3pDevOnce once;
+                    const int rc_once = once.run([&] { return cm3p_set_max_lds({(const void*)gemm8p_kernel<AK, BK, E, REBAL>}, kLds8p); });
+                    if (rc_once != CM3P_OK) return rc_once;
+                    gemm8p_kernel<AK, BK, E, REBAL><<<grid, 512, kLds8p, s>>>(a, b, g.C, g.R, g.M, g.N, g.K, g.lda, g.ldb, g.ldc, tiles_n, ntiles, total,
+                                                                            r.kchunk, g.c_split_stride, g.rope, g.bt, g.batch > 0 ? 1 : 0);
+                    return CM3P_OK;
+                } else {
+                    return CM3P_ERR_INTERNAL;
+                }
+            });
+        });
+    });
 }
 
 // timing-only ablation switches this object was built with (0 in every shipped build: cm3p_build_ablation_flags, tests/test_cabi.py)

@@ -156,33 +156,25 @@ def _wgrad_splits(M: int, N: int, K: int) -> int:
     return query("cm3p_gemm_wgrad_splits", M, N, K)
 
 
-def _big_gemm_kernel(M: int, N: int) -> str:
-    """Which 256 x 256 kernel cm3p_gemm_bf16 takes for a big shape (csrc/gemm.hip big_gemm): the half-tile-ring kernel of gemm8p.hip
-    unless the extents are not multiples of 8 or CM3P_GEMM_IMPL=256 selects the r01 kernel."""
-    return "gemm8p_kernel" if (M % 8 == 0 and N % 8 == 0 and not os.environ.get("CM3P_GEMM_IMPL", "").startswith("2")) else "gemm256_kernel"
+_GEMM_KERNELS = ("gemm_bf16_kernel", "gemm256_kernel", "gemm8p_kernel")  # the kernel numbers of cm3p_gemm_route
+_GEMM_RING, _GEMM_REBAL = 2, 4
+EPI_ROPE, EPI_GEGLU = 3, 6  # internal epilogue numbers cm3p_gemm_route accepts (csrc/common.h)
 
 
-def _g8p_rebal(K: int, kchunk: int) -> bool:
-    """gemm8p.hip's instance choice (cm3p_gemm8p_dispatch): REBAL when every work item has an even number of 64-deep k-tiles."""
-    if os.environ.get("CM3P_G8P_REBAL", "1").startswith("0"):
-        return False
-    splits = max(1, -(-K // kchunk))
-    last = K - (splits - 1) * kchunk
-    return (kchunk // 64) % 2 == 0 and ((K // 64) % 2 == 0 if splits == 1 else (last > 0 and (last // 64) % 2 == 0))
-
-
-def _gemm_tag(M: int, N: int, K: int, a_kc, b_kc, epilogue, split_k: int) -> str:
-    """Profiler tag = the kernel the library will pick (same rule as cm3p_gemm_bf16 in csrc/gemm.hip), spelled like rocprof."""
-    q = 128 if K % 128 == 0 else 64  # (csrc/gemm.hip: k-split lengths are multiples of 128 where K allows it)
-    kchunk = K if split_k <= 1 else -(-(-(-K // split_k)) // q) * q
-    big = K % 64 == 0 and kchunk % 64 == 0 and (-(-M // 256)) * (-(-N // 256)) * max(1, -(-K // kchunk)) >= 200 \
-        and not os.environ.get("CM3P_GEMM_IMPL", "").startswith("1")  # (CM3P_GEMM_IMPL=128: the 128 x 128 kernel for every shape)
+def _gemm_tag(M: int, N: int, K: int, a_kc, b_kc, epilogue, split_k: int, lda: Optional[int] = None, ldb: Optional[int] = None,
+              rope_cols: int = 0, kernel: Optional[int] = None) -> str:
+    """Profiler tag = the kernel instance the library's own routing rule names (cm3p_gemm_route; csrc/gemm.hip cm3p_gemm_route_of),
+    spelled like rocprof.  Asked on every call: CM3P_GEMM_IMPL may change inside a process.  lda / ldb default to the unpadded
+    operands'; kernel: the entry point's own kernel where it has only one (cm3p_gemm_geglu)."""
+    lda = (K if a_kc else M) if lda is None else lda
+    ldb = (K if b_kc else N) if ldb is None else ldb
+    code = query("cm3p_gemm_route", M, N, K, lda, ldb, int(bool(a_kc)), int(bool(b_kc)), epilogue, split_k, rope_cols, 0)
+    if code < 0:
+        raise _lib.Cm3pHipError(f"cm3p_gemm_route: no bf16 GEMM kernel takes M {M} N {N} K {K} a_kc {a_kc} b_kc {b_kc} epilogue {epilogue} split_k {split_k}")
+    kernel = code & 3 if kernel is None else kernel
     b2s = lambda v: "true" if v else "false"
-    if not big:
-        return f"gemm_bf16_kernel<{b2s(a_kc)}, {b2s(b_kc)}, {epilogue}>"
-    name = _big_gemm_kernel(M, N)
-    tail = f", {b2s(_g8p_rebal(K, kchunk))}" if name == "gemm8p_kernel" else ""
-    return f"{name}<{b2s(a_kc)}, {b2s(b_kc)}, {epilogue}{tail}>"
+    tail = f", {b2s(code & _GEMM_REBAL)}" if kernel == _GEMM_RING else ""
+    return f"{_GEMM_KERNELS[kernel]}<{b2s(a_kc)}, {b2s(b_kc)}, {epilogue}{tail}>"
 
 
 def gemm(a: Tensor, b: Tensor, M: int, N: int, K: int, a_kc: bool, b_kc: bool, epilogue: int,
@@ -193,7 +185,7 @@ def gemm(a: Tensor, b: Tensor, M: int, N: int, K: int, a_kc: bool, b_kc: bool, e
         out = _empty((M, N), torch.bfloat16 if epilogue in (EPI_BF16, EPI_BF16_RESID) else torch.float32, a)
     ws = _empty((split_k, M, N), torch.float32, a) if split_k > 1 else None
     call("cm3p_gemm_bf16", ptr(a), ptr(b), ptr(out), ptr(resid), M, N, K, lda, ldb, N, int(a_kc), int(b_kc), epilogue, split_k,
-         ptr(ws), stream(), tag=_gemm_tag(M, N, K, a_kc, b_kc, epilogue, split_k), work=2.0 * M * N * K)
+         ptr(ws), stream(), tag=_gemm_tag(M, N, K, a_kc, b_kc, epilogue, split_k, lda, ldb), work=2.0 * M * N * K)
     return out
 
 
@@ -223,8 +215,7 @@ def qkv_linear_rope(x: Tensor, w: Tensor, cos: Tensor, sin: Tensor, S: int, per_
     N = w.shape[0]
     out = _empty((T, N), torch.bfloat16, x)
     call("cm3p_qkv_gemm_rope", ptr(x), ptr(w), ptr(out), T, N, Kd, ptr(cos, torch.float32), ptr(sin, torch.float32), S, int(per_batch), 2 * N // 3, float(q_scale), stream(),
-         tag=_gemm_tag(T, N, Kd, True, True, 3, 1) if (2 * N // 3) % 256 == 0 else "gemm_bf16_kernel<true, true, 3>",
-         work=2.0 * T * N * Kd)
+         tag=_gemm_tag(T, N, Kd, True, True, EPI_ROPE, 1, rope_cols=2 * N // 3), work=2.0 * T * N * Kd)
     return out
 
 
@@ -556,9 +547,10 @@ def geglu_fwd(h: Tensor) -> Tensor:
 
 
 def gemm_geglu_supported(T: int, I: int, Kd: int) -> bool:
-    """cm3p_gemm_geglu's shape rule (csrc/gemm.hip): the 256 x 256 ring kernel's big shapes."""
-    return Kd % 64 == 0 and I % 32 == 0 and T % 8 == 0 and (-(-T // 256)) * (-(-2 * I // 256)) >= 200 \
-        and not os.environ.get("CM3P_GEMM_IMPL", "").startswith("2")
+    """Whether the Wi projection of this shape runs fused with GeGLU: cm3p_gemm_geglu's shape rule (the ring's big shapes), and the
+    library's route names the ring (it does not under CM3P_GEMM_IMPL=256)."""
+    code = query("cm3p_gemm_route", T, 2 * I, Kd, Kd, Kd, 1, 1, EPI_GEGLU, 1, 0, 0)
+    return code >= 0 and (code & 3) == _GEMM_RING
 
 
 def geglu_interleave_index(I: int, device) -> Tensor:
@@ -575,7 +567,7 @@ def gemm_geglu(x: Tensor, w_interleaved: Tensor) -> Tensor:
     I = w_interleaved.shape[0] // 2
     a = _empty((T, I), torch.bfloat16, x)
     call("cm3p_gemm_geglu", ptr(x), ptr(w_interleaved), ptr(a), T, I, Kd, stream(),
-         tag=f"gemm8p_kernel<true, true, 6, {'true' if _g8p_rebal(Kd, Kd) else 'false'}>", work=2.0 * T * 2 * I * Kd)
+         tag=_gemm_tag(T, 2 * I, Kd, True, True, EPI_GEGLU, 1, kernel=_GEMM_RING), work=2.0 * T * 2 * I * Kd)
     return a
 
 

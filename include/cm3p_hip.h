@@ -26,12 +26,13 @@ extern "C" {
 #define CM3P_OK 0
 #define CM3P_ERR_INVALID (-1) /* bad argument: null pointer, unsupported shape, misaligned buffer */
 #define CM3P_ERR_LAUNCH (-2)  /* the HIP runtime refused the launch */
+#define CM3P_ERR_INTERNAL (-3) /* the library's own dispatch named a kernel instance that does not exist: a bug, never a fallback */
 
 #define CM3P_F32 0
 #define CM3P_BF16 1
 
 /* ABI version of this header; cm3p_abi_version() must return it. */
-#define CM3P_ABI_VERSION 19
+#define CM3P_ABI_VERSION 20
 int cm3p_abi_version(void);
 
 /* ---------------------------------------------------------------------------------------------------------------
@@ -168,6 +169,22 @@ int cm3p_qkv_gemm_rope(const void* x, const void* Wqkv, void* qkv, int64_t M, in
 
 /* Host-only: the split_k the library recommends for a weight-gradient GEMM of this shape (sizes the workspace). */
 int cm3p_gemm_wgrad_splits(int64_t M, int64_t N, int64_t K);
+
+/* Host-only: where a bf16 GEMM call of these shape facts lands - the answer of the one routing rule the four launching entry points
+ * (cm3p_gemm_bf16, cm3p_qkv_gemm_rope, cm3p_gemm_geglu, cm3p_gemm_bf16_batched) execute (csrc/gemm.hip, cm3p_gemm_route_of), read
+ * under the current value of the CM3P_GEMM_IMPL development switch.  Profiler tags and tests are spelled from it.
+ *   epilogue: a public CM3P_EPI_* number with the arguments of cm3p_gemm_bf16 (rope_cols = 0, batch = 0); 3 with the M, N, K and
+ *   rope_cols of cm3p_qkv_gemm_rope (lda = ldb = K); 6 with M = T, N = 2 I of cm3p_gemm_geglu; 4 with batch > 0 for
+ *   cm3p_gemm_bf16_batched.
+ * Returns a non-negative code: bits 0-1 the kernel (0 gemm_bf16_kernel, 128 x 128; 1 gemm256_kernel; 2 gemm8p_kernel, the ring),
+ * bit 2 set when every work item of a 256 x 256 route has an even number of k-tiles (the ring's REBAL instances), bits 3 and up
+ * the split count the library uses.  Negative (CM3P_ERR_INVALID): the rule has no kernel for the call and the entry point refuses
+ * it - a non-positive extent, split_k < 1, a rotary / bias / GeGLU epilogue outside the forward layout, a shape outside
+ * cm3p_gemm_geglu's rule (the pointer, alignment and leading-dimension checks stay with the entry points).
+ * Epilogue 6 answers kernel 1 under CM3P_GEMM_IMPL=256: the caller then keeps the two-kernel Wi + GeGLU path
+ * (cm3p_gemm_geglu itself runs on the ring whenever it is called: no other kernel has that epilogue). */
+int cm3p_gemm_route(int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb, int a_kc, int b_kc, int epilogue, int split_k,
+                    int rope_cols, int batch);
 
 /* fp32 -> bf16 cast of n elements (n % 4 == 0): the autocast weight / activation cast in front of a bf16 linear. */
 int cm3p_cast_f32_bf16(const float* x, void* y, int64_t n, void* stream);

@@ -252,9 +252,10 @@ def kchunk_of(K, split_k):
 
 @dataclass(frozen=True)
 class Case:
-    """One GEMM shape.  kernel / rebal: where it lands by default, stated here by hand from the dispatchers (csrc/gemm.hip
-    cm3p_gemm_bf16 and big_gemm, csrc/gemm8p.hip cm3p_gemm8p_dispatch) and compared with cm3p_amd.kernels._gemm_tag on the GPU and
-    with the restated rule on the host - three statements of one rule; none of them observes the launch."""
+    """One GEMM shape.  kernel / rebal: where it lands by default, stated here by hand from the routing rule (csrc/gemm.hip
+    cm3p_gemm_route_of) and compared on the host with the rule restated below (restated_kernel) and with the library's own answer
+    (cm3p_gemm_route, which the entry points launch from), and again on the GPU before every launch - three statements of one rule,
+    the third being the one that runs."""
     name: str
     M: int
     N: int

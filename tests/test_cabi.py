@@ -61,6 +61,20 @@ def test_host_only_queries(lib_path):
     assert _lib.query("cm3p_attn_bwd_fused_workspace_bytes", 32, 4096, 12) == 32 * 12 * (76 * 512 + 8 * 4160 * 128)  # (two 256-key blocks share a slab since ABI 13)
 
 
+def test_gemm_route_query_packs_kernel_rebal_and_splits(lib_path, monkeypatch):
+    """cm3p_gemm_route (host-only, ABI 20): bits 0-1 the kernel, bit 2 REBAL, bits 3+ the recomputed split count; negative = refused."""
+    from cm3p_amd import _lib
+
+    monkeypatch.delenv("CM3P_GEMM_IMPL", raising=False)
+    assert _lib.ABI_VERSION == 20
+    assert _lib.query("cm3p_gemm_route", 200, 72, 96, 96, 96, 1, 1, _lib.EPI_BF16, 1, 0, 0) == 0 | 1 << 3  # 128 x 128
+    assert _lib.query("cm3p_gemm_route", 51200, 256, 128, 128, 128, 1, 1, _lib.EPI_BF16, 1, 0, 0) == 2 | 4 | 1 << 3  # the ring, REBAL
+    assert _lib.query("cm3p_gemm_route", 51204, 252, 64, 64, 64, 1, 1, _lib.EPI_F32, 1, 0, 0) == 1 | 1 << 3  # gemm256_kernel
+    # 49 requested splits of K = 32768 become 43 of 768 (the last one 512): every item an even number of k-tiles
+    assert _lib.query("cm3p_gemm_route", 776, 264, 32768, 776, 264, 0, 0, _lib.EPI_F32, 49, 0, 0) == 2 | 4 | 43 << 3
+    assert _lib.query("cm3p_gemm_route", 51200, 256, 64, 51200, 64, 0, 1, _lib.EPI_F32_BIAS, 1, 0, 0) == -1
+
+
 def test_cpu_tensors_are_refused(lib_path):
     import torch
 

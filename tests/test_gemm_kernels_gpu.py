@@ -7,9 +7,10 @@ restatement of the kernels' arithmetic passes every check used here and that wro
 m 2^e at full bf16 significand width: the fp32 accumulator is exact, so everything that is a single IEEE operation after it is
 asserted BIT FOR BIT against the float64 matmul; the RoPE, GeGLU and random-data checks are per element |got - ref| <= bound and
 print their largest err / bound (`pytest -rP`).  Every case states the kernel and REBAL flag it is meant for (the table's hand-stated
-entry) and asserts before it runs that cm3p_amd.kernels._gemm_tag, the library's dispatch rule restated in Python, agrees: that
-catches a shape that the rule routes elsewhere, not a launch that went elsewhere - nothing here observes which kernel the C
-dispatcher started (no table case meets one of the ring's refusals, after which big_gemm would fall back to gemm256_kernel).
+entry) and asserts before it runs that cm3p_amd.kernels._gemm_tag agrees.  That tag is spelled from cm3p_gemm_route, the answer of
+the one routing function (csrc/gemm.hip cm3p_gemm_route_of) that the entry point itself evaluates and then launches from: the
+hand table is compared with the rule the dispatcher executes, under the CM3P_GEMM_IMPL of the call.  (The launch itself is still
+not observed: what is asserted is the route, and the launchers have no decision left to make after it.)
 Every big-path case of cm3p_gemm_bf16 and cm3p_qkv_gemm_rope runs three times: by default (the ring), under CM3P_GEMM_IMPL=256
 (gemm256_kernel) and under CM3P_GEMM_IMPL=128 (the 128 x 128 kernel); cm3p_gemm_geglu exists on the ring only and the cases of
 test_small_kernel_natively take the 128 x 128 kernel whatever the switch.  Every output lies inside a larger buffer
@@ -134,6 +135,7 @@ def _grids(case, impl):
 
 
 def _assert_tag(K, case, epi, impl, what):
+    """The hand table against the library's own route for this call (K._gemm_tag formats cm3p_gemm_route's answer)."""
     tag = K._gemm_tag(case.M, case.N, case.K, case.a_kc, case.b_kc, epi, case.split_k)
     assert tag == case.tag(epi, impl), f"{what}: lands on {tag}, the case table says {case.tag(epi, impl)}"
 
@@ -333,7 +335,7 @@ def test_rope_epilogue_against_its_kernels_specification(K, monkeypatch, S, B, i
     T, N, Kd, nh = case.M, case.N, case.K, G.ROPE_NH
     x, w, acc = _rope_operands(S, B)
     assert (2 * N // 3) % 256 == 0
-    tag = K._gemm_tag(T, N, Kd, True, True, G.EPI_ROPE, 1)  # (the tag expression of K.qkv_linear_rope)
+    tag = K._gemm_tag(T, N, Kd, True, True, G.EPI_ROPE, 1, rope_cols=2 * N // 3)  # (the tag expression of K.qkv_linear_rope)
     assert tag == case.tag(G.EPI_ROPE, impl), (tag, case.tag(G.EPI_ROPE, impl))
     small = tag.startswith(G.SMALL)
     pos = G.rope_positions(S, B, per_batch)
@@ -370,7 +372,8 @@ def test_geglu_epilogue_against_float64_and_the_two_kernel_chain(K, T, I, Kd, mo
 
     _set_impl(monkeypatch, None)
     assert K.gemm_geglu_supported(T, I, Kd)
-    assert K._g8p_rebal(Kd, Kd) == ((Kd // 64) % 2 == 0)  # (the instance in K.gemm_geglu's tag)
+    rebal = "true" if (Kd // 64) % 2 == 0 else "false"  # (the instance in K.gemm_geglu's tag)
+    assert K._gemm_tag(T, 2 * I, Kd, True, True, G.EPI_GEGLU, 1, kernel=K._GEMM_RING) == f"{G.RING}<true, true, {G.EPI_GEGLU}, {rebal}>"
     g = gen("gemm", "geglu", T, I, Kd)
     ea, eb = G.geglu_exps(Kd)
     x, wi = G.exact_operand(T, Kd, g, exps=ea), G.exact_operand(2 * I, Kd, g, exps=eb)

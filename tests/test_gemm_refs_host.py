@@ -1,7 +1,8 @@
 """The generators, references and bounds of tests/test_gemm_kernels_gpu.py, checked without a GPU: the data is exact (an fp32 matmul
 equals the float64 one bit for bit), a torch fp32 restatement of the kernels' arithmetic (tests/gemm_refs.py: gemm_f32_path,
 rope_f32_path, R.geglu_fwd_f32_path) passes every check the GPU test makes, and the wrong evaluations the kernels could fall into
-fail them.  The case table's hand-stated kernels agree with the restated dispatch rule."""
+fail them.  The case table's hand-stated kernels agree with the restated dispatch rule and with the library's own: cm3p_gemm_route,
+the host-only answer of the routing function the entry points launch from (csrc/gemm.hip cm3p_gemm_route_of)."""
 import pytest
 import torch
 
@@ -44,6 +45,126 @@ def test_case_table_states_the_kernel_the_restated_rule_gives():
         assert G.rope_case(S, B).kernel == G.RING and (S * B) % 8 == 0
     for S, B in G.ROPE_SMALL:
         assert G.rope_case(S, B).kernel == G.SMALL
+
+
+# ================================================================================================ the library's own route
+IMPLS = [None, "256", "128"]
+K128, K256, KRING = 0, 1, 2  # cm3p_gemm_route's kernel numbers (include/cm3p_hip.h)
+EPI_AXPBY = 4
+
+
+def _set_impl(monkeypatch, impl):
+    if impl is None:
+        monkeypatch.delenv("CM3P_GEMM_IMPL", raising=False)
+    else:
+        monkeypatch.setenv("CM3P_GEMM_IMPL", impl)
+
+
+def _route(M, N, K, a_kc=True, b_kc=True, epi=G.EPI_F32, split_k=1, lda=None, ldb=None, rope_cols=0, batch=0):
+    """One call of cm3p_gemm_route -> (kernel, rebal, splits), or None where the library refuses."""
+    from cm3p_amd import _lib
+
+    lda = (K if a_kc else M) if lda is None else lda
+    ldb = (K if b_kc else N) if ldb is None else ldb
+    code = _lib.query("cm3p_gemm_route", M, N, K, lda, ldb, int(a_kc), int(b_kc), epi, split_k, rope_cols, batch)
+    return None if code < 0 else (code & 3, bool(code & 4), code >> 3)
+
+
+@pytest.mark.parametrize("impl", IMPLS)
+def test_the_librarys_route_spells_the_tag_the_case_table_states(monkeypatch, impl):
+    """Every case, every epilogue it accepts, under every value of CM3P_GEMM_IMPL: the tag cm3p_amd.kernels spells from
+    cm3p_gemm_route is the hand table's, and the split count the library recomputes is kchunk_of's."""
+    from cm3p_amd import kernels as K
+
+    _set_impl(monkeypatch, impl)
+    for c in G.ALL_CASES:
+        for epi in c.epilogues():
+            assert K._gemm_tag(c.M, c.N, c.K, c.a_kc, c.b_kc, epi, c.split_k) == c.tag(epi, impl), (c, epi, impl)
+        assert _route(c.M, c.N, c.K, c.a_kc, c.b_kc, G.EPI_F32, c.split_k)[2] == G.kchunk_of(c.K, c.split_k)[1], c
+    for S, B in G.ROPE_BIG + G.ROPE_SMALL:
+        c = G.rope_case(S, B)
+        assert (2 * c.N // 3) % 256 == 0
+        assert K._gemm_tag(c.M, c.N, c.K, True, True, G.EPI_ROPE, 1, rope_cols=2 * c.N // 3) == c.tag(G.EPI_ROPE, impl), (c, impl)
+    for T, I, Kd in G.GEGLU:
+        # cm3p_gemm_geglu runs on the ring whenever it is called; under CM3P_GEMM_IMPL=256 the route names gemm256_kernel and the
+        # caller keeps the two-kernel path (gemm_geglu_supported), under 128 the fusion stays on
+        rebal = (Kd // 64) % 2 == 0
+        assert _route(T, 2 * I, Kd, epi=G.EPI_GEGLU) == (K256 if impl == "256" else KRING, rebal, 1)
+        assert K.gemm_geglu_supported(T, I, Kd) == (impl != "256")
+        assert K._gemm_tag(T, 2 * I, Kd, True, True, G.EPI_GEGLU, 1, kernel=K._GEMM_RING) == f"{G.RING}<true, true, 6, {'true' if rebal else 'false'}>"
+
+
+def test_routes_no_case_states():
+    """The ring's 32-bit lane offsets, the rotary tile-boundary condition, the batched entry's thresholds and layouts, what the
+    route refuses: one query each, no data."""
+    big = dict(M=51200, N=256, K=64)  # 200 tiles
+    assert _route(**big) == (KRING, False, 1)
+    # 16 rows of an operand must lie inside a 32-bit byte offset: lda * 16 elements * 2 bytes < 2^32 / 2
+    assert _route(**big, lda=2 ** 27 - 8) == (KRING, False, 1) and _route(**big, lda=2 ** 27) == (K256, False, 1)
+    assert _route(**big, ldb=2 ** 27 - 8) == (KRING, False, 1) and _route(**big, ldb=2 ** 27) == (K256, False, 1)
+    # RoPE: 3 heads rotate 384 columns, which end inside a 256-column tile: the 128 x 128 kernel whatever M; 4 heads end on one
+    for M in (256, 51200, 2 ** 22):
+        assert _route(M, 576, 64, epi=G.EPI_ROPE, rope_cols=384) == (K128, False, 1)
+    assert _route(51200, 768, 64, epi=G.EPI_ROPE, rope_cols=512) == (KRING, False, 1)
+    assert _route(2 ** 31, 768, 64, epi=G.EPI_ROPE, rope_cols=512) == (K128, False, 1)  # (32-bit table row arithmetic)
+    # batched (epilogue 4): 128 (matrix, tile) items
+    bt = dict(K=128, epi=EPI_AXPBY)
+    assert _route(256, 256, batch=127, **bt) == (K128, False, 1) and _route(256, 256, batch=128, **bt) == (KRING, True, 1)
+    # ... whose tiles are 0.7 full: 256 x 184 = 47104 >= 0.7 x 65536 = 45875.2 > 256 x 176 = 45056
+    assert _route(256, 184, batch=128, **bt) == (KRING, True, 1) and _route(256, 176, batch=128, **bt) == (K128, False, 1)
+    # ... in the Muon step's three layouts
+    for a_kc, b_kc in ((True, True), (True, False), (False, False)):
+        assert _route(256, 256, a_kc=a_kc, b_kc=b_kc, batch=128, **bt) == (KRING, True, 1)
+    assert _route(256, 256, a_kc=False, b_kc=True, batch=128, **bt) == (K128, False, 1)
+    assert _route(256, 256, batch=128, K=96, epi=EPI_AXPBY) == (K128, False, 1) and _route(252, 256, a_kc=False, b_kc=False, batch=200, **bt)[0] == K128
+    # refusals: no kernel has the pair, or the arguments are no call of any entry point
+    for epi in (G.EPI_ROPE, G.EPI_F32_BIAS, G.EPI_GEGLU):
+        for a_kc, b_kc in ((True, False), (False, True), (False, False)):
+            assert _route(51200, 256, 64, a_kc, b_kc, epi) is None
+    assert _route(**big, epi=EPI_AXPBY) is None and _route(**big, batch=2) is None and _route(**big, epi=8) is None and _route(**big, epi=-1) is None
+    assert _route(**big, split_k=0) is None and _route(0, 256, 64) is None and _route(256, 0, 64) is None and _route(256, 256, 0) is None
+    # cm3p_gemm_geglu's shape rule (T, 2 I, K): T % 8, I % 32, K % 64, 200 tiles
+    assert _route(51200, 256, 64, epi=G.EPI_GEGLU) == (KRING, False, 1)
+    for T, N, Kd in ((51204, 256, 64), (51200, 288, 64), (51200, 256, 96), (50944, 256, 64)):
+        assert _route(T, N, Kd, epi=G.EPI_GEGLU) is None, (T, N, Kd)
+
+
+@pytest.mark.parametrize("impl", IMPLS)
+def test_switches_on_the_routes_no_case_states(monkeypatch, impl):
+    """CM3P_GEMM_IMPL=256 takes the ring away from a batch too (128 x 128 then); 128 leaves the batched and GeGLU entries alone."""
+    _set_impl(monkeypatch, impl)
+    assert _route(256, 256, 128, epi=EPI_AXPBY, batch=128)[0] == (K128 if impl == "256" else KRING)
+    assert _route(51200, 256, 64, lda=2 ** 27)[0] == (K128 if impl == "128" else K256)
+    assert _route(51200, 768, 64, epi=G.EPI_ROPE, rope_cols=512)[0] == {None: KRING, "256": K256, "128": K128}[impl]
+
+
+@pytest.mark.parametrize("impl", IMPLS)
+def test_no_route_names_a_ring_or_256_instance_that_does_not_exist(monkeypatch, impl):
+    """The launchers answer CM3P_ERR_INTERNAL for a (layout, epilogue) pair their file does not instantiate.  No such pair comes out
+    of the route: over every layout and epilogue number, at shapes that reach each kernel, a route either refuses or names a kernel
+    that has the pair (the has_instance statements of csrc/gemm.hip, gemm256.hip and gemm8p.hip, restated)."""
+    _set_impl(monkeypatch, impl)
+    fwd_only = (G.EPI_ROPE, G.EPI_F32_BIAS, G.EPI_GEGLU)
+
+    def exists(kernel, a_kc, b_kc, epi):
+        if epi in fwd_only and not (a_kc and b_kc):
+            return False
+        if epi == G.EPI_GEGLU:
+            return kernel == KRING
+        if epi == EPI_AXPBY:
+            return kernel == K128 or (kernel == KRING and (a_kc or not b_kc))
+        return True
+
+    seen = set()
+    for M, N, Kd, batch in ((51200, 256, 64, 200), (51204, 252, 64, 200), (264, 136, 96, 2)):
+        for a_kc in (True, False):
+            for b_kc in (True, False):
+                for epi in range(8):
+                    r = _route(M, N, Kd, a_kc, b_kc, epi, rope_cols=256 if epi == G.EPI_ROPE else 0, batch=batch if epi == EPI_AXPBY else 0)
+                    if r is not None and not (epi == G.EPI_GEGLU and impl == "256"):  # (that route is advice to the caller: see above)
+                        assert exists(r[0], a_kc, b_kc, epi), (M, N, Kd, a_kc, b_kc, epi, r)
+                        seen.add(r[0])
+    assert seen == {None: {K128, K256, KRING}, "256": {K128, K256}, "128": {K128, KRING}}[impl]
 
 
 @pytest.mark.parametrize("K", KS_USED)

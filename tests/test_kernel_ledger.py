@@ -124,6 +124,7 @@ EXEMPT = {
     "cm3p_embed_ln_bwd_sorted_chunk": "host query: the id-order backward's chunk size",
     "cm3p_token_order_workspace_ints": "host query: workspace size of cm3p_token_order",
     "cm3p_gemm_wgrad_splits": "host query: split-K factor the wrapper picks",
+    "cm3p_gemm_route": "host query: the kernel, instance and split count a bf16 GEMM call lands on (tests/test_gemm_refs_host.py)",
     "cm3p_build_ablation_flags": "ablation hook: tests/test_cabi.py and _lib.load() require 0 from a product library",
     "cm3p_debug_set_dma_audit": "audit hook of the debug twin (tests/test_dma_audit_gpu.py)",
     "cm3p_attn_fwd_impl": "host query: which forward kernel a shape takes",
