@@ -17,6 +17,7 @@ ADD_A_BF16 = 16  # cm3p_add_f32: or-ed into b_dtype when the first operand (and 
 POOL_PACKED = 2  # cm3p_pool_fwd / cm3p_pool_bwd: or-ed into cls when the rows are packed and `mask` carries their int32 cu_seqlens
 GEMM_F32_TILED = 2  # cm3p_gemm_f32: or-ed into accumulate to run the register-tiled kernel (same bits; operands need a unit stride)
 EPI_BF16, EPI_F32, EPI_F32_RESID, EPI_F32_BIAS, EPI_BF16_RESID = 0, 1, 2, 5, 7
+EPI_BF16_GEGLU_FWD, EPI_BF16_GEGLU_BWD = 9, 10  # cm3p_gemm_bf16: the GeGLU of a training step in the Wi GEMM's / the Wo2 dgrad's store phase
 ABI_VERSION = 20
 
 _HERE = os.path.dirname(os.path.abspath(__file__))

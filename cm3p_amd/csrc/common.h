@@ -22,13 +22,14 @@ typedef __attribute__((ext_vector_type(16))) float f32x16;
 #define CM3P_EPI_BF16_AXPBY 4  // internal: bf16 output = alpha * acc + beta * Rb (cm3p_gemm_bf16_batched)
 // 5 = CM3P_EPI_F32_BIAS (public, include/cm3p_hip.h)
 #define CM3P_EPI_BF16_GEGLU 6  // internal (cm3p_gemm_geglu): every 64 output columns are [32 h | 32 g]; stores gelu_erf(h) * g, 32 columns
-// 7 = CM3P_EPI_BF16_RESID (public, include/cm3p_hip.h)
+// 7 = CM3P_EPI_BF16_RESID, 9 = CM3P_EPI_BF16_GEGLU_FWD, 10 = CM3P_EPI_BF16_GEGLU_BWD (public, include/cm3p_hip.h; 8 is not assigned)
 
 // Strided-batch offsets (elements) and the AXPBY epilogue operands of the 128 x 128 GEMM kernel.
 struct BatchArgs {
     int64_t a_stride = 0, b_stride = 0, c_stride = 0, r_stride = 0;
     const uint16_t* Rb = nullptr;
     float alpha = 1.f, beta = 0.f;
+    void* C2 = nullptr;  // second output of CM3P_EPI_BF16_GEGLU_FWD (a [M, N / 2] bf16); no batch has one
 };
 
 // Cache policy of write-once / read-once global traffic.  A plain store leaves its line in the XCD's 4 MiB L2, where it pushes out
@@ -247,6 +248,35 @@ __device__ __forceinline__ float bf16hi(uint32_t w) { return __builtin_bit_cast(
 // bf16 + bf16 of two packed pairs, added in fp32 and rounded once (torch's bf16 add): the CM3P_EPI_BF16_RESID epilogues
 __device__ __forceinline__ uint32_t add_bf16x2(uint32_t a, uint32_t b) { return pack_bf16x2(bf16lo(a) + bf16lo(b), bf16hi(a) + bf16hi(b)); }
 
+// ---- 8 bf16 <-> 8 floats, and one item of the GeGLU backward (the element kernels of elementwise.hip and the Wo2 dgrad's store
+// phase in gemm8p.hip, CM3P_EPI_BF16_GEGLU_BWD: one definition, same bits) ----------------------------------------------------------
+__device__ __forceinline__ void unpack8(const uint4 w, float (&f)[8]) {
+    f[0] = bf16lo(w.x); f[1] = bf16hi(w.x); f[2] = bf16lo(w.y); f[3] = bf16hi(w.y);
+    f[4] = bf16lo(w.z); f[5] = bf16hi(w.z); f[6] = bf16lo(w.w); f[7] = bf16hi(w.w);
+}
+__device__ __forceinline__ uint4 pack8(const float (&f)[8]) {
+    return uint4{pack_bf16x2(f[0], f[1]), pack_bf16x2(f[2], f[3]), pack_bf16x2(f[4], f[5]), pack_bf16x2(f[6], f[7])};
+}
+// 8 columns of one row, the incoming gradient already widened: ha / hb = the gate / up halves of h, oa / ob = those of dh
+__device__ __forceinline__ void geglu_bwd_item_f(const uint4 ha, const uint4 hb, const float (&d)[8], uint4& oa, uint4& ob) {
+    float a[8], b[8], da[8], db[8];
+    unpack8(ha, a);
+    unpack8(hb, b);
+#pragma unroll
+    for (int j = 0; j < 8; j += 2) {  // gelu'(a) = Phi(a) + a phi(a), gelu(a) = a Phi(a): one Phi for both
+        const f32x2 av = {a[j], a[j + 1]};
+        f32x2 cdf, pdf;
+        gelu_cdf_pdf2(av, cdf, pdf);
+        const f32x2 gr = av * pdf + cdf, gl = av * cdf;
+        da[j] = d[j] * b[j] * gr.x;
+        da[j + 1] = d[j + 1] * b[j + 1] * gr.y;
+        db[j] = d[j] * gl.x;
+        db[j + 1] = d[j + 1] * gl.y;
+    }
+    oa = pack8(da);
+    ob = pack8(db);
+}
+
 // Rotary tables for epilogue fusion: cos/sin are [n_pos, 32] fp32; a token row m uses table row (per_batch ? m : m % S);
 // only the first `ncols` output columns (the q and k thirds of a packed qkv row) are rotated.
 struct RopeArgs {
@@ -304,13 +334,18 @@ int cm3p_with_epilogue(int epi, F&& f) {
         case CM3P_EPI_F32_BIAS: return f(std::integral_constant<int, CM3P_EPI_F32_BIAS>{});
         case CM3P_EPI_BF16_GEGLU: return f(std::integral_constant<int, CM3P_EPI_BF16_GEGLU>{});
         case CM3P_EPI_BF16_RESID: return f(std::integral_constant<int, CM3P_EPI_BF16_RESID>{});
+        case CM3P_EPI_BF16_GEGLU_FWD: return f(std::integral_constant<int, CM3P_EPI_BF16_GEGLU_FWD>{});
+        case CM3P_EPI_BF16_GEGLU_BWD: return f(std::integral_constant<int, CM3P_EPI_BF16_GEGLU_BWD>{});
         default: return CM3P_ERR_INTERNAL;
     }
 }
 // (layout, epilogue) pairs that exist in all three kernels or in none: the rotary, bias and GeGLU epilogues are written for the
 // forward orientation only
+constexpr bool cm3p_epi_is_geglu(int epi) {  // the ring's three GeGLU store phases (no other kernel has them)
+    return epi == CM3P_EPI_BF16_GEGLU || epi == CM3P_EPI_BF16_GEGLU_FWD || epi == CM3P_EPI_BF16_GEGLU_BWD;
+}
 constexpr bool cm3p_gemm_pair_exists(bool a_kc, bool b_kc, int epi) {
-    return (epi != CM3P_EPI_BF16_ROPE && epi != CM3P_EPI_F32_BIAS && epi != CM3P_EPI_BF16_GEGLU) || (a_kc && b_kc);
+    return (epi != CM3P_EPI_BF16_ROPE && epi != CM3P_EPI_F32_BIAS && !cm3p_epi_is_geglu(epi)) || (a_kc && b_kc);
 }
 
 // a = head dims [d, d+3], b = head dims [d+32, d+35] of one token (d < 32): rotate_half convention

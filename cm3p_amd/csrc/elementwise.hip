@@ -18,13 +18,7 @@ inline int ew_grid(int64_t items, int per_block = 256) {
 }
 
 // (the GELU itself: gelu_erf2 / gelu_cdf_pdf2 in common.h)
-__device__ __forceinline__ void unpack8(const uint4 w, float (&f)[8]) {
-    f[0] = bf16lo(w.x); f[1] = bf16hi(w.x); f[2] = bf16lo(w.y); f[3] = bf16hi(w.y);
-    f[4] = bf16lo(w.z); f[5] = bf16hi(w.z); f[6] = bf16lo(w.w); f[7] = bf16hi(w.w);
-}
-__device__ __forceinline__ uint4 pack8(const float (&f)[8]) {
-    return uint4{pack_bf16x2(f[0], f[1]), pack_bf16x2(f[2], f[3]), pack_bf16x2(f[4], f[5]), pack_bf16x2(f[6], f[7])};
-}
+// (unpack8 / pack8: common.h)
 
 __global__ __launch_bounds__(256) void cast_f32_bf16_kernel(const float* __restrict__ x, uint16_t* __restrict__ y, int64_t n4) {
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) {
@@ -80,7 +74,11 @@ __global__ __launch_bounds__(256) void cast_f32_bf16_t_multi_kernel(const int64_
     const float* x = reinterpret_cast<const float*>(table[6 * lo]);
     uint16_t* y = reinterpret_cast<uint16_t*>(table[6 * lo + 1]);
     uint16_t* yt = reinterpret_cast<uint16_t*>(table[6 * lo + 2]);
-    const int rows = (int)table[6 * lo + 3], cols = (int)table[6 * lo + 4];
+    // rows < 0: a Wi weight [2 I, cols] whose bf16 copy is written in the row order of the ring's GeGLU store phases (every 64 rows are
+    // 32 gate rows and the 32 matching up rows: include/cm3p_hip.h, cm3p_gemm_geglu); the transposed copy stays canonical
+    const int rows_arg = (int)table[6 * lo + 3], cols = (int)table[6 * lo + 4];
+    const bool interleave = rows_arg < 0;
+    const int rows = interleave ? -rows_arg : rows_arg, half = rows >> 1;
     const int blk = (int)((int64_t)blockIdx.x - table[6 * lo + 5]);
     const int tiles_c = (cols + 63) / 64;
     const int r0 = (blk / tiles_c) * 64, c0 = (blk % tiles_c) * 64;
@@ -91,7 +89,9 @@ __global__ __launch_bounds__(256) void cast_f32_bf16_t_multi_kernel(const int64_
         if (r0 + r < rows && c0 + c < cols) {
             const f32x4 v = *reinterpret_cast<const f32x4*>(x + (int64_t)(r0 + r) * cols + c0 + c);
             const uint32_t lo2 = pack_bf16x2(v.x, v.y), hi2 = pack_bf16x2(v.z, v.w);
-            *reinterpret_cast<uint2*>(y + (int64_t)(r0 + r) * cols + c0 + c) = uint2{lo2, hi2};
+            int yr = r0 + r;
+            if (interleave) yr = yr < half ? (yr >> 5) * 64 + (yr & 31) : ((yr - half) >> 5) * 64 + 32 + ((yr - half) & 31);
+            *reinterpret_cast<uint2*>(y + (int64_t)yr * cols + c0 + c) = uint2{lo2, hi2};
             tile[r][c] = (uint16_t)lo2;
             tile[r][c + 1] = (uint16_t)(lo2 >> 16);
             tile[r][c + 2] = (uint16_t)hi2;
@@ -271,26 +271,7 @@ __global__ __launch_bounds__(256) void geglu_fwd_kernel(const uint16_t* __restri
     }
 }
 
-// one item of the GeGLU backward: 8 columns of one row, the incoming gradient already widened
-__device__ __forceinline__ void geglu_bwd_item_f(const uint4 ha, const uint4 hb, const float (&d)[8], uint4& oa, uint4& ob) {
-    float a[8], b[8], da[8], db[8];
-    unpack8(ha, a);
-    unpack8(hb, b);
-#pragma unroll
-    for (int j = 0; j < 8; j += 2) {  // gelu'(a) = Phi(a) + a phi(a), gelu(a) = a Phi(a): one Phi for both
-        const f32x2 av = {a[j], a[j + 1]};
-        f32x2 cdf, pdf;
-        gelu_cdf_pdf2(av, cdf, pdf);
-        const f32x2 gr = av * pdf + cdf, gl = av * cdf;
-        da[j] = d[j] * b[j] * gr.x;
-        da[j + 1] = d[j + 1] * b[j + 1] * gr.y;
-        db[j] = d[j] * gl.x;
-        db[j + 1] = d[j + 1] * gl.y;
-    }
-    oa = pack8(da);
-    ob = pack8(db);
-}
-
+// one item of the GeGLU backward (geglu_bwd_item_f: common.h, shared with the Wo2 dgrad's store phase in gemm8p.hip)
 __device__ __forceinline__ void geglu_bwd_item(const uint4 ha, const uint4 hb, const uint4 hd, uint4& oa, uint4& ob) {
     float d[8];
     unpack8(hd, d);

@@ -233,7 +233,7 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restr
 
 // the pairs this file instantiates: every layout with the plain and AXPBY epilogues, the forward layout with the rotary and bias ones
 template <bool A_KC, bool B_KC, int EPI>
-constexpr bool has_instance = cm3p_gemm_pair_exists(A_KC, B_KC, EPI) && EPI != CM3P_EPI_BF16_GEGLU;
+constexpr bool has_instance = cm3p_gemm_pair_exists(A_KC, B_KC, EPI) && !cm3p_epi_is_geglu(EPI);
 
 int launch128(const GemmRoute& r, const GemmCall& g, hipStream_t s) {
     const int tiles_m = (int)((g.M + BM - 1) / BM), tiles_n = (int)((g.N + BN - 1) / BN);
@@ -278,6 +278,9 @@ constexpr int64_t kBigItems = 200, kBigBatchItems = 128;
 //   of the two 256 x 256 kernels the ring (gemm8p_kernel) where it can run: M and N multiples of 8 (it clamps whole 16-byte pieces)
 //     and 16 rows of either operand inside its 32-bit lane offsets; gemm256_kernel otherwise.  A batch has the ring only (in the three
 //     layouts of the Muon step) and the GeGLU epilogue has the ring only: a call outside cm3p_gemm_geglu's shapes is refused.
+//     The two GeGLU store phases of a training step (CM3P_EPI_BF16_GEGLU_FWD / _BWD through cm3p_gemm_bf16) have the ring only as
+//     well and are refused everywhere else, under either development switch too: their caller asks cm3p_gemm_route first and keeps
+//     the two-kernel path unless both calls land on the ring.  Epilogue number 8 is not assigned and is refused.
 //   REBAL (the ring's instances that read B-lo one phase early): every work item has an even number of 64-deep k-tiles.
 // Development switches.  CM3P_GEMM_IMPL, read on every call so that one process can A/B: 256 = gemm256_kernel (the r01 kernel) in
 // place of the ring - a batch then runs on the 128 x 128 kernel and a GeGLU route names gemm256_kernel, which tells the caller to
@@ -287,7 +290,7 @@ static GemmRoute cm3p_gemm_route_of(int64_t M, int64_t N, int64_t K, int64_t lda
                                     int split_k, int rope_cols, int batch) {
     GemmRoute r{CM3P_GEMM_128, false, 1, K};
     const bool batched = epi == CM3P_EPI_BF16_AXPBY;
-    if (M <= 0 || N <= 0 || K <= 0 || split_k < 1 || epi < 0 || epi > CM3P_EPI_BF16_RESID || batched != (batch > 0) ||
+    if (M <= 0 || N <= 0 || K <= 0 || split_k < 1 || epi < 0 || epi > CM3P_EPI_BF16_GEGLU_BWD || epi == 8 /* not assigned */ || batched != (batch > 0) ||
         !cm3p_gemm_pair_exists(a_kc, b_kc, epi)) {
         r.kernel = CM3P_ERR_INVALID;
         return r;
@@ -308,6 +311,11 @@ static GemmRoute cm3p_gemm_route_of(int64_t M, int64_t N, int64_t K, int64_t lda
     if (epi == CM3P_EPI_BF16_GEGLU) {
         if (!(big && N % 64 == 0 && ring_ok)) r.kernel = CM3P_ERR_INVALID;  // (N = 2 I, I a multiple of 32)
         else r.kernel = no_ring ? CM3P_GEMM_256 : CM3P_GEMM_RING;
+    } else if (epi == CM3P_EPI_BF16_GEGLU_FWD || epi == CM3P_EPI_BF16_GEGLU_BWD) {
+        // the training step's two GeGLU store phases: forward N = 2 I, backward N = I, I a multiple of 32; the ring or nothing (no
+        // split, and neither development switch has another kernel to offer: the caller keeps its two-kernel path)
+        const int64_t cols = epi == CM3P_EPI_BF16_GEGLU_FWD ? 64 : 32;
+        r.kernel = (big && N % cols == 0 && ring_ok && split_k == 1 && !no_ring && !small_only) ? CM3P_GEMM_RING : CM3P_ERR_INVALID;
     } else if (batched) {
         const bool filled = M * N * batch * 10 >= items * 65536 * 7;
         big = big && filled && (a_kc || !b_kc) && ring_ok && !no_ring;
@@ -409,19 +417,26 @@ int cm3p_qkv_gemm_rope(const void* x, const void* Wqkv, void* qkv, int64_t M, in
 int cm3p_gemm_bf16(const void* A, const void* B, void* C, const float* R, int64_t M, int64_t N, int64_t K, int64_t lda,
                    int64_t ldb, int64_t ldc, int a_kc, int b_kc, int epilogue, int split_k, float* workspace, void* stream) {
     CM3P_REQUIRE(A && B && C && M > 0 && N > 0 && K > 0);
-    CM3P_REQUIRE((epilogue >= CM3P_EPI_BF16 && epilogue <= CM3P_EPI_F32_RESID) || epilogue == CM3P_EPI_F32_BIAS || epilogue == CM3P_EPI_BF16_RESID);
+    const bool geglu_fwd = epilogue == CM3P_EPI_BF16_GEGLU_FWD, geglu_bwd = epilogue == CM3P_EPI_BF16_GEGLU_BWD;
+    CM3P_REQUIRE((epilogue >= CM3P_EPI_BF16 && epilogue <= CM3P_EPI_F32_RESID) || epilogue == CM3P_EPI_F32_BIAS || epilogue == CM3P_EPI_BF16_RESID ||
+                 geglu_fwd || geglu_bwd);
     CM3P_REQUIRE(cm3p_aligned16(A) && cm3p_aligned16(B) && cm3p_aligned16(C));
     CM3P_REQUIRE(lda % 8 == 0 && ldb % 8 == 0 && ldc % 4 == 0 && N % 4 == 0);
     CM3P_REQUIRE(a_kc ? (K % 8 == 0 && lda >= K) : (M % 8 == 0 && lda >= M));
     CM3P_REQUIRE(b_kc ? (K % 8 == 0 && ldb >= K) : (N % 8 == 0 && ldb >= N));
     CM3P_REQUIRE(ldc >= N);  // (ldc % 4 == 0 above is all the bf16 stores ask for: gemm256.hip on rows that are 8-byte aligned only)
-    CM3P_REQUIRE((epilogue != CM3P_EPI_F32_RESID && epilogue != CM3P_EPI_F32_BIAS && epilogue != CM3P_EPI_BF16_RESID) || (R && cm3p_aligned16(R)));
+    CM3P_REQUIRE((epilogue != CM3P_EPI_F32_RESID && epilogue != CM3P_EPI_F32_BIAS && epilogue != CM3P_EPI_BF16_RESID && !geglu_bwd) || (R && cm3p_aligned16(R)));
+    // the training step's GeGLU store phases: forward C = h' [M, N] and workspace = a [M, N / 2] (both written), backward C = dh
+    // [M, 2 N] and R = h' [M, 2 N]; dense rows (the second matrix has no pitch argument of its own)
+    CM3P_REQUIRE(!geglu_fwd || (workspace && cm3p_aligned16(workspace) && ldc == N && N % 64 == 0 && split_k == 1));
+    CM3P_REQUIRE(!geglu_bwd || (ldc == 2 * N && N % 32 == 0 && split_k == 1));
     CM3P_REQUIRE(epilogue != CM3P_EPI_BF16_RESID || (N % 8 == 0 && ldc % 8 == 0));  // (16-byte bf16 row chunks in the 256 x 256 kernels)
     CM3P_REQUIRE(split_k >= 1 && (split_k == 1 || (epilogue == CM3P_EPI_F32 && workspace && cm3p_aligned16(workspace) && ldc == N)));
     const GemmRoute r = cm3p_gemm_route_of(M, N, K, lda, ldb, a_kc != 0, b_kc != 0, epilogue, split_k, 0, 0);
     CM3P_REQUIRE(r.kernel >= 0);  // (the bias epilogue exists in the forward layout only)
     hipStream_t s = static_cast<hipStream_t>(stream);
     GemmCall g{A, B, C, R, M, N, K, lda, ldb, ldc, a_kc != 0, b_kc != 0, epilogue};
+    if (geglu_fwd) g.bt.C2 = workspace;
     if (r.splits > 1) {
         g.C = workspace;
         g.c_split_stride = M * N;

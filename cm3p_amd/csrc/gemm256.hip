@@ -413,7 +413,7 @@ __global__ __launch_bounds__(kThreads, kWN == 4 ? 2 : 1) void gemm256_kernel(con
 
 // the pairs this file instantiates: every layout with the plain epilogues, the forward layout with the rotary and bias ones
 template <bool A_KC, bool B_KC, int EPI>
-constexpr bool has_instance = cm3p_gemm_pair_exists(A_KC, B_KC, EPI) && EPI != CM3P_EPI_BF16_GEGLU && EPI != CM3P_EPI_BF16_AXPBY;
+constexpr bool has_instance = cm3p_gemm_pair_exists(A_KC, B_KC, EPI) && !cm3p_epi_is_geglu(EPI) && EPI != CM3P_EPI_BF16_AXPBY;
 
 }  // namespace
 

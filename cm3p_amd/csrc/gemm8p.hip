@@ -512,6 +512,107 @@ __global__ __launch_bounds__(512, 2) void gemm8p_kernel(const uint16_t* __restri
                     G8P_GLOBAL(gstore16<(CM3P_NT & 1) != 0>(Cb + (uint32_t)(i4 * 16 + row) * ldcb + dc * 16, y));
                 if constexpr (CM3P_G8P_ABL & 1) asm volatile("" ::"v"(y));
             }
+        } else if constexpr (EPI == CM3P_EPI_BF16_GEGLU_FWD) {
+            // The Wi projection of a training step: the staged bf16 rows leave twice.  As they are, whole 128-byte lines to
+            // h' = C [M, N] (the plain bf16 store path; its columns are in the interleaved order of the weight rows, which is
+            // what the backward's store phase below reads), and as gelu_erf(gate) * up to a = bt.C2 [M, N / 2] (the GeGLU epilogue
+            // above: same lanes, same roundings).  ldc == N (checked by the entry point): a's row pitch is ldc / 2 elements.
+            char* Cb = reinterpret_cast<char*>(static_cast<uint16_t*>(Cv) + mw * ldc + nw);
+            char* Ab = reinterpret_cast<char*>(static_cast<uint16_t*>(bt.C2) + mw * (ldc / 2) + nw / 2);
+            const uint32_t ldcb = (uint32_t)ldc * 2, ldab = (uint32_t)ldc;
+#pragma unroll
+            for (int i4 = 0; i4 < 8; ++i4) {
+                char* eb = ebuf + (i4 & 1) * 2048;
+#pragma unroll
+                for (int j4 = 0; j4 < 4; ++j4) {
+                    const f32x4 a = acc[i4][j4];
+                    const int row = lane & 15, s8 = (j4 * 4 + (lane >> 4)) ^ ((row & 7) << 1);
+                    *reinterpret_cast<uint2*>(eb + row * 128 + s8 * 8) = uint2{pack_bf16x2(a.x, a.y), pack_bf16x2(a.z, a.w)};
+                }
+                G8P_LANE_XCHG_FENCE();
+                const int r0 = lane >> 3, r1 = 8 + (lane >> 3), ch = lane & 7;
+                const int row = lane >> 2, dc = lane & 3;
+                const u32x4 x0 = *reinterpret_cast<const u32x4*>(eb + r0 * 128 + ((ch ^ (r0 & 7)) << 4));
+                const u32x4 x1 = *reinterpret_cast<const u32x4*>(eb + r1 * 128 + ((ch ^ (r1 & 7)) << 4));
+                const u32x4 xh = *reinterpret_cast<const u32x4*>(eb + row * 128 + ((dc ^ (row & 7)) << 4));
+                const u32x4 xg = *reinterpret_cast<const u32x4*>(eb + row * 128 + (((dc + 4) ^ (row & 7)) << 4));
+                G8P_LANE_XCHG_FENCE();
+                const bool col_ok = FULL || nw + ch * 8 < N;
+                if (FULL || (col_ok && mw + i4 * 16 + r0 < M)) G8P_GLOBAL(gstore16<(CM3P_NT & 1) != 0>(Cb + (uint32_t)(i4 * 16 + r0) * ldcb + ch * 16, x0));
+                if (FULL || (col_ok && mw + i4 * 16 + r1 < M)) G8P_GLOBAL(gstore16<(CM3P_NT & 1) != 0>(Cb + (uint32_t)(i4 * 16 + r1) * ldcb + ch * 16, x1));
+                u32x4 y;
+#pragma unroll
+                for (int t = 0; t < 4; ++t) {  // (gelu_erf2: common.h, the function cm3p_geglu_fwd evaluates - same bits)
+                    const f32x2 gl = gelu_erf2(f32x2{bf16lo(xh[t]), bf16hi(xh[t])});
+                    y[t] = pack_bf16x2(gl.x * bf16lo(xg[t]), gl.y * bf16hi(xg[t]));
+                }
+                if (FULL || (mw + i4 * 16 + row < M && nw + dc * 8 < N))
+                    G8P_GLOBAL(gstore16<(CM3P_NT & 1) != 0>(Ab + (uint32_t)(i4 * 16 + row) * ldab + dc * 16, y));
+                if constexpr (CM3P_G8P_ABL & 1) asm volatile("" ::"v"(x0), "v"(x1), "v"(y));
+            }
+        } else if constexpr (EPI == CM3P_EPI_BF16_GEGLU_BWD) {
+            // The Wo2 input gradient dg = g Wo2 (N = I) with the GeGLU backward in its store phase: dg is never written.  A lane takes
+            // the 8 staged dg columns it would have stored (rounded to bf16, as the stored dg was), reads gate and up of the same
+            // columns from h' = R [M, 2 N] bf16 in the interleaved order the forward's store phase above wrote - the wave's 64
+            // columns are two whole lines of an h' row, [32 gate | 32 up] each - and stores dh = C [M, 2 N] in CANONICAL order
+            // (gate at column n, up at N + n: what the Wi dgrad and wgrad contract over), 16-byte pieces that form whole lines where
+            // N * 2 bytes is a multiple of 128.  ldc == 2 N (checked by the entry point) is the pitch of both.  The h' rows of
+            // step i4 + 1 are requested before step i4 computes (an exposed epilogue waits out every round trip it does not hide).
+            char* Cb = reinterpret_cast<char*>(static_cast<uint16_t*>(Cv) + mw * ldc + nw);
+            const char* Hb = reinterpret_cast<const char*>(reinterpret_cast<const uint16_t*>(R) + mw * ldc + 2 * nw);
+            const uint32_t ldcb = (uint32_t)ldc * 2, upb = (uint32_t)N * 2;
+            const int r0 = lane >> 3, ch = lane & 7;
+            const uint32_t hoff = (uint32_t)((ch >> 2) * 128 + (ch & 3) * 16);  // gate chunk inside the wave's two lines; up: + 64 bytes
+            const bool col_ok = FULL || nw + ch * 8 < N;
+            u32x4 ga0, up0, ga1, up1;  // gate / up chunks of rows r0 and r0 + 8 of the next step
+            auto load_h = [&](int i4) {
+                const bool ok0 = FULL || (col_ok && mw + i4 * 16 + r0 < M), ok1 = FULL || (col_ok && mw + i4 * 16 + 8 + r0 < M);
+                const char* p0 = Hb + (uint32_t)(i4 * 16 + r0) * ldcb + hoff;
+                const char* p1 = Hb + (uint32_t)(i4 * 16 + 8 + r0) * ldcb + hoff;
+                const u32x4 zero = {0u, 0u, 0u, 0u};
+                if constexpr (CM3P_G8P_ABL & 1) {
+                    asm volatile("" : "=v"(ga0), "=v"(up0), "=v"(ga1), "=v"(up1) : "v"(p0), "v"(p1));
+                } else {
+                    ga0 = ok0 ? __builtin_bit_cast(u32x4, gload16<(CM3P_NT & 64) != 0>(p0)) : zero;
+                    up0 = ok0 ? __builtin_bit_cast(u32x4, gload16<(CM3P_NT & 64) != 0>(p0 + 64)) : zero;
+                    ga1 = ok1 ? __builtin_bit_cast(u32x4, gload16<(CM3P_NT & 64) != 0>(p1)) : zero;
+                    up1 = ok1 ? __builtin_bit_cast(u32x4, gload16<(CM3P_NT & 64) != 0>(p1 + 64)) : zero;
+                }
+            };
+            load_h(0);
+#pragma unroll
+            for (int i4 = 0; i4 < 8; ++i4) {
+                char* eb = ebuf + (i4 & 1) * 2048;
+#pragma unroll
+                for (int j4 = 0; j4 < 4; ++j4) {
+                    const f32x4 a = acc[i4][j4];
+                    const int row = lane & 15, s8 = (j4 * 4 + (lane >> 4)) ^ ((row & 7) << 1);
+                    *reinterpret_cast<uint2*>(eb + row * 128 + s8 * 8) = uint2{pack_bf16x2(a.x, a.y), pack_bf16x2(a.z, a.w)};
+                }
+                G8P_LANE_XCHG_FENCE();
+                const int r1 = 8 + r0;
+                const u32x4 x0 = *reinterpret_cast<const u32x4*>(eb + r0 * 128 + ((ch ^ (r0 & 7)) << 4));
+                const u32x4 x1 = *reinterpret_cast<const u32x4*>(eb + r1 * 128 + ((ch ^ (r1 & 7)) << 4));
+                G8P_LANE_XCHG_FENCE();
+                const u32x4 g0 = ga0, u0 = up0, g1 = ga1, u1 = up1;
+                if (i4 < 7) load_h(i4 + 1);
+                float d[8];
+                uint4 oa, ob;
+                unpack8(uint4{x0[0], x0[1], x0[2], x0[3]}, d);
+                geglu_bwd_item_f(uint4{g0[0], g0[1], g0[2], g0[3]}, uint4{u0[0], u0[1], u0[2], u0[3]}, d, oa, ob);
+                if (FULL || (col_ok && mw + i4 * 16 + r0 < M)) {
+                    G8P_GLOBAL(gstore16<(CM3P_NT & 1) != 0>(Cb + (uint32_t)(i4 * 16 + r0) * ldcb + ch * 16, oa));
+                    G8P_GLOBAL(gstore16<(CM3P_NT & 1) != 0>(Cb + (uint32_t)(i4 * 16 + r0) * ldcb + upb + ch * 16, ob));
+                }
+                if constexpr (CM3P_G8P_ABL & 1) asm volatile("" ::"v"(oa.x), "v"(ob.x));
+                unpack8(uint4{x1[0], x1[1], x1[2], x1[3]}, d);
+                geglu_bwd_item_f(uint4{g1[0], g1[1], g1[2], g1[3]}, uint4{u1[0], u1[1], u1[2], u1[3]}, d, oa, ob);
+                if (FULL || (col_ok && mw + i4 * 16 + r1 < M)) {
+                    G8P_GLOBAL(gstore16<(CM3P_NT & 1) != 0>(Cb + (uint32_t)(i4 * 16 + r1) * ldcb + ch * 16, oa));
+                    G8P_GLOBAL(gstore16<(CM3P_NT & 1) != 0>(Cb + (uint32_t)(i4 * 16 + r1) * ldcb + upb + ch * 16, ob));
+                }
+                if constexpr (CM3P_G8P_ABL & 1) asm volatile("" ::"v"(oa.x), "v"(ob.x));
+            }
         } else if constexpr (EPI == CM3P_EPI_BF16_AXPBY) {
             // C_z = bf16(alpha * acc + beta * R_z), R bf16 with C's layout (the Newton-Schulz polynomial steps of the Muon update):
             // the fp32 rows of the exchange below, combined in fp32 and rounded once (the arithmetic of gemm.hip's small-tile kernel)
@@ -646,7 +747,7 @@ __global__ __launch_bounds__(512, 2) void gemm8p_kernel(const uint16_t* __restri
 }
 
 // the pairs this file instantiates (each with and without REBAL): every layout with the plain epilogues, the forward layout with the
-// rotary, bias and GeGLU ones, the Muon step's three layouts with AXPBY
+// rotary, bias and the three GeGLU ones (forward-only, training forward, training backward), the Muon step's three layouts with AXPBY
 template <bool A_KC, bool B_KC, int EPI>
 constexpr bool has_instance = cm3p_gemm_pair_exists(A_KC, B_KC, EPI) && (EPI != CM3P_EPI_BF16_AXPBY || A_KC || !B_KC);
 

@@ -16,6 +16,11 @@ TF:models/modernbert/modeling_modernbert.py:262-333,434-478:
 Numerics: the residual stream, LayerNorm statistics, softmax and all accumulations are fp32; GEMM operands and saved
 activations are bf16 (what HF Trainer's bf16 autocast gives the reference's nn.Linear calls).
 
+GeGLU of a training step: where the library's route names the ring GEMM for both calls (the beatmap tower's shapes), no MLP dropout is
+planned and CM3P_GEGLU_FUSED is not "0", `h = xn Wi^T` and `g = gelu(h[:I]) * h[I:]` are one launch (K.linear_geglu_fwd: h is kept with
+interleaved columns) and the backward's `dg = dy Wo` never exists (K.linear_dgrad_geglu_bwd turns it into the canonical dh in the GEMM's
+store phase); loss, output and gradients are those of the two-kernel path bit for bit.
+
 Dropout (training mode, p > 0): embedding output, attention probabilities (inside the attention kernels), attention output before
 the residual add, and gelu(h[:I]) * h[I:] before Wo - the masks follow csrc/dropout_rng.h from one seed per stack forward.
 
@@ -166,7 +171,7 @@ class _Geometry:
     """Static description of one forward call of the stack (no tensors that need grad)."""
 
     __slots__ = ("B", "S", "H", "I", "nh", "L", "eps", "windows", "key_mask", "rope", "per_batch_pos", "save", "cu", "max_s", "checkpoint",
-                 "handoff", "attn_out", "wcast", "hd", "drop", "bf16")
+                 "handoff", "attn_out", "wcast", "hd", "drop", "bf16", "fused_mlp")
 
 
 def _hand_upstream(geo: _Geometry, gx32: Tensor, gx16: Optional[Tensor]) -> None:
@@ -239,6 +244,8 @@ def _layer_forward(geo: _Geometry, i: int, x: Tensor, wb, want_stats: bool):
     _, xn2, mean_m, rstd_m = K.layernorm_fwd(x_mid, w_mn, geo.eps, False, True, want_stats)
     if len(wb) > 6 and wb[6] is not None:  # forward-only call: Wi and GeGLU in one kernel, h and g never exist (bit-identical a)
         h, g = None, K.gemm_geglu(xn2, wb[6])
+    elif len(wb) > 7 and wb[7]:  # training step, fused pair: Wi_b has interleaved rows and the GEMM stores h' (interleaved columns) and g
+        h, g = K.linear_geglu_fwd(xn2, Wi_b)
     else:
         h = K.linear_fwd(xn2, Wi_b)
         if geo.drop is not None and geo.drop.mlp:  # g o Z: what Wo and its weight gradient read (TF:...modeling_modernbert.py:91)
@@ -280,7 +287,9 @@ class _EncoderLayerFn(torch.autograd.Function):
         # (training: the casts of every layer were made in one launch at the top of the stack, _run_stack)
         pre = geo.wcast if geo.save and geo.wcast is not None else {}
         pairs = [pre.get(id(w)) or _bf16_weight_pair(w, geo.save) if not (fuse_geglu and w is Wi) else (None, None) for w in (Wqkv, Wo, Wi, Wo2)]
-        wb = (w_an, pairs[0][0], pairs[1][0], w_mn, pairs[2][0], pairs[3][0], _bf16_weight_cached(Wi, True) if fuse_geglu else None)
+        # training step, fused pair (_run_stack decided; CM3P_GEGLU_FUSED=0: the two-kernel path): this Wi's copy has interleaved rows
+        fused_train = geo.save and id(Wi) in geo.fused_mlp
+        wb = (w_an, pairs[0][0], pairs[1][0], w_mn, pairs[2][0], pairs[3][0], _bf16_weight_cached(Wi, True) if fuse_geglu else None, fused_train)
         x_out, acts = _layer_forward(geo, i, x, wb, geo.save)
         if geo.save:
             # gradient checkpointing (ref: supports_gradient_checkpointing, TF GradientCheckpointingLayer): keep only the
@@ -310,13 +319,15 @@ class _EncoderLayerFn(torch.autograd.Function):
             acts = ctx.saved
         x, xn, mean_a, rstd_a, qkv, o, lse, x_mid, xn2, mean_m, rstd_m, h, ga = acts
         del acts
-        w_an, Wqkv_b, Wo_b, w_mn, Wi_b, Wo2_b = ctx.wb[:6]
+        ctx_wb = ctx.wb
+        w_an, Wqkv_b, Wo_b, w_mn, Wi_b, Wo2_b = ctx_wb[:6]
         Wqkv_t, Wo_t, Wi_t, Wo2_t = ctx.wt
         ctx.saved = ctx.wb = ctx.wt = None  # release activations as we go
         # ---- MLP branch: x_out = x_mid + g Wo2^T
-        dg = K.linear_dgrad(g, Wo2_b, Wo2_t)
+        fused = len(ctx_wb) > 7 and ctx_wb[7]  # h is h' (interleaved columns): the Wo2 dgrad's store phase turns dg into the canonical dh
+        dg = None if fused else K.linear_dgrad(g, Wo2_b, Wo2_t)
         dWo2 = K.linear_wgrad(g, ga) if n_o2 else None
-        dh = K.geglu_bwd(dg, h)
+        dh = K.linear_dgrad_geglu_bwd(g, Wo2_t, h) if fused else K.geglu_bwd(dg, h)
         del dg, ga
         dxn2 = K.linear_dgrad(dh, Wi_b, Wi_t)
         dWi = K.linear_wgrad(dh, xn2) if n_i else None
@@ -360,13 +371,17 @@ class _EncoderLayerFn(torch.autograd.Function):
             acts = ctx.saved
         x, xn, mean_a, rstd_a, qkv, o, lse, x_mid, xn2, mean_m, rstd_m, h, g = acts
         del acts
-        w_an, Wqkv_b, Wo_b, w_mn, Wi_b, Wo2_b = ctx.wb[:6]
+        ctx_wb = ctx.wb
+        w_an, Wqkv_b, Wo_b, w_mn, Wi_b, Wo2_b = ctx_wb[:6]
         Wqkv_t, Wo_t, Wi_t, Wo2_t = ctx.wt
         ctx.saved = ctx.wb = ctx.wt = None  # release activations as we go
         # ---- MLP branch: x_out = x_mid + g Wo2^T
-        dg = K.linear_dgrad(gx16, Wo2_b, Wo2_t)
+        fused = len(ctx_wb) > 7 and ctx_wb[7]  # h is h' (interleaved columns): the Wo2 dgrad's store phase turns dg into the canonical dh
+        dg = None if fused else K.linear_dgrad(gx16, Wo2_b, Wo2_t)
         dWo2 = K.linear_wgrad(gx16, g) if n_o2 else None
-        if geo.drop is not None and geo.drop.mlp:
+        if fused:
+            dh = K.linear_dgrad_geglu_bwd(gx16, Wo2_t, h)
+        elif geo.drop is not None and geo.drop.mlp:
             dh = K.geglu_bwd_dropout(dg, h, geo.drop.mlp, geo.drop.seed, i, geo.S, geo.cu)
         else:
             dh = K.geglu_bwd(dg, h)
@@ -778,12 +793,22 @@ class CM3PEncoder(nn.Module):
         if geo.save and _eval_weights:
             invalidate_weight_cache()  # a backward will follow, so an optimizer will: no copy made before this step may outlive it
         geo.wcast = None
+        geo.fused_mlp = frozenset()
         if geo.save and os.environ.get("CM3P_CAST_BATCHED", "1") != "0":
             # bf16 copies + transposes of every projection weight of the stack in ONE launch (r03: 4 launches per layer)
             elig = [w for ws in weights for w in ws
                     if w.dim() == 2 and w.dtype == torch.float32 and w.shape[0] % 8 == 0 and w.shape[1] % 8 == 0 and w.is_contiguous()]
             if elig:
-                geo.wcast = {id(w): pair for w, pair in zip(elig, K.cast_bf16_with_transpose_many([w.detach() for w in elig]))}
+                # GeGLU in the store phases of the Wi GEMM and the Wo2 dgrad (K.linear_geglu_fwd / K.linear_dgrad_geglu_bwd): taken by the
+                # layers whose Wi and Wo2 are cast here - the same launch then writes Wi's copy with interleaved rows; the canonical
+                # copy is not needed, the Wi dgrad reads Wi^T - when no MLP dropout is planned and the library's route names the ring
+                # for both calls.  CM3P_GEGLU_FUSED=0: the two-kernel path everywhere.
+                if not (plan is not None and plan.mlp) and os.environ.get("CM3P_GEGLU_FUSED", "1") != "0" \
+                        and K.mlp_geglu_fused_supported(x0.shape[0], cfg.intermediate_size, H):
+                    cast = {id(w) for w in elig}
+                    geo.fused_mlp = frozenset(id(ws[-2]) for ws in weights if id(ws[-2]) in cast and id(ws[-1]) in cast)
+                pairs = K.cast_bf16_with_transpose_many([w.detach() for w in elig], [id(w) in geo.fused_mlp for w in elig])
+                geo.wcast = {id(w): pair for w, pair in zip(elig, pairs)}
         geo.handoff = None
         geo.attn_out = [] if output_attentions else None
         # output_hidden_states: the stack's input and every layer's output (TF:...modeling_modernbert.py:457-470), detached

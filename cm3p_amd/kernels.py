@@ -11,7 +11,7 @@ from typing import Optional
 import torch
 
 from . import _lib
-from ._lib import ADD_A_BF16, BF16, GEMM_F32_TILED, POOL_PACKED, EPI_BF16, EPI_BF16_RESID, EPI_F32, EPI_F32_RESID, F32, call, dt, ptr, query, stream
+from ._lib import ADD_A_BF16, BF16, GEMM_F32_TILED, POOL_PACKED, EPI_BF16, EPI_BF16_GEGLU_BWD, EPI_BF16_GEGLU_FWD, EPI_BF16_RESID, EPI_F32, EPI_F32_RESID, F32, call, dt, ptr, query, stream
 
 Tensor = torch.Tensor
 
@@ -251,20 +251,25 @@ def cast_bf16_with_transpose(x: Tensor):
     return y, yt
 
 
-def cast_bf16_with_transpose_many(ws: list) -> list:
+def cast_bf16_with_transpose_many(ws: list, geglu_rows: Optional[list] = None) -> list:
     """[fp32 2-D weights, extents multiples of 8] -> [(bf16 copy, bf16 transpose)] in ONE launch (cm3p_cast_f32_bf16_t_multi): the values
-    of cast_bf16_with_transpose per matrix.  One bf16 allocation holds all copies; the address table travels with one small H2D copy."""
+    of cast_bf16_with_transpose per matrix.  One bf16 allocation holds all copies; the address table travels with one small H2D copy.
+    geglu_rows: one flag per matrix - a flagged Wi [2I, K] gets its bf16 copy in the row order of geglu_interleave_index (what
+    linear_geglu_fwd reads) instead of the canonical one; its transpose is the canonical W^T either way."""
     if not ws:
         return []
+    geglu_rows = geglu_rows or [False] * len(ws)
     dev = ws[0].device
     numel = sum(w.numel() for w in ws)
     store = torch.empty((2 * numel,), dtype=torch.bfloat16, device=dev)
     base, out, table, off, blocks = store.data_ptr(), [], [], 0, 0
-    for w in ws:
+    for w, il in zip(ws, geglu_rows):
         rows, cols = w.shape
+        if il and rows % 64:
+            raise ValueError(f"cast_bf16_with_transpose_many: interleaved GeGLU rows need 2I a multiple of 64, got {rows}")
         y = store[off:off + rows * cols].view(rows, cols)
         yt = store[off + rows * cols:off + 2 * rows * cols].view(cols, rows)
-        table += [w.data_ptr(), base + 2 * off, base + 2 * (off + rows * cols), rows, cols, blocks]
+        table += [w.data_ptr(), base + 2 * off, base + 2 * (off + rows * cols), -rows if il else rows, cols, blocks]
         out.append((y, yt))
         off += 2 * rows * cols
         blocks += (-(-rows // 64)) * (-(-cols // 64))
@@ -569,6 +574,38 @@ def gemm_geglu(x: Tensor, w_interleaved: Tensor) -> Tensor:
     call("cm3p_gemm_geglu", ptr(x), ptr(w_interleaved), ptr(a), T, I, Kd, stream(),
          tag=_gemm_tag(T, 2 * I, Kd, True, True, EPI_GEGLU, 1, kernel=_GEMM_RING), work=2.0 * T * 2 * I * Kd)
     return a
+
+
+def mlp_geglu_fused_supported(T: int, I: int, H: int) -> bool:
+    """Whether a training step's MLP of this shape takes the fused pair linear_geglu_fwd / linear_dgrad_geglu_bwd: the library's route
+    (cm3p_gemm_route) names the ring for both calls - the Wi projection [T, H] -> [T, 2I] and the Wo2 input gradient [T, H] -> [T, I]."""
+    fwd = query("cm3p_gemm_route", T, 2 * I, H, H, H, 1, 1, EPI_BF16_GEGLU_FWD, 1, 0, 0)
+    bwd = query("cm3p_gemm_route", T, I, H, H, H, 1, 1, EPI_BF16_GEGLU_BWD, 1, 0, 0)
+    return fwd >= 0 and (fwd & 3) == _GEMM_RING and bwd >= 0 and (bwd & 3) == _GEMM_RING
+
+
+def linear_geglu_fwd(x: Tensor, w_interleaved: Tensor):
+    """x [T,K] bf16, interleaved Wi [2I,K] bf16 (geglu_interleave_index) -> (h' [T,2I], a [T,I]) in one kernel: h' = x Wi^T with
+    its columns in the order of the weight rows (linear_fwd's h permuted by geglu_interleave_index) and a = geglu_fwd(h), bit for bit.
+    The Wi GEMM of a training step; linear_dgrad_geglu_bwd reads h'."""
+    T, Kd = x.shape
+    N = w_interleaved.shape[0]
+    h = _empty((T, N), torch.bfloat16, x)
+    a = _empty((T, N // 2), torch.bfloat16, x)
+    call("cm3p_gemm_bf16", ptr(x), ptr(w_interleaved), ptr(h), None, T, N, Kd, Kd, Kd, N, 1, 1, EPI_BF16_GEGLU_FWD, 1, ptr(a), stream(),
+         tag=_gemm_tag(T, N, Kd, True, True, EPI_BF16_GEGLU_FWD, 1), work=2.0 * T * N * Kd)
+    return h, a
+
+
+def linear_dgrad_geglu_bwd(dy: Tensor, w_t: Tensor, h_interleaved: Tensor) -> Tensor:
+    """dy [T,H] bf16, w_t = Wo2^T [I,H] bf16, h' [T,2I] of linear_geglu_fwd -> dh [T,2I] bf16 in CANONICAL column order =
+    geglu_bwd(linear_dgrad(dy, Wo2, w_t), h), bit for bit, in one kernel: the bf16 dg exists only in the GEMM's store phase."""
+    T, Kd = dy.shape
+    I = w_t.shape[0]
+    dh = torch.empty_like(h_interleaved)
+    call("cm3p_gemm_bf16", ptr(dy), ptr(w_t), ptr(dh), ptr(h_interleaved), T, I, Kd, Kd, Kd, 2 * I, 1, 1, EPI_BF16_GEGLU_BWD, 1, None, stream(),
+         tag=_gemm_tag(T, I, Kd, True, True, EPI_BF16_GEGLU_BWD, 1), work=2.0 * T * I * Kd)
+    return dh
 
 
 def geglu_bwd(dg: Tensor, h: Tensor) -> Tensor:

@@ -117,12 +117,27 @@ int cm3p_audio_slots(const int64_t* ids, int64_t T, int64_t audio_token_id, int3
  *   `hidden_states + Wo(x)` of a bf16 model, TF:...modeling_modernbert.py:331-332 - bit for bit a CM3P_EPI_BF16 GEMM followed by
  *   torch's bf16 add; N and ldc multiples of 8, split_k = 1; R is read through the `const float*` parameter as bf16).
  *   Constraints: contiguous extents and leading dimensions are multiples of 8 elements.
+ *
+ *   The GeGLU of a TRAINING step in the store phases of its two neighbouring GEMMs (ModernBertMLP.forward and its autograd,
+ *   TF:...modeling_modernbert.py:89-91): forward orientation (a_kc = b_kc = 1), split_k = 1, dense rows, and only shapes the routing
+ *   rule sends to the 256 x 256 ring kernel (cm3p_gemm_route says so; every other shape is CM3P_ERR_INVALID and the caller keeps
+ *   cm3p_geglu_fwd / cm3p_geglu_bwd).  Both give, bit for bit, what the two-kernel chains give.
+ *   CM3P_EPI_BF16_GEGLU_FWD: A = x [M, K], B = Wi with its rows interleaved as cm3p_gemm_geglu reads them [N = 2 I, K], I % 32 == 0.
+ *     Two outputs: C = h' [M, N] bf16 (ldc == N), the projection in the column order of those weight rows - h of the plain GEMM
+ *     with column 64 q + r holding h[:, 32 q + r] (r < 32) or h[:, I + 32 q + r - 32] - and a [M, I] bf16 = cm3p_geglu_fwd(h),
+ *     written through the non-const `workspace` parameter (read as a bf16 pointer; no split uses it at split_k = 1).
+ *   CM3P_EPI_BF16_GEGLU_BWD: A = dy [M, K], B = Wo2^T [N = I, K], I % 32 == 0: the input gradient dg = dy Wo2 of the MLP's output
+ *     projection is rounded to bf16 and consumed in place - dg is never written.  R = the h' [M, 2 I] of the epilogue above, read
+ *     as bf16 through the `const float*` parameter as CM3P_EPI_BF16_RESID reads its R; C = dh [M, 2 I] bf16 (ldc == 2 I) =
+ *     cm3p_geglu_bwd(dg, h) in CANONICAL column order (gate half, then up half: what the Wi input and weight gradients contract over).
  */
 #define CM3P_EPI_BF16 0
 #define CM3P_EPI_F32 1
 #define CM3P_EPI_F32_RESID 2
 #define CM3P_EPI_F32_BIAS 5
 #define CM3P_EPI_BF16_RESID 7
+#define CM3P_EPI_BF16_GEGLU_FWD 9 /* (8 stays unassigned: the route refuses it) */
+#define CM3P_EPI_BF16_GEGLU_BWD 10
 /* split_k > 1 (CM3P_EPI_F32 only, ldc == N): the contraction is cut into split_k ranges whose fp32 partial tiles go to
  * `workspace` (split_k * M * N floats) and are then summed in a fixed order - used for dW, whose contraction runs over
  * all tokens while its output is only a few hundred tiles. */
@@ -175,7 +190,8 @@ int cm3p_gemm_wgrad_splits(int64_t M, int64_t N, int64_t K);
  * under the current value of the CM3P_GEMM_IMPL development switch.  Profiler tags and tests are spelled from it.
  *   epilogue: a public CM3P_EPI_* number with the arguments of cm3p_gemm_bf16 (rope_cols = 0, batch = 0); 3 with the M, N, K and
  *   rope_cols of cm3p_qkv_gemm_rope (lda = ldb = K); 6 with M = T, N = 2 I of cm3p_gemm_geglu; 4 with batch > 0 for
- *   cm3p_gemm_bf16_batched.
+ *   cm3p_gemm_bf16_batched.  CM3P_EPI_BF16_GEGLU_FWD / _BWD (N = 2 I / N = I) answer the ring or CM3P_ERR_INVALID, never another
+ *   kernel (also under CM3P_GEMM_IMPL=256 / 128): a caller takes the fused pair only where both answers are the ring.
  * Returns a non-negative code: bits 0-1 the kernel (0 gemm_bf16_kernel, 128 x 128; 1 gemm256_kernel; 2 gemm8p_kernel, the ring),
  * bit 2 set when every work item of a 256 x 256 route has an even number of k-tiles (the ring's REBAL instances), bits 3 and up
  * the split count the library uses.  Negative (CM3P_ERR_INVALID): the rule has no kernel for the call and the entry point refuses
@@ -195,7 +211,10 @@ int cm3p_cast_f32_bf16_t(const float* x, void* y, void* y_t, int64_t rows, int64
 /* The same for n matrices in ONE launch (all the projection weights of a tower at the start of a training forward).  table: n rows of
  * six int64 on the device - source (fp32 [rows, cols]), bf16 copy, transposed bf16 copy [cols, rows] (device addresses, 16-byte
  * aligned), rows, cols (multiples of 8), index of the matrix's first 64 x 64 block - with first-block indices ascending from 0;
- * total_blocks = the sum of ceil(rows / 64) * ceil(cols / 64).  The table is the caller's (it must outlive the launch). */
+ * total_blocks = the sum of ceil(rows / 64) * ceil(cols / 64).  The table is the caller's (it must outlive the launch).
+ * A NEGATIVE rows entry -2 I marks a Wi weight [2 I, cols], I % 32 == 0, whose bf16 copy is wanted in the interleaved row order of
+ * cm3p_gemm_geglu / CM3P_EPI_BF16_GEGLU_FWD (row 64 q + r <- Wi[32 q + r] for r < 32, Wi[I + 32 q + r - 32] otherwise); its
+ * transposed copy [cols, 2 I] and its block count are those of rows = 2 I.  Tables without such an entry run as before. */
 int cm3p_cast_f32_bf16_t_multi(const int64_t* table, int n, int64_t total_blocks, void* stream);
 /* y_f32 (and y_bf16 if not NULL) = a_f32 + b (b fp32 or bf16); n % 4 == 0.  Residual-gradient join for layer 0,
  * whose attn_norm is nn.Identity (TF:...modeling_modernbert.py:309-310).
