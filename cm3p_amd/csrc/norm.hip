@@ -20,6 +20,13 @@ struct RowRegs {
     f32x4 v[NC];
 };
 
+// row `row` of a [*, H] array of fp32 or bf16 values
+template <bool BF16>
+__device__ __forceinline__ const void* row_ptr(const void* base, int64_t row, int H) {
+    if constexpr (BF16) return static_cast<const uint16_t*>(base) + row * H;
+    else return static_cast<const float*>(base) + row * H;
+}
+
 // load a row of H values (fp32 or bf16 source) into registers, lane owns columns c*256 + lane*4 .. +3
 template <bool SRC_BF16, int NC>
 __device__ __forceinline__ void load_row(RowRegs<NC>& r, const void* src, int H, int lane) {
@@ -86,9 +93,7 @@ __global__ __launch_bounds__(256) void layernorm_fwd_kernel(const void* __restri
         // reverse: the last rows first - what the kernel before this one wrote last is what the Infinity Cache still holds
         const int64_t row = reverse ? rows - 1 - it : it;
         RowRegs<NC> r;
-        const void* src = X_BF16 ? (const void*)(static_cast<const uint16_t*>(x) + row * H)
-                                 : (const void*)(static_cast<const float*>(x) + row * H);
-        load_row<X_BF16, NC>(r, src, H, lane);
+        load_row<X_BF16, NC>(r, row_ptr<X_BF16>(x, row, H), H, lane);
         float mean, rstd;
         row_stats(r, H, lane, eps, mean, rstd);
         store_norm(r, w, mean, rstd, y32 ? y32 + row * H : nullptr, y16 ? y16 + row * H : nullptr, H, lane);
@@ -101,62 +106,42 @@ __global__ __launch_bounds__(256) void layernorm_fwd_kernel(const void* __restri
 
 // Backward.  xhat = (x - mean) * rstd, g = dy * w:
 //   dx = rstd * (g - mean_H(g) - xhat * mean_H(g * xhat)) [+ dres]      dw[col] = sum_rows dy * xhat
-// Each wave walks rows grid-stride and keeps its dw partial in registers; one partial row per block.
-template <bool DY_BF16, int NC>
-__global__ __launch_bounds__(256) void layernorm_bwd_kernel(const void* __restrict__ dy, const float* __restrict__ x,
-                                                            const float* __restrict__ w, const float* __restrict__ mean_in,
-                                                            const float* __restrict__ rstd_in, const float* dres,
-                                                            float* dx32, uint16_t* __restrict__ dx16,
-                                                            float* __restrict__ dw_partial, int64_t rows, int H) {
-    extern __shared__ __attribute__((aligned(16))) float dw_lds[];  // [4][H]
-    const int lane = threadIdx.x & 63;
-    const int wid = threadIdx.x >> 6;
-    const int64_t wave = (int64_t)blockIdx.x * 4 + wid;
-    const int64_t nwaves = (int64_t)gridDim.x * 4;
-    RowRegs<NC> dw;
-#pragma unroll
-    for (int c = 0; c < NC; ++c) dw.v[c] = f32x4{0.f, 0.f, 0.f, 0.f};
+// Each wave walks rows grid-stride and keeps its dw partial in registers; one partial row per block.  The row math is written once,
+// in the three functions below, for the LayerNorm backward and both embedding backwards.
+struct RowMeans {
+    float g, gxhat;  // mean_H(g), mean_H(g * xhat)
+};
 
-    for (int64_t row = wave; row < rows; row += nwaves) {
-        RowRegs<NC> xr, gr;
-        load_row<false, NC>(xr, x + row * H, H, lane);
-        const void* dsrc = DY_BF16 ? (const void*)(static_cast<const uint16_t*>(dy) + row * H)
-                                   : (const void*)(static_cast<const float*>(dy) + row * H);
-        load_row<DY_BF16, NC>(gr, dsrc, H, lane);
-        // (requested with the row, not behind the two wave reductions: one exposed round trip per row less, 0.314 -> 0.305 ms at C2)
-        RowRegs<NC> rr;
-        if (dres) load_row<false, NC>(rr, dres + row * H, H, lane);
-        const float mean = mean_in[row], rstd = rstd_in[row];
-        float s1 = 0.f, s2 = 0.f;
+// The row step, on xr = the x row and gr = the dy row as loaded: leaves xhat in xr and g in gr, adds dy * xhat to the wave's dw.
+template <int NC>
+__device__ __forceinline__ RowMeans ln_bwd_row(RowRegs<NC>& xr, RowRegs<NC>& gr, RowRegs<NC>& dw, const float* __restrict__ w,
+                                               float mean, float rstd, int H, int lane) {
+    float s1 = 0.f, s2 = 0.f;
 #pragma unroll
-        for (int c = 0; c < NC; ++c) {
-            const int col = c * 256 + lane * 4;
-            if (col < H) {
-                const f32x4 xhat = (xr.v[c] - mean) * rstd;
-                const f32x4 wv = *reinterpret_cast<const f32x4*>(w + col);
-                dw.v[c] += gr.v[c] * xhat;
-                const f32x4 g = gr.v[c] * wv;
-                xr.v[c] = xhat;
-                gr.v[c] = g;
-                s1 += (g.x + g.y) + (g.z + g.w);
-                const f32x4 gx = g * xhat;
-                s2 += (gx.x + gx.y) + (gx.z + gx.w);
-            }
-        }
-        s1 = wave_sum(s1) / (float)H;
-        s2 = wave_sum(s2) / (float)H;
-#pragma unroll
-        for (int c = 0; c < NC; ++c) {
-            const int col = c * 256 + lane * 4;
-            if (col < H) {
-                f32x4 d = (gr.v[c] - s1 - xr.v[c] * s2) * rstd;
-                if (dres) d += rr.v[c];
-                if (dx32) gstore16f<(CM3P_NT & 16) != 0>(dx32 + row * H + col, d);
-                if (dx16) gstore8<(CM3P_NT & 16) != 0>(dx16 + row * H + col, uint2{pack_bf16x2(d.x, d.y), pack_bf16x2(d.z, d.w)});
-            }
+    for (int c = 0; c < NC; ++c) {
+        const int col = c * 256 + lane * 4;
+        if (col < H) {
+            const f32x4 xhat = (xr.v[c] - mean) * rstd;
+            const f32x4 wv = *reinterpret_cast<const f32x4*>(w + col);
+            dw.v[c] += gr.v[c] * xhat;
+            const f32x4 g = gr.v[c] * wv;
+            xr.v[c] = xhat;
+            gr.v[c] = g;
+            s1 += (g.x + g.y) + (g.z + g.w);
+            const f32x4 gx = g * xhat;
+            s2 += (gx.x + gx.y) + (gx.z + gx.w);
         }
     }
-    // block-level reduction of the four waves' dw partials, fixed order -> deterministic
+    return RowMeans{wave_sum(s1) / (float)H, wave_sum(s2) / (float)H};
+}
+
+__device__ __forceinline__ f32x4 ln_bwd_dx(f32x4 g, f32x4 xhat, RowMeans m, float rstd) { return (g - m.g - xhat * m.gxhat) * rstd; }
+
+// Block-level reduction of the four waves' dw partials through LDS ([4][H] floats of dynamic LDS), in wave order -> deterministic;
+// one partial row per block.
+template <int NC>
+__device__ __forceinline__ void store_dw_partial(const RowRegs<NC>& dw, float* __restrict__ dw_partial, int H, int lane, int wid) {
+    extern __shared__ __attribute__((aligned(16))) float dw_lds[];
 #pragma unroll
     for (int c = 0; c < NC; ++c) {
         const int col = c * 256 + lane * 4;
@@ -168,19 +153,18 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const void* __restri
     }
 }
 
-// The same backward for the bf16 residual stream of a training step: x and / or the incoming residual gradient are bf16 rows, and with
-// dx32 == nullptr the only output is bf16(dres + LN'(dy)) - the sum is formed in fp32 and rounded ONCE (a bf16 torch model rounds LN'(dy)
-// and the sum separately).  8 bytes per element (dy, x, dres in, dx out) where the fp32 stream moves 16 and more.  Statistics, the row
-// reductions and the dw partial sums are fp32 in the order of the kernel above, so dw differs from it only through the rounded inputs.
-// dx16 may alias dres: every lane reads its four columns of a row before it writes them.
-// The body restates layernorm_bwd_kernel (whose instances keep their code, so that no bit of the fp32 stream can move): a fix to one
-// of the two kernels must be made in the other.  The stack launches <true, true, true, NC>; the other dtype forms serve the entry point.
+// x, dy and the incoming residual gradient dres are fp32 or bf16 rows, each by its own flag; statistics, the row reductions and the dw
+// partial sums are fp32 whatever the loads read.  The fp32 residual stream runs <., false, false, NC>.  The bf16 stream of a training
+// step runs <true, true, true, NC> with dx32 == nullptr: its only output is bf16(dres + LN'(dy)) - the sum is formed in fp32 and
+// rounded ONCE (a bf16 torch model rounds LN'(dy) and the sum separately), 8 bytes per element (dy, x, dres in, dx out) where the fp32
+// stream moves 16 and more.  The other dtype forms serve the entry point.
+// dx32 may alias an fp32 dres and dx16 a bf16 dres (hence no __restrict__ on the three): every lane reads its four columns of a row
+// before it writes them.
 template <bool DY_BF16, bool X_BF16, bool RES_BF16, int NC>
-__global__ __launch_bounds__(256) void layernorm_bwd_s16_kernel(const void* __restrict__ dy, const void* __restrict__ x,
-                                                                const float* __restrict__ w, const float* __restrict__ mean_in,
-                                                                const float* __restrict__ rstd_in, const void* dres, float* dx32,
-                                                                uint16_t* dx16, float* __restrict__ dw_partial, int64_t rows, int H) {
-    extern __shared__ __attribute__((aligned(16))) float dw_lds[];  // [4][H]
+__global__ __launch_bounds__(256) void layernorm_bwd_kernel(const void* __restrict__ dy, const void* __restrict__ x,
+                                                            const float* __restrict__ w, const float* __restrict__ mean_in,
+                                                            const float* __restrict__ rstd_in, const void* dres, float* dx32,
+                                                            uint16_t* dx16, float* __restrict__ dw_partial, int64_t rows, int H) {
     const int lane = threadIdx.x & 63;
     const int wid = threadIdx.x >> 6;
     const int64_t wave = (int64_t)blockIdx.x * 4 + wid;
@@ -191,56 +175,24 @@ __global__ __launch_bounds__(256) void layernorm_bwd_s16_kernel(const void* __re
 
     for (int64_t row = wave; row < rows; row += nwaves) {
         RowRegs<NC> xr, gr, rr;
-        const void* xsrc = X_BF16 ? (const void*)(static_cast<const uint16_t*>(x) + row * H)
-                                  : (const void*)(static_cast<const float*>(x) + row * H);
-        load_row<X_BF16, NC>(xr, xsrc, H, lane);
-        const void* dsrc = DY_BF16 ? (const void*)(static_cast<const uint16_t*>(dy) + row * H)
-                                   : (const void*)(static_cast<const float*>(dy) + row * H);
-        load_row<DY_BF16, NC>(gr, dsrc, H, lane);
-        if (dres) {  // (requested with the row, as above)
-            const void* rsrc = RES_BF16 ? (const void*)(static_cast<const uint16_t*>(dres) + row * H)
-                                        : (const void*)(static_cast<const float*>(dres) + row * H);
-            load_row<RES_BF16, NC>(rr, rsrc, H, lane);
-        }
-        const float mean = mean_in[row], rstd = rstd_in[row];
-        float s1 = 0.f, s2 = 0.f;
+        load_row<X_BF16, NC>(xr, row_ptr<X_BF16>(x, row, H), H, lane);
+        load_row<DY_BF16, NC>(gr, row_ptr<DY_BF16>(dy, row, H), H, lane);
+        // (requested with the row, not behind the two wave reductions: one exposed round trip per row less, 0.314 -> 0.305 ms at C2)
+        if (dres) load_row<RES_BF16, NC>(rr, row_ptr<RES_BF16>(dres, row, H), H, lane);
+        const float rstd = rstd_in[row];
+        const RowMeans m = ln_bwd_row(xr, gr, dw, w, mean_in[row], rstd, H, lane);
 #pragma unroll
         for (int c = 0; c < NC; ++c) {
             const int col = c * 256 + lane * 4;
             if (col < H) {
-                const f32x4 xhat = (xr.v[c] - mean) * rstd;
-                const f32x4 wv = *reinterpret_cast<const f32x4*>(w + col);
-                dw.v[c] += gr.v[c] * xhat;
-                const f32x4 g = gr.v[c] * wv;
-                xr.v[c] = xhat;
-                gr.v[c] = g;
-                s1 += (g.x + g.y) + (g.z + g.w);
-                const f32x4 gx = g * xhat;
-                s2 += (gx.x + gx.y) + (gx.z + gx.w);
-            }
-        }
-        s1 = wave_sum(s1) / (float)H;
-        s2 = wave_sum(s2) / (float)H;
-#pragma unroll
-        for (int c = 0; c < NC; ++c) {
-            const int col = c * 256 + lane * 4;
-            if (col < H) {
-                f32x4 d = (gr.v[c] - s1 - xr.v[c] * s2) * rstd;
+                f32x4 d = ln_bwd_dx(gr.v[c], xr.v[c], m, rstd);
                 if (dres) d += rr.v[c];
                 if (dx32) gstore16f<(CM3P_NT & 16) != 0>(dx32 + row * H + col, d);
                 if (dx16) gstore8<(CM3P_NT & 16) != 0>(dx16 + row * H + col, uint2{pack_bf16x2(d.x, d.y), pack_bf16x2(d.z, d.w)});
             }
         }
     }
-#pragma unroll
-    for (int c = 0; c < NC; ++c) {
-        const int col = c * 256 + lane * 4;
-        if (col < H) *reinterpret_cast<f32x4*>(dw_lds + wid * H + col) = dw.v[c];
-    }
-    __syncthreads();
-    for (int col = threadIdx.x; col < H; col += 256) {
-        dw_partial[(int64_t)blockIdx.x * H + col] = (dw_lds[col] + dw_lds[H + col]) + (dw_lds[2 * H + col] + dw_lds[3 * H + col]);
-    }
+    store_dw_partial(dw, dw_partial, H, lane, wid);
 }
 
 // out[col] = sum_b partial[b][col], fixed summation order.  Block = 32 columns x 32 row slices (1024 threads: the 24 workgroups
@@ -284,9 +236,7 @@ __device__ __forceinline__ void load_embed_row(RowRegs<NC>& r, const int64_t* id
                                                const void* ovr, int64_t t, int H, int lane, int64_t vocab) {
     const int s = slot ? slot[t] : -1;
     if (s >= 0) {
-        const void* src = OVR_BF16 ? (const void*)(static_cast<const uint16_t*>(ovr) + (int64_t)s * H)
-                                   : (const void*)(static_cast<const float*>(ovr) + (int64_t)s * H);
-        load_row<OVR_BF16, NC>(r, src, H, lane);
+        load_row<OVR_BF16, NC>(r, row_ptr<OVR_BF16>(ovr, s, H), H, lane);
     } else {
         const int64_t id = ids[t];
         if ((uint64_t)id >= (uint64_t)vocab) {  // nn.Embedding raises a device-side assert here; a kernel must not fault: zero row
@@ -294,9 +244,7 @@ __device__ __forceinline__ void load_embed_row(RowRegs<NC>& r, const int64_t* id
             for (int c = 0; c < NC; ++c) r.v[c] = f32x4{0.f, 0.f, 0.f, 0.f};
             return;
         }
-        const void* src = TAB_BF16 ? (const void*)(static_cast<const uint16_t*>(table) + id * H)
-                                   : (const void*)(static_cast<const float*>(table) + id * H);
-        load_row<TAB_BF16, NC>(r, src, H, lane);
+        load_row<TAB_BF16, NC>(r, row_ptr<TAB_BF16>(table, id, H), H, lane);
     }
 }
 
@@ -333,7 +281,6 @@ __global__ __launch_bounds__(256) void embed_ln_bwd_kernel(const void* __restric
                                                            float* __restrict__ d_table, float* __restrict__ d_ovr,
                                                            float* __restrict__ dw_partial, int64_t T, int H,
                                                            int64_t padding_idx, int64_t vocab) {
-    extern __shared__ __attribute__((aligned(16))) float dw_lds[];
     const int lane = threadIdx.x & 63;
     const int wid = threadIdx.x >> 6;
     const int64_t wave = (int64_t)blockIdx.x * 4 + wid;
@@ -344,27 +291,9 @@ __global__ __launch_bounds__(256) void embed_ln_bwd_kernel(const void* __restric
     for (int64_t t = wave; t < T; t += nwaves) {
         RowRegs<NC> xr, gr;
         load_embed_row<TAB_BF16, OVR_BF16, NC>(xr, ids, table, slot, ovr, t, H, lane, vocab);
-        if constexpr (DY_BF16) load_row<true, NC>(gr, static_cast<const uint16_t*>(dy) + t * H, H, lane);  // (bf16 residual stream)
-        else load_row<false, NC>(gr, static_cast<const float*>(dy) + t * H, H, lane);
-        const float mean = mean_in[t], rstd = rstd_in[t];
-        float s1 = 0.f, s2 = 0.f;
-#pragma unroll
-        for (int c = 0; c < NC; ++c) {
-            const int col = c * 256 + lane * 4;
-            if (col < H) {
-                const f32x4 xhat = (xr.v[c] - mean) * rstd;
-                const f32x4 wv = *reinterpret_cast<const f32x4*>(w + col);
-                dw.v[c] += gr.v[c] * xhat;
-                const f32x4 g = gr.v[c] * wv;
-                xr.v[c] = xhat;
-                gr.v[c] = g;
-                s1 += (g.x + g.y) + (g.z + g.w);
-                const f32x4 gx = g * xhat;
-                s2 += (gx.x + gx.y) + (gx.z + gx.w);
-            }
-        }
-        s1 = wave_sum(s1) / (float)H;
-        s2 = wave_sum(s2) / (float)H;
+        load_row<DY_BF16, NC>(gr, row_ptr<DY_BF16>(dy, t, H), H, lane);  // (bf16: the gradient that leaves a bf16 residual stream)
+        const float rstd = rstd_in[t];
+        const RowMeans m = ln_bwd_row(xr, gr, dw, w, mean_in[t], rstd, H, lane);
         const int s = slot ? slot[t] : -1;
         // nn.Embedding(padding_idx=pad_token_id) gives the padding row no gradient (TF:...modeling_modernbert.py:60)
         const int64_t id = ids[t];
@@ -374,7 +303,7 @@ __global__ __launch_bounds__(256) void embed_ln_bwd_kernel(const void* __restric
         for (int c = 0; c < NC; ++c) {
             const int col = c * 256 + lane * 4;
             if (col < H && dst) {
-                const f32x4 d = (gr.v[c] - s1 - xr.v[c] * s2) * rstd;
+                const f32x4 d = ln_bwd_dx(gr.v[c], xr.v[c], m, rstd);
                 if (s >= 0) {
                     *reinterpret_cast<f32x4*>(dst + col) = d;
                 } else {
@@ -386,15 +315,7 @@ __global__ __launch_bounds__(256) void embed_ln_bwd_kernel(const void* __restric
             }
         }
     }
-#pragma unroll
-    for (int c = 0; c < NC; ++c) {
-        const int col = c * 256 + lane * 4;
-        if (col < H) *reinterpret_cast<f32x4*>(dw_lds + wid * H + col) = dw.v[c];
-    }
-    __syncthreads();
-    for (int col = threadIdx.x; col < H; col += 256) {
-        dw_partial[(int64_t)blockIdx.x * H + col] = (dw_lds[col] + dw_lds[H + col]) + (dw_lds[2 * H + col] + dw_lds[3 * H + col]);
-    }
+    store_dw_partial(dw, dw_partial, H, lane, wid);
 }
 
 // ---- the same backward without atomics: tokens visited in id order ------------------------------------------------------------------
@@ -415,7 +336,6 @@ __global__ __launch_bounds__(256) void embed_ln_bwd_sorted_kernel(const void* __
                                                                   float* __restrict__ d_ovr, float* __restrict__ run_rows,
                                                                   int64_t* __restrict__ run_ids, float* __restrict__ dw_partial,
                                                                   int64_t T, int H, int64_t padding_idx, int64_t vocab) {
-    extern __shared__ __attribute__((aligned(16))) float dw_lds[];
     const int lane = threadIdx.x & 63;
     const int wid = threadIdx.x >> 6;
     const int64_t chunk = (int64_t)blockIdx.x * 4 + wid;
@@ -445,27 +365,9 @@ __global__ __launch_bounds__(256) void embed_ln_bwd_sorted_kernel(const void* __
         }
         RowRegs<NC> xr, gr;
         load_embed_row<TAB_BF16, OVR_BF16, NC>(xr, ids, table, slot, ovr, t, H, lane, vocab);
-        if constexpr (DY_BF16) load_row<true, NC>(gr, static_cast<const uint16_t*>(dy) + t * H, H, lane);  // (bf16 residual stream)
-        else load_row<false, NC>(gr, static_cast<const float*>(dy) + t * H, H, lane);
-        const float mean = mean_in[t], rstd = rstd_in[t];
-        float s1 = 0.f, s2 = 0.f;
-#pragma unroll
-        for (int c = 0; c < NC; ++c) {
-            const int col = c * 256 + lane * 4;
-            if (col < H) {
-                const f32x4 xhat = (xr.v[c] - mean) * rstd;
-                const f32x4 wv = *reinterpret_cast<const f32x4*>(w + col);
-                dw.v[c] += gr.v[c] * xhat;
-                const f32x4 g = gr.v[c] * wv;
-                xr.v[c] = xhat;
-                gr.v[c] = g;
-                s1 += (g.x + g.y) + (g.z + g.w);
-                const f32x4 gx = g * xhat;
-                s2 += (gx.x + gx.y) + (gx.z + gx.w);
-            }
-        }
-        s1 = wave_sum(s1) / (float)H;
-        s2 = wave_sum(s2) / (float)H;
+        load_row<DY_BF16, NC>(gr, row_ptr<DY_BF16>(dy, t, H), H, lane);  // (bf16: the gradient that leaves a bf16 residual stream)
+        const float rstd = rstd_in[t];
+        const RowMeans m = ln_bwd_row(xr, gr, dw, w, mean_in[t], rstd, H, lane);
         const int sl = slot ? slot[t] : -1;
         const int64_t id = ids[t];
         // audio placeholders: the row gradient belongs to the audio embedding, not to the table; padding row / ids outside the table: none
@@ -474,7 +376,7 @@ __global__ __launch_bounds__(256) void embed_ln_bwd_sorted_kernel(const void* __
         for (int c = 0; c < NC; ++c) {
             const int col = c * 256 + lane * 4;
             if (col < H) {
-                const f32x4 d = (gr.v[c] - s1 - xr.v[c] * s2) * rstd;
+                const f32x4 d = ln_bwd_dx(gr.v[c], xr.v[c], m, rstd);
                 if (sl >= 0) {
                     if (d_ovr) *reinterpret_cast<f32x4*>(d_ovr + (int64_t)sl * H + col) = d;
                 } else if (to_table) {
@@ -484,15 +386,7 @@ __global__ __launch_bounds__(256) void embed_ln_bwd_sorted_kernel(const void* __
         }
     }
     flush();
-#pragma unroll
-    for (int c = 0; c < NC; ++c) {
-        const int col = c * 256 + lane * 4;
-        if (col < H) *reinterpret_cast<f32x4*>(dw_lds + wid * H + col) = dw.v[c];
-    }
-    __syncthreads();
-    for (int col = threadIdx.x; col < H; col += 256) {
-        dw_partial[(int64_t)blockIdx.x * H + col] = (dw_lds[col] + dw_lds[H + col]) + (dw_lds[2 * H + col] + dw_lds[3 * H + col]);
-    }
+    store_dw_partial(dw, dw_partial, H, lane, wid);
 }
 
 // d_table[v] = sum of the runs whose id is v, in run order (zero when there is none): one wave per vocabulary row.  The run ids
@@ -717,16 +611,16 @@ __global__ __launch_bounds__(1024) void token_run_number_kernel(const int32_t* _
     if (p < T) run_of[p] = run;
 }
 
-// run MACRO(NC) with NC = the smallest supported chunk count covering H
-#define CM3P_NC_SWITCH(H, MACRO)      \
-    {                                 \
-        const int nc__ = ((H) + 255) / 256; \
-        if (nc__ <= 1) { MACRO(1) }   \
-        else if (nc__ == 2) { MACRO(2) } \
-        else if (nc__ == 3) { MACRO(3) } \
-        else if (nc__ == 4) { MACRO(4) } \
-        else { MACRO(8) }             \
-    }
+// f(NC as a compile-time constant), NC = the smallest supported chunk count covering H; dtype flags come through cm3p_with_flag
+template <class F>
+int with_nc(int H, F&& f) {
+    const int nc = (H + 255) / 256;
+    if (nc <= 1) return f(std::integral_constant<int, 1>{});
+    if (nc == 2) return f(std::integral_constant<int, 2>{});
+    if (nc == 3) return f(std::integral_constant<int, 3>{});
+    if (nc == 4) return f(std::integral_constant<int, 4>{});
+    return f(std::integral_constant<int, kMaxChunks>{});
+}
 
 inline int ln_grid(int64_t rows, int cap = 2048) {
     int64_t blocks = (rows + 3) / 4;
@@ -755,13 +649,13 @@ int cm3p_layernorm_fwd(const void* x, int x_dtype, const float* weight, float* y
     hipStream_t s = static_cast<hipStream_t>(stream);
     const char* env_r = getenv("CM3P_LN_REVERSE");  // development probe (tools/mall_order_probe.py): row order of the sweep
     const int reverse = env_r && env_r[0] == '1';
-#define CM3P_LN_FWD(NC)                                                                                                      \
-    if (x_dtype == CM3P_BF16)                                                                                                \
-        layernorm_fwd_kernel<true, NC><<<ln_grid(rows), 256, 0, s>>>(x, weight, y_f32, (uint16_t*)y_bf16, mean, rstd, rows, H, eps, reverse); \
-    else                                                                                                                     \
-        layernorm_fwd_kernel<false, NC><<<ln_grid(rows), 256, 0, s>>>(x, weight, y_f32, (uint16_t*)y_bf16, mean, rstd, rows, H, eps, reverse);
-    CM3P_NC_SWITCH(H, CM3P_LN_FWD)
-#undef CM3P_LN_FWD
+    with_nc(H, [&](auto nc) {
+        return cm3p_with_flag(x_dtype == CM3P_BF16, [&](auto xb) {
+            layernorm_fwd_kernel<decltype(xb)::value, decltype(nc)::value>
+                <<<ln_grid(rows), 256, 0, s>>>(x, weight, y_f32, (uint16_t*)y_bf16, mean, rstd, rows, H, eps, reverse);
+            return CM3P_OK;
+        });
+    });
     CM3P_LAUNCH_CHECK();
     return CM3P_OK;
 }
@@ -779,32 +673,17 @@ int cm3p_layernorm_bwd(const void* dy, int dy_dtype, const void* x, int x_dtype,
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int grid = ln_bwd_grid(rows);
     const size_t lds = (size_t)4 * H * sizeof(float);
-    const bool xb = x_dtype == CM3P_BF16, rb = dres && dres_dtype == CM3P_BF16;
-    if (!xb && !rb) {  // the fp32 residual stream: the instances it has always run
-        const float* x32 = static_cast<const float*>(x);
-        const float* r32 = static_cast<const float*>(dres);
-#define CM3P_LN_BWD(NC)                                                                                                      \
-    if (dy_dtype == CM3P_BF16)                                                                                               \
-        layernorm_bwd_kernel<true, NC><<<grid, 256, lds, s>>>(dy, x32, weight, mean, rstd, r32, dx_f32, (uint16_t*)dx_bf16, dw_partial, rows, H); \
-    else                                                                                                                     \
-        layernorm_bwd_kernel<false, NC><<<grid, 256, lds, s>>>(dy, x32, weight, mean, rstd, r32, dx_f32, (uint16_t*)dx_bf16, dw_partial, rows, H);
-        CM3P_NC_SWITCH(H, CM3P_LN_BWD)
-#undef CM3P_LN_BWD
-    } else {  // bf16 rows on the stream (x, the residual gradient, or both)
-        const bool db = dy_dtype == CM3P_BF16;
-#define CM3P_LN_BWD_NC(NC) \
-    layernorm_bwd_s16_kernel<DB_, XB_, RB_, NC><<<grid, 256, lds, s>>>(dy, x, weight, mean, rstd, dres, dx_f32, (uint16_t*)dx_bf16, dw_partial, rows, H);
-#define CM3P_LN_BWD_S16(DB, XB, RB)                   \
-    do {                                              \
-        constexpr bool DB_ = DB, XB_ = XB, RB_ = RB;  \
-        CM3P_NC_SWITCH(H, CM3P_LN_BWD_NC)             \
-    } while (0)
-        if (xb && rb) { if (db) CM3P_LN_BWD_S16(true, true, true); else CM3P_LN_BWD_S16(false, true, true); }
-        else if (xb) { if (db) CM3P_LN_BWD_S16(true, true, false); else CM3P_LN_BWD_S16(false, true, false); }
-        else { if (db) CM3P_LN_BWD_S16(true, false, true); else CM3P_LN_BWD_S16(false, false, true); }
-#undef CM3P_LN_BWD_S16
-#undef CM3P_LN_BWD_NC
-    }
+    with_nc(H, [&](auto nc) {
+        return cm3p_with_flag(dy_dtype == CM3P_BF16, [&](auto db) {
+            return cm3p_with_flag(x_dtype == CM3P_BF16, [&](auto xb) {
+                return cm3p_with_flag(dres && dres_dtype == CM3P_BF16, [&](auto rb) {
+                    layernorm_bwd_kernel<decltype(db)::value, decltype(xb)::value, decltype(rb)::value, decltype(nc)::value>
+                        <<<grid, 256, lds, s>>>(dy, x, weight, mean, rstd, dres, dx_f32, (uint16_t*)dx_bf16, dw_partial, rows, H);
+                    return CM3P_OK;
+                });
+            });
+        });
+    });
     CM3P_LAUNCH_CHECK();
     colsum_kernel<<<(H + 31) / 32, 1024, 0, s>>>(dw_partial, dw, grid, H);
     CM3P_LAUNCH_CHECK();
@@ -819,20 +698,15 @@ int cm3p_embed_ln_fwd(const int64_t* ids, const void* table, int table_dtype, co
     if (T == 0) return CM3P_OK;
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int grid = ln_grid(T);
-    const bool tb = table_dtype == CM3P_BF16, ob = override_dtype == CM3P_BF16;
-#define CM3P_EMB_FWD_NC(NC) \
-    embed_ln_fwd_kernel<TB_, OB_, NC><<<grid, 256, 0, s>>>(ids, table, slot, override_rows, weight, y_f32, (uint16_t*)y_bf16, mean, rstd, T, H, eps, vocab);
-#define CM3P_EMB_FWD(TB, OB)               \
-    do {                                   \
-        constexpr bool TB_ = TB, OB_ = OB; \
-        CM3P_NC_SWITCH(H, CM3P_EMB_FWD_NC) \
-    } while (0)
-    if (tb && ob) CM3P_EMB_FWD(true, true);
-    else if (tb) CM3P_EMB_FWD(true, false);
-    else if (ob) CM3P_EMB_FWD(false, true);
-    else CM3P_EMB_FWD(false, false);
-#undef CM3P_EMB_FWD
-#undef CM3P_EMB_FWD_NC
+    with_nc(H, [&](auto nc) {
+        return cm3p_with_flag(table_dtype == CM3P_BF16, [&](auto tb) {
+            return cm3p_with_flag(override_dtype == CM3P_BF16, [&](auto ob) {
+                embed_ln_fwd_kernel<decltype(tb)::value, decltype(ob)::value, decltype(nc)::value><<<grid, 256, 0, s>>>(
+                    ids, table, slot, override_rows, weight, y_f32, (uint16_t*)y_bf16, mean, rstd, T, H, eps, vocab);
+                return CM3P_OK;
+            });
+        });
+    });
     CM3P_LAUNCH_CHECK();
     return CM3P_OK;
 }
@@ -847,25 +721,18 @@ int cm3p_embed_ln_bwd(const void* dy, int dy_dtype, const int64_t* ids, const vo
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int grid = ln_bwd_grid(T);
     const size_t lds = (size_t)4 * H * sizeof(float);
-    const bool tb = table_dtype == CM3P_BF16, ob = override_dtype == CM3P_BF16;
-#define CM3P_EMB_BWD_NC(NC)                                                                                                         \
-    if (dy_dtype == CM3P_BF16)                                                                                                      \
-        embed_ln_bwd_kernel<TB_, OB_, NC, true><<<grid, 256, lds, s>>>(dy, ids, table, slot, override_rows, weight, mean, rstd, d_table, \
-                                                                       d_override, dw_partial, T, H, padding_idx, vocab);          \
-    else                                                                                                                            \
-        embed_ln_bwd_kernel<TB_, OB_, NC><<<grid, 256, lds, s>>>(dy, ids, table, slot, override_rows, weight, mean, rstd, d_table,  \
-                                                                 d_override, dw_partial, T, H, padding_idx, vocab);
-#define CM3P_EMB_BWD(TB, OB)               \
-    do {                                   \
-        constexpr bool TB_ = TB, OB_ = OB; \
-        CM3P_NC_SWITCH(H, CM3P_EMB_BWD_NC) \
-    } while (0)
-    if (tb && ob) CM3P_EMB_BWD(true, true);
-    else if (tb) CM3P_EMB_BWD(true, false);
-    else if (ob) CM3P_EMB_BWD(false, true);
-    else CM3P_EMB_BWD(false, false);
-#undef CM3P_EMB_BWD
-#undef CM3P_EMB_BWD_NC
+    with_nc(H, [&](auto nc) {
+        return cm3p_with_flag(table_dtype == CM3P_BF16, [&](auto tb) {
+            return cm3p_with_flag(override_dtype == CM3P_BF16, [&](auto ob) {
+                return cm3p_with_flag(dy_dtype == CM3P_BF16, [&](auto db) {
+                    embed_ln_bwd_kernel<decltype(tb)::value, decltype(ob)::value, decltype(nc)::value, decltype(db)::value>
+                        <<<grid, 256, lds, s>>>(dy, ids, table, slot, override_rows, weight, mean, rstd, d_table, d_override, dw_partial,
+                                                T, H, padding_idx, vocab);
+                    return CM3P_OK;
+                });
+            });
+        });
+    });
     CM3P_LAUNCH_CHECK();
     colsum_kernel<<<(H + 31) / 32, 1024, 0, s>>>(dw_partial, dw, grid, H);
     CM3P_LAUNCH_CHECK();
@@ -886,29 +753,23 @@ int cm3p_embed_ln_bwd_sorted(const void* dy, int dy_dtype, const int64_t* ids, c
     const int64_t chunks = (T + kEmbChunk - 1) / kEmbChunk;
     const int grid = (int)((chunks + 3) / 4);
     const size_t lds = (size_t)4 * H * sizeof(float);
-    const bool tb = table_dtype == CM3P_BF16, ob = override_dtype == CM3P_BF16;
-#define CM3P_EMB_SORT_NC(NC)                                                                                                              \
-    if (dy_dtype == CM3P_BF16)                                                                                                            \
-        embed_ln_bwd_sorted_kernel<TB_, OB_, NC, true><<<grid, 256, lds, s>>>(dy, ids, order, run_of, table, slot, override_rows, weight, mean, \
-                                                                              rstd, d_override, run_rows, run_ids, dw_partial, T, H, padding_idx, vocab); \
-    else                                                                                                                                  \
-        embed_ln_bwd_sorted_kernel<TB_, OB_, NC><<<grid, 256, lds, s>>>(dy, ids, order, run_of, table, slot, override_rows, weight, mean,  \
-                                                                        rstd, d_override, run_rows, run_ids, dw_partial, T, H, padding_idx, vocab);
-#define CM3P_EMB_SORT(TB, OB)               \
-    do {                                    \
-        constexpr bool TB_ = TB, OB_ = OB;  \
-        CM3P_NC_SWITCH(H, CM3P_EMB_SORT_NC) \
-    } while (0)
-    if (tb && ob) CM3P_EMB_SORT(true, true);
-    else if (tb) CM3P_EMB_SORT(true, false);
-    else if (ob) CM3P_EMB_SORT(false, true);
-    else CM3P_EMB_SORT(false, false);
-#undef CM3P_EMB_SORT
-#undef CM3P_EMB_SORT_NC
+    with_nc(H, [&](auto nc) {
+        return cm3p_with_flag(table_dtype == CM3P_BF16, [&](auto tb) {
+            return cm3p_with_flag(override_dtype == CM3P_BF16, [&](auto ob) {
+                return cm3p_with_flag(dy_dtype == CM3P_BF16, [&](auto db) {
+                    embed_ln_bwd_sorted_kernel<decltype(tb)::value, decltype(ob)::value, decltype(nc)::value, decltype(db)::value>
+                        <<<grid, 256, lds, s>>>(dy, ids, order, run_of, table, slot, override_rows, weight, mean, rstd, d_override, run_rows,
+                                                run_ids, dw_partial, T, H, padding_idx, vocab);
+                    return CM3P_OK;
+                });
+            });
+        });
+    });
     CM3P_LAUNCH_CHECK();
-#define CM3P_EMB_SUM_NC(NC) embed_run_sum_kernel<NC><<<(int)((vocab + 3) / 4), 256, 0, s>>>(run_rows, run_ids, run_of, d_table, T, H, vocab);
-    CM3P_NC_SWITCH(H, CM3P_EMB_SUM_NC)
-#undef CM3P_EMB_SUM_NC
+    with_nc(H, [&](auto nc) {
+        embed_run_sum_kernel<decltype(nc)::value><<<(int)((vocab + 3) / 4), 256, 0, s>>>(run_rows, run_ids, run_of, d_table, T, H, vocab);
+        return CM3P_OK;
+    });
     CM3P_LAUNCH_CHECK();
     colsum_kernel<<<(H + 31) / 32, 1024, 0, s>>>(dw_partial, dw, grid, H);
     CM3P_LAUNCH_CHECK();

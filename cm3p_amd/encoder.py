@@ -32,8 +32,8 @@ last_hidden_state and hidden_states are bf16.  Every other call runs the fp32 st
 bf16 residual stream of a training step (opt-in, its own switch: `CM3PEncoder.train_residual_dtype = torch.bfloat16`, or
 `model.set_residual_dtype(torch.bfloat16, training=True)`): a call that records a backward and has no dropout plan runs the forward
 above (the same kernels; LayerNorm also writes its fp32 mean / rstd, and a layer keeps x and x_mid as bf16) and a backward whose
-residual-stream gradient is ONE bf16 tensor: LayerNorm backward reads dy, x and the incoming gradient g in bf16 and writes
-bf16(g + LN'(dy)), the sum formed in fp32 and rounded once (8 bytes per element where the fp32 stream moves 16 and more).
+residual-stream gradient is ONE bf16 tensor: LayerNorm backward (both streams' one kernel, in its all-bf16 form) reads dy, x and the
+incoming gradient g in bf16 and writes bf16(g + LN'(dy)), the sum formed in fp32 and rounded once (8 B per element, not 16 and more).
 Statistics, dw partial sums, softmax and GEMM accumulation stay fp32; weight gradients come out of the wgrad GEMMs in fp32 and are cast to
 the parameter's dtype as on the fp32 stream.  With a dropout plan (train mode, any p > 0) the fp32 stream runs: the dropout sites have
 no bf16 form.

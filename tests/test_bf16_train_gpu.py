@@ -11,6 +11,7 @@
   5. the switch changes nothing where it must not: forward-only calls, train-mode dropout calls.
 """
 import copy
+import itertools
 import json
 import os
 
@@ -134,6 +135,44 @@ def test_layernorm_backward_bf16_stream_forms(K, H, rows):
             r3 = R.ln_bwd_ref(dy32.double(), x32.double(), w.double(), xs_mean.cpu().double(), xs_rstd.cpu().double(), dres.double())
             check(f16.cpu(), r3["dx"], R.bf16_bound(r3["dx"], r3["dx_b"]), f"{what} fp32 x, bf16 dres: dx_bf16")
             check(fw.cpu(), r3["p"].sum(0), c_dw * U * r3["p"].abs().sum(0) * R.SECOND + FTZ, f"{what} fp32 x, bf16 dres: dw")
+
+
+@pytest.mark.parametrize("H", [260, 1792])  # NC = 2 partly filled, and the NC = 8 instance
+@pytest.mark.parametrize("rows", [5, 4097])  # 4097: one more than the grid's 1024 blocks x 4 waves
+def test_layernorm_backward_dtype_forms_give_the_same_bits_on_the_same_values(K, H, rows):
+    """The dtype forms of cm3p_layernorm_bwd are one body behind different loads: bf16 values handed over as bf16 or widened to
+    fp32, in every position the entry point takes either (dy, x, dres: eight forms), give the same dx_f32, dx_bf16 and dw."""
+    g = gen("lnforms", H, rows)
+    x, dy, dres = ((torch.randn(rows, H, generator=g) * s + m).to(BF).to(DEV) for s, m in ((2, 0.5), (1, 0), (1, 0)))
+    w = (1 + 0.2 * torch.randn(H, generator=g)).to(DEV)
+    _, _, mean, rstd = K.layernorm_fwd(x, w, LN_EPS, False, True, True)
+    want = K.layernorm_bwd(dy, x, w, mean, rstd, dres, True, inplace=False)
+    assert want[0].dtype == torch.float32 and want[1].dtype == BF
+    for f32_dy, f32_x, f32_dres in itertools.product((False, True), repeat=3):
+        got = K.layernorm_bwd(dy.float() if f32_dy else dy, x.float() if f32_x else x, w, mean, rstd,
+                              dres.float() if f32_dres else dres, True, inplace=False)
+        for name, a, b in zip(("dx_f32", "dx_bf16", "dw"), got, want):
+            assert torch.equal(a, b), f"H {H} rows {rows}: {name} with fp32 dy {f32_dy} x {f32_x} dres {f32_dres} != the all-bf16 form's"
+
+
+def test_sorted_embedding_backward_gives_the_same_bits_for_a_bf16_and_a_widened_gradient(K):
+    """cm3p_embed_ln_bwd_sorted with dy in bf16 and the same values as fp32: 130 tokens (two chunk seams of 64), 3 audio override
+    rows, one id outside the table."""
+    T, V, H, audio_id = 130, 16, 260, 15
+    g = gen("embforms")
+    ids = torch.randint(0, audio_id, (T,), generator=g)
+    ids[3], ids[64], ids[129] = audio_id, audio_id, audio_id  # (one on a chunk seam of the token order's input, one last)
+    ids[70] = V + 5
+    table, audio = torch.randn(V, H, generator=g).to(DEV), torch.randn(3, H, generator=g).to(DEV)
+    w = (1 + 0.1 * torch.randn(H, generator=g)).to(DEV)
+    dy = torch.randn(T, H, generator=g).to(BF).to(DEV)
+    idd = ids.to(DEV)
+    slot, _ = K.audio_slots(idd, audio_id)
+    _, _, mean, rstd = K.embed_ln_fwd(idd, table, w, LN_EPS, slot, audio)
+    want = K._embed_ln_bwd_sorted(dy, idd, table, w, mean, rstd, 0, slot, audio)
+    got = K._embed_ln_bwd_sorted(dy.float(), idd, table, w, mean, rstd, 0, slot, audio)
+    for name, a, b in zip(("d_table", "d_override", "dw"), got, want):
+        assert a.dtype == torch.float32 and torch.equal(a, b), f"{name}: fp32 dy != bf16 dy"
 
 
 @pytest.mark.parametrize("shape", [(131072, 768), (3, 4), (1, 1028)])

@@ -129,7 +129,7 @@ def test_new_entry_forms_refuse_bad_dtype_codes_without_a_gpu():
 
 # ------------------------------------------------------------------------------------------------ the bounds, without a GPU
 def _ln_bwd_bf16_path(dy, x, w, mean, rstd, dres, two_roundings=False, bf16_dw=False):
-    """layernorm_bwd_s16_kernel in torch fp32 on bf16 inputs (R.ln_bwd_f32_path is the fp32 walk: fp32 sum, then ONE rounding to bf16).
+    """layernorm_bwd_kernel's all-bf16 dtype form in torch fp32 on bf16 inputs (R.ln_bwd_f32_path is the fp32 walk: fp32 sum, then ONE rounding to bf16).
     two_roundings: bf16(bf16(LN'(dy)) + dres), what a bf16 torch model computes.  bf16_dw: the dw sum kept in bf16."""
     if two_roundings:
         dx_ln, dw = R.ln_bwd_f32_path(dy, x, w, mean, rstd, None)
