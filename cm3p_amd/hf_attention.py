@@ -2,13 +2,14 @@
 
 `transformers` looks attention up by name (TF:models/modernbert/modeling_modernbert.py:282-297: `ALL_ATTENTION_FUNCTIONS.get_interface(
 config._attn_implementation, ...)`) and builds the mask through a second registry indexed by the SAME name (TF:masking_utils.py:711-725,
-1059, 1306).  Importing this module registers `"cm3p_hip"` in both, after which any model of the installed `transformers` whose
-attention goes through the registry - the reference's `ModernBertModel` towers included - runs its attention on libcm3p_hip.so with
+1059, 1306).  Importing this module registers `"cm3p_hip"` in both, after which models of the installed `transformers` that dispatch
+through `AttentionInterface` (encoder self-attention with a key-padding mask and an optional sliding window; tested with the installed
+`ModernBertModel`, which the reference's towers are) run their attention on libcm3p_hip.so with
 
     config._attn_implementation = "cm3p_hip"          # ref:configs/train/default.yaml:8 -> ref:train.py:275
 
 This is the NARROW seam: it cannot fuse LayerNorm / RoPE / GeGLU / the residual adds (the product replaces the modeling module for that,
-cm3p_amd/modeling_cm3p.py); q, k, v arrive rotated and head-major and are re-packed into the [B, S, 3, nh, hd] layout the kernels read.
+cm3p_amd/modeling_cm3p.py, and cm3p_amd/hf_modernbert.py puts a whole Hugging Face ModernBERT on the fused stack); q, k, v arrive rotated and head-major and are re-packed into the [B, S, 3, nh, hd] layout the kernels read.
 What it does carry over unchanged is the mask RULE, which is the reason for having it tested:
 
     key kv is visible to query q of batch b  iff  padding[b, kv]  and  (global layer  or  |q - kv| <= sliding_window - 1)
