@@ -16,6 +16,7 @@ MU = "tests/test_muon_gpu.py::"
 MG = "tests/test_model_gpu.py::"
 RK = "tests/test_row_kernels_gpu.py::"
 GK = "tests/test_gemm_kernels_gpu.py::"
+AD = "tests/test_attention_d64_gpu.py::"
 
 LEDGER = {
     "cm3p_layernorm_fwd": [KG + "test_layernorm_fwd_bwd", CH + "test_layernorm_with_many_rows_per_wave",
@@ -51,18 +52,24 @@ LEDGER = {
                         RK + "test_rope_table_is_cos_sin_of_the_fp32_product"],
     "cm3p_rope_apply": [KG + "test_rope_matches_reference_formula",
                         RK + "test_rope_apply_against_the_float64_rotation"],
-    "cm3p_attn_fwd": [KG + "test_attention_global_nopad", KG + "test_attention_random_shapes", KG + "test_attention_sliding_window"],
-    "cm3p_attn_probs": [MG + "test_output_attentions_matches_the_reference_eager_probabilities"],
-    "cm3p_attn_bwd": [KG + "test_attention_global_backward_both_implementations", KG + "test_attention_random_shapes"],
+    "cm3p_attn_fwd": [KG + "test_attention_global_nopad", KG + "test_attention_random_shapes", KG + "test_attention_sliding_window",
+                      AD + "test_matches_float64", AD + "test_exact_conditions", AD + "test_count_probe", AD + "test_window0_copies_v_and_dout"],
+    "cm3p_attn_probs": [MG + "test_output_attentions_matches_the_reference_eager_probabilities",
+                        AD + "test_probs"],
+    "cm3p_attn_bwd": [KG + "test_attention_global_backward_both_implementations", KG + "test_attention_random_shapes",
+                      AD + "test_matches_float64", AD + "test_exact_conditions", AD + "test_count_probe", AD + "test_band_equals_global_when_the_window_covers_everything"],
     "cm3p_attn_fwd_generic": [KG + "test_generic_attention_matches_fp32_reference"],
     "cm3p_attn_bwd_generic": [KG + "test_generic_attention_matches_fp32_reference"],
     "cm3p_attn_fwd_generic_dropout": [DR + "test_generic_attention_dropout_matches_fp32_restatement"],
     "cm3p_attn_bwd_generic_dropout": [DR + "test_generic_attention_dropout_matches_fp32_restatement"],
     "cm3p_rope_apply_generic": [KG + "test_generic_rope_is_the_reference_rotation_and_its_transpose",
                                 RK + "test_rope_apply_against_the_float64_rotation"],
-    "cm3p_attn_bwd_fused": [KG + "test_attention_global_backward_both_implementations"],
-    "cm3p_attn_fwd_dropout": [DR + "test_attention_dropout_matches_fp32_restatement"],
-    "cm3p_attn_bwd_dropout": [DR + "test_attention_dropout_matches_fp32_restatement"],
+    "cm3p_attn_bwd_fused": [KG + "test_attention_global_backward_both_implementations",
+                            AD + "test_matches_float64"],
+    "cm3p_attn_fwd_dropout": [DR + "test_attention_dropout_matches_fp32_restatement",
+                              AD + "test_dropout_at_other_windows"],
+    "cm3p_attn_bwd_dropout": [DR + "test_attention_dropout_matches_fp32_restatement",
+                              AD + "test_dropout_at_other_windows"],
     "cm3p_attn_fwd_dropout_varlen": [DR + "test_attention_dropout_varlen_equals_padded"],
     "cm3p_attn_bwd_dropout_varlen": [DR + "test_attention_dropout_varlen_equals_padded"],
     "cm3p_geglu_fwd": [KG + "test_geglu_and_gelu",
@@ -104,8 +111,10 @@ LEDGER = {
     "cm3p_colsum_f32": [CH + "test_colsum_against_float64"],
     "cm3p_pointwise_loss": [CH + "test_pointwise_loss_against_float64"],
     "cm3p_first_zero_index": [KG + "test_head_kernels"],
-    "cm3p_attn_fwd_varlen": [KG + "test_attention_varlen_equals_padded_on_valid_rows"],
-    "cm3p_attn_bwd_varlen": [KG + "test_attention_varlen_equals_padded_on_valid_rows"],
+    "cm3p_attn_fwd_varlen": [KG + "test_attention_varlen_equals_padded_on_valid_rows",
+                             AD + "test_varlen_equals_padded"],
+    "cm3p_attn_bwd_varlen": [KG + "test_attention_varlen_equals_padded_on_valid_rows",
+                             AD + "test_varlen_equals_padded"],
     "cm3p_gather_rows_f32": [KG + "test_gather_scatter_rows",
                              RK + "test_gather_and_scatter_rows_bit_for_bit"],
     "cm3p_scatter_rows_f32": [KG + "test_gather_scatter_rows",
