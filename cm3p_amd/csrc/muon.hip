@@ -23,6 +23,15 @@ __device__ __forceinline__ float block_sum(float v, float* red) {
     return t;
 }
 
+// fl(fl(a * b) + c): the two roundings of buf.mul_(momentum).add_(g), two kernels in the reference.  Under hipcc __fmul_rn and __fadd_rn
+// are the plain operators, which -ffp-contract=fast (the default) fuses into ONE fma rounding - so the contraction is switched off for
+// this body (tests/test_muon_kernels_gpu.py compares the buffer bit for bit with the two-rounding value).
+__device__ __forceinline__ float mul_then_add(float a, float b, float c) {
+#pragma clang fp contract(off)
+    const float prod = a * b;
+    return prod + c;
+}
+
 // buf = momentum * buf + g;  u = nesterov ? g + momentum * buf : g (sic, :163-164);  X = bf16(u);  partial[mat][blk] = sum float(X)^2
 // (ref:utils/muon_utils.py:160-164 and the first two lines of zeropower_via_newtonschulz5, :46-47)
 template <bool VEC>
@@ -46,7 +55,7 @@ __global__ __launch_bounds__(kThreads) void muon_momentum_kernel(const int64_t* 
             f32x4 u;
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-                bv[j] = __fadd_rn(__fmul_rn(bv[j], momentum), gv[j]);  // buf.mul_(momentum).add_(g): two roundings
+                bv[j] = mul_then_add(bv[j], momentum, gv[j]);  // buf.mul_(momentum).add_(g): two roundings
                 u[j] = nesterov ? fmaf(momentum, bv[j], gv[j]) : gv[j];  // g.add(buf, alpha=momentum)
             }
             reinterpret_cast<f32x4*>(buf)[i] = bv;
@@ -62,7 +71,7 @@ __global__ __launch_bounds__(kThreads) void muon_momentum_kernel(const int64_t* 
         const int64_t beg = per * blockIdx.x, end = min(numel, beg + per);
         for (int64_t e = beg + threadIdx.x; e < end; e += kThreads) {
             const float gv = g[e];
-            const float bv = __fadd_rn(__fmul_rn(buf[e], momentum), gv);
+            const float bv = mul_then_add(buf[e], momentum, gv);
             buf[e] = bv;
             const float u = nesterov ? fmaf(momentum, bv, gv) : gv;
             const uint16_t w = f32_to_bf16_bits(u);

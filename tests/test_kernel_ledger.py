@@ -17,6 +17,7 @@ MG = "tests/test_model_gpu.py::"
 RK = "tests/test_row_kernels_gpu.py::"
 GK = "tests/test_gemm_kernels_gpu.py::"
 AD = "tests/test_attention_d64_gpu.py::"
+MK = "tests/test_muon_kernels_gpu.py::"
 
 LEDGER = {
     "cm3p_layernorm_fwd": [KG + "test_layernorm_fwd_bwd", CH + "test_layernorm_with_many_rows_per_wave",
@@ -119,12 +120,17 @@ LEDGER = {
                              RK + "test_gather_and_scatter_rows_bit_for_bit"],
     "cm3p_scatter_rows_f32": [KG + "test_gather_scatter_rows",
                               RK + "test_gather_and_scatter_rows_bit_for_bit"],
-    "cm3p_gemm_bf16_batched": [MU + "test_batched_gemm_axpby"],
-    "cm3p_muon_partials": [MU + "test_steps_match_the_reference_fixture", MU + "test_model_sized_group_against_the_oracle"],
-    "cm3p_muon_momentum": [MU + "test_steps_match_the_reference_fixture", MU + "test_model_sized_group_against_the_oracle"],
-    "cm3p_muon_normalize": [MU + "test_steps_match_the_reference_fixture", MU + "test_model_sized_group_against_the_oracle"],
-    "cm3p_muon_apply": [MU + "test_steps_match_the_reference_fixture", MU + "test_model_sized_group_against_the_oracle"],
-    "cm3p_adamw_multi": [MU + "test_steps_match_the_reference_fixture"],
+    "cm3p_gemm_bf16_batched": [MU + "test_batched_gemm_axpby",
+                               MK + "test_one_newton_schulz_iteration_against_float64", MK + "test_six_iterations_keep_the_padding_zero_and_everything_finite"],
+    "cm3p_muon_partials": [MU + "test_steps_match_the_reference_fixture", MU + "test_model_sized_group_against_the_oracle",
+                           MK + "test_stage_kernels_against_their_references", MK + "test_an_all_zero_matrix_stays_zero_and_leaves_its_group_alone", MK + "test_two_steps_of_the_class_at_the_block_seams_aligned_and_not"],
+    "cm3p_muon_momentum": [MU + "test_steps_match_the_reference_fixture", MU + "test_model_sized_group_against_the_oracle",
+                           MK + "test_stage_kernels_against_their_references", MK + "test_float4_and_scalar_momentum_kernels_give_the_same_bits", MK + "test_an_all_zero_matrix_stays_zero_and_leaves_its_group_alone", MK + "test_two_steps_of_the_class_at_the_block_seams_aligned_and_not"],
+    "cm3p_muon_normalize": [MU + "test_steps_match_the_reference_fixture", MU + "test_model_sized_group_against_the_oracle",
+                            MK + "test_stage_kernels_against_their_references", MK + "test_an_all_zero_matrix_stays_zero_and_leaves_its_group_alone", MK + "test_two_steps_of_the_class_at_the_block_seams_aligned_and_not"],
+    "cm3p_muon_apply": [MU + "test_steps_match_the_reference_fixture", MU + "test_model_sized_group_against_the_oracle",
+                        MK + "test_stage_kernels_against_their_references", MK + "test_an_all_zero_matrix_stays_zero_and_leaves_its_group_alone", MK + "test_two_steps_of_the_class_at_the_block_seams_aligned_and_not"],
+    "cm3p_adamw_multi": [MU + "test_steps_match_the_reference_fixture", MK + "test_adamw_multi_against_float64"],
 }
 
 EXEMPT = {
