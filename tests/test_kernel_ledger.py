@@ -18,6 +18,7 @@ RK = "tests/test_row_kernels_gpu.py::"
 GK = "tests/test_gemm_kernels_gpu.py::"
 AD = "tests/test_attention_d64_gpu.py::"
 MK = "tests/test_muon_kernels_gpu.py::"
+LH = "tests/test_loss_head_gpu.py::"
 
 LEDGER = {
     "cm3p_layernorm_fwd": [KG + "test_layernorm_fwd_bwd", CH + "test_layernorm_with_many_rows_per_wave",
@@ -97,21 +98,25 @@ LEDGER = {
     "cm3p_pool_bwd": [KG + "test_pooling",
                       RK + "test_pooling_against_float64"],
     "cm3p_gemm_f32": [CH + "test_gemm_f32_all_stride_forms", KG + "test_head_kernels"],
-    "cm3p_l2norm_fwd": [KG + "test_head_kernels"],
-    "cm3p_l2norm_bwd": [KG + "test_head_kernels"],
+    "cm3p_l2norm_fwd": [KG + "test_head_kernels", LH + "test_l2norm_forward_and_backward_against_float64"],
+    "cm3p_l2norm_bwd": [KG + "test_head_kernels", LH + "test_l2norm_forward_and_backward_against_float64"],
     "cm3p_cross_entropy": [CH + "test_cross_entropy_with_the_specs_of_the_contrastive_loss", KG + "test_head_kernels"],
     "cm3p_scale_exp": [CH + "test_scale_exp_dot_and_sum_against_float64"],
-    "cm3p_scale_by": [KG + "test_masked_lm_loss_kernels", CH + "test_cross_entropy_masked_against_float64"],
+    "cm3p_scale_by": [KG + "test_masked_lm_loss_kernels", CH + "test_cross_entropy_masked_against_float64",
+                      LH + "test_scale_by_is_the_fp32_product_in_bits"],
     "cm3p_dot_f32": [CH + "test_scale_exp_dot_and_sum_against_float64"],
-    "cm3p_sum_f32": [CH + "test_scale_exp_dot_and_sum_against_float64", KG + "test_masked_lm_loss_kernels"],
+    "cm3p_sum_f32": [CH + "test_scale_exp_dot_and_sum_against_float64", KG + "test_masked_lm_loss_kernels",
+                     LH + "test_sum_f32_against_float64", LH + "test_add_scaled_node_in_bits"],
     "cm3p_cross_entropy_masked": [CH + "test_cross_entropy_masked_against_float64", CH + "test_single_label_classifier_ignores_minus_100_rows"],
-    "cm3p_inv_valid_count": [KG + "test_masked_lm_loss_kernels"],
-    "cm3p_ce_masked_stats": [KG + "test_masked_lm_loss_kernels"],
-    "cm3p_ce_masked_dlogits_bf16": [KG + "test_masked_lm_loss_kernels"],
+    "cm3p_inv_valid_count": [KG + "test_masked_lm_loss_kernels", LH + "test_inv_valid_count_is_the_fp32_quotient_in_bits"],
+    "cm3p_ce_masked_stats": [KG + "test_masked_lm_loss_kernels",
+                             LH + "test_masked_ce_stats_and_dlogits_at_every_seam", LH + "test_masked_ce_with_a_whole_row_block_ignored_into_guarded_buffers"],
+    "cm3p_ce_masked_dlogits_bf16": [KG + "test_masked_lm_loss_kernels",
+                                    LH + "test_masked_ce_stats_and_dlogits_at_every_seam", LH + "test_masked_ce_with_a_whole_row_block_ignored_into_guarded_buffers"],
     "cm3p_add_bias_f32": [CH + "test_add_bias_is_the_fp32_add_bit_for_bit"],
     "cm3p_colsum_f32": [CH + "test_colsum_against_float64"],
     "cm3p_pointwise_loss": [CH + "test_pointwise_loss_against_float64"],
-    "cm3p_first_zero_index": [KG + "test_head_kernels"],
+    "cm3p_first_zero_index": [KG + "test_head_kernels", LH + "test_first_zero_index_is_the_argmax_of_the_zero_mask"],
     "cm3p_attn_fwd_varlen": [KG + "test_attention_varlen_equals_padded_on_valid_rows",
                              AD + "test_varlen_equals_padded"],
     "cm3p_attn_bwd_varlen": [KG + "test_attention_varlen_equals_padded_on_valid_rows",
