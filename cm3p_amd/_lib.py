@@ -118,6 +118,18 @@ SIGNATURES = {
     "cm3p_adamw_multi": [_P, _P, _P, _P, _P, _I, _L, _F, _F, _F, _F, _F, _P],
 }
 
+# name -> argtypes of the extension headers (include/cm3p_lora.h), one to one as above.  A table of its own: SIGNATURES stays the mirror
+# of cm3p_hip.h and its ABI_VERSION; each extension header carries its own version query.
+EXT_SIGNATURES = {
+    "cm3p_lora_abi_version": [],
+    "cm3p_lora_merge_cast_multi": [_P, _P, _I, _P],
+    "cm3p_lora_grad": [_P, _L, _P, _L, _P, _P, _F, _P, _P, _L, _L, _L, _I, _P, _L, _P],
+    "cm3p_lora_grad_workspace_bytes": [_L, _L, _L, _I],
+    "cm3p_lora_grad_row_block": [_L],
+}
+LORA_ABI_VERSION = 1
+_RETURNS_INT64.add("cm3p_lora_grad_workspace_bytes")
+
 _lib = None
 
 
@@ -136,12 +148,14 @@ def load() -> ctypes.CDLL:
             "cm3p_amd has no CPU or PyTorch fallback."
         )
     lib = ctypes.CDLL(LIB_PATH)
-    for name, argtypes in SIGNATURES.items():
+    for name, argtypes in (*SIGNATURES.items(), *EXT_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if a declared symbol is not exported
         fn.argtypes = argtypes
         fn.restype = c_int64 if name in _RETURNS_INT64 else c_int
     if lib.cm3p_abi_version() != ABI_VERSION:
         raise Cm3pHipError(f"ABI mismatch: library {lib.cm3p_abi_version()} vs binding {ABI_VERSION}; rebuild")
+    if lib.cm3p_lora_abi_version() != LORA_ABI_VERSION:
+        raise Cm3pHipError(f"cm3p_lora.h ABI mismatch: library {lib.cm3p_lora_abi_version()} vs binding {LORA_ABI_VERSION}; rebuild")
     if lib.cm3p_build_ablation_flags() != 0 and os.environ.get("CM3P_ALLOW_ABLATED_LIB") != "1":
         raise Cm3pHipError(
             f"{LIB_PATH} was built with timing-only ablation macros (mask {lib.cm3p_build_ablation_flags():#x}): its results are wrong by "

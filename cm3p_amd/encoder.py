@@ -37,6 +37,11 @@ incoming gradient g in bf16 and writes bf16(g + LN'(dy)), the sum formed in fp32
 Statistics, dw partial sums, softmax and GEMM accumulation stay fp32; weight gradients come out of the wgrad GEMMs in fp32 and are cast to
 the parameter's dtype as on the fp32 stream.  With a dropout plan (train mode, any p > 0) the fp32 stream runs: the dropout sites have
 no bf16 form.
+
+Low-rank adapters (cm3p_amd.lora.add_lora puts `lora_A` / `lora_B` on the container nn.Linear of a projection): the bf16 operand of an
+adapted weight is bf16(W + s B A), made in the stack's one cast launch (K.lora_merge_cast_many; kept across forward-only calls like the
+plain copies), so every GEMM above runs unchanged; the adapter tensors are extra inputs of _EncoderLayerFn and get their gradients from
+K.lora_grad on the operands of the projection's weight-gradient GEMM.  Not on the bf16 stream of training steps.
 """
 from __future__ import annotations
 
@@ -167,11 +172,57 @@ def _bf16_weight_pair(w: Tensor, want_t: bool):
     return _bf16_weight(w), None
 
 
+def lora_of(lin):
+    """-> (A [r, in], B [out, r], s) of a container nn.Linear that carries a low-rank adapter (cm3p_amd.lora.add_lora), or None."""
+    A = getattr(lin, "lora_A", None)
+    return None if A is None else (A, lin.lora_B, float(lin.lora_scale))
+
+
+def _check_lora_operands(w: Tensor, A: Tensor, B: Tensor) -> None:
+    """What the merged cast reads through raw addresses; add_lora refuses the same before it registers anything, this is for edits since."""
+    r = A.shape[0]
+    if w.dtype != torch.float32 or A.dtype != torch.float32 or B.dtype != torch.float32:
+        raise NotImplementedError(f"cm3p_amd LoRA: master weights and adapters must be fp32 (weight {w.dtype}, lora_A {A.dtype}, lora_B {B.dtype})")
+    if r not in K.LORA_RANKS or tuple(A.shape) != (r, w.shape[1]) or tuple(B.shape) != (w.shape[0], r) or w.shape[0] % 8 or w.shape[1] % 8:
+        raise NotImplementedError(f"cm3p_amd LoRA: weight {tuple(w.shape)} with lora_A {tuple(A.shape)}, lora_B {tuple(B.shape)}: r must be one of "
+                                  f"{K.LORA_RANKS} and the weight's extents multiples of 8")
+
+
+def _lora_merged_cached(entries: list) -> list:
+    """Forward-only calls: [(W, A, B, s, geglu_rows)] -> [bf16(W + s B A)] (rows interleaved for a flagged Wi), kept like the copies of
+    _bf16_weight_cached for as long as W, A AND B are the same objects with the same version counters and storage; the misses of one call
+    are merged in one launch."""
+    out, miss = [None] * len(entries), []
+    for n, (w, A, B, s, il) in enumerate(entries):
+        hit = _eval_weights.get((id(w), il, "lora"))
+        if hit is not None and hit[4][0] == s and all(r() is t and v == t._version and p == t.data_ptr()
+                                                      for (r, v, p), t in zip((hit[:3], *hit[4][1:]), (w, A, B))):
+            out[n] = hit[3]
+        else:
+            miss.append(n)
+    if miss:
+        made = K.lora_merge_cast_many([(entries[n][0].detach().contiguous(), entries[n][1].detach().contiguous(), entries[n][2].detach().contiguous(),
+                                        entries[n][3], entries[n][4]) for n in miss])
+        for n, (y, _) in zip(miss, made):
+            w, A, B, s, il = entries[n]
+            y = y.clone()  # (the launch's one allocation also holds the transposes, which no forward-only call reads)
+            stamp = [(weakref.ref(t), t._version, t.data_ptr()) for t in (w, A, B)]
+            _eval_weights[(id(w), il, "lora")] = (*stamp[0], y, (s, stamp[1], stamp[2]))  # (the layout of _bf16_weight_cached's entries, and more)
+            out[n] = y
+    return out
+
+
+def _geglu_fwd_fused(plan, rows: int, Wi: Tensor) -> bool:
+    """Forward-only call on a shape of the ring kernel: the Wi GEMM stores gelu(h) * g itself (CM3P_GEGLU_FUSED=0: the two-kernel path)."""
+    return not (plan is not None and plan.mlp) and Wi.dim() == 2 and K.gemm_geglu_supported(rows, Wi.shape[0] // 2, Wi.shape[1]) \
+        and os.environ.get("CM3P_GEGLU_FUSED", "1") != "0"
+
+
 class _Geometry:
     """Static description of one forward call of the stack (no tensors that need grad)."""
 
     __slots__ = ("B", "S", "H", "I", "nh", "L", "eps", "windows", "key_mask", "rope", "per_batch_pos", "save", "cu", "max_s", "checkpoint",
-                 "handoff", "attn_out", "wcast", "hd", "drop", "bf16", "fused_mlp")
+                 "handoff", "attn_out", "wcast", "hd", "drop", "bf16", "fused_mlp", "lora", "wcast_geglu")
 
 
 def _hand_upstream(geo: _Geometry, gx32: Tensor, gx16: Optional[Tensor]) -> None:
@@ -281,15 +332,21 @@ class _EncoderLayerFn(torch.autograd.Function):
         it = iter(weights)
         w_an = None if i == 0 else _f32(next(it))
         Wqkv, Wo, w_mn, Wi, Wo2 = next(it), next(it), _f32(next(it)), next(it), next(it)
+        # low-rank adapters (cm3p_amd.lora): (A, B, s) per projection in the order Wqkv, Wo, Wi, Wo2; their tensors follow the weights
+        spec = geo.lora[i] if geo.lora is not None else (None,) * 4
+        adapters = [None if sc is None else (next(it).detach(), next(it).detach(), sc) for sc in spec]
         # forward-only and a shape of the ring kernel: the Wi GEMM stores gelu(h) * g itself (CM3P_GEGLU_FUSED=0: the two-kernel path)
-        fuse_geglu = (not geo.save) and not (geo.drop is not None and geo.drop.mlp) and Wi.dim() == 2 and K.gemm_geglu_supported(x.shape[0], Wi.shape[0] // 2, Wi.shape[1]) \
-            and os.environ.get("CM3P_GEGLU_FUSED", "1") != "0"
-        # (training: the casts of every layer were made in one launch at the top of the stack, _run_stack)
-        pre = geo.wcast if geo.save and geo.wcast is not None else {}
+        fuse_geglu = (not geo.save) and _geglu_fwd_fused(geo.drop, x.shape[0], Wi)
+        # (training: the casts of every layer were made in one launch at the top of the stack, _run_stack; adapted weights: their merged
+        # copies bf16(W + s B A) were made there on every kind of call)
+        pre = geo.wcast if geo.wcast is not None else {}
         pairs = [pre.get(id(w)) or _bf16_weight_pair(w, geo.save) if not (fuse_geglu and w is Wi) else (None, None) for w in (Wqkv, Wo, Wi, Wo2)]
         # training step, fused pair (_run_stack decided; CM3P_GEGLU_FUSED=0: the two-kernel path): this Wi's copy has interleaved rows
         fused_train = geo.save and id(Wi) in geo.fused_mlp
-        wb = (w_an, pairs[0][0], pairs[1][0], w_mn, pairs[2][0], pairs[3][0], _bf16_weight_cached(Wi, True) if fuse_geglu else None, fused_train)
+        Wi_geglu = None
+        if fuse_geglu:
+            Wi_geglu = geo.wcast_geglu[id(Wi)] if adapters[2] is not None else _bf16_weight_cached(Wi, True)
+        wb = (w_an, pairs[0][0], pairs[1][0], w_mn, pairs[2][0], pairs[3][0], Wi_geglu, fused_train)
         x_out, acts = _layer_forward(geo, i, x, wb, geo.save)
         if geo.save:
             # gradient checkpointing (ref: supports_gradient_checkpointing, TF GradientCheckpointingLayer): keep only the
@@ -298,6 +355,7 @@ class _EncoderLayerFn(torch.autograd.Function):
             ctx.geo, ctx.i, ctx.wb = geo, i, wb
             ctx.wt = tuple(p[1] for p in pairs)  # W^T copies for the input-gradient GEMMs
             ctx.wdtypes = [w.dtype for w in weights]
+            ctx.lora = adapters
         return x_out
 
     @staticmethod
@@ -311,6 +369,7 @@ class _EncoderLayerFn(torch.autograd.Function):
         need_w = list(need[3:])
         if i == 0:
             need_w.insert(0, False)  # (no attn_norm in layer 0)
+        assert not any(a is not None for a in ctx.lora)  # (refused before the forward ran: CM3PEncoder._bf16_stream)
         n_an, n_qkv, n_o, n_mn, n_i, n_o2 = need_w
         g = _take_bf16_from_downstream(geo, dy)
         if geo.checkpoint:
@@ -359,11 +418,24 @@ class _EncoderLayerFn(torch.autograd.Function):
         if ctx.geo.bf16:
             return _EncoderLayerFn._backward_bf16(ctx, dy)
         geo, i = ctx.geo, ctx.i
-        need = ctx.needs_input_grad  # (geo, i, x, *weights)
-        need_w = list(need[3:])
+        need = ctx.needs_input_grad  # (geo, i, x, *weights, *adapter tensors)
+        n_base = 5 if i == 0 else 6
+        need_w = list(need[3:3 + n_base])
         if i == 0:
             need_w.insert(0, False)  # (no attn_norm in layer 0)
         n_an, n_qkv, n_o, n_mn, n_i, n_o2 = need_w
+        # adapter gradients (dA, dB) of projection p from the operands its weight-gradient GEMM reads; () when it carries no adapter
+        need_l, lora = iter(need[3 + n_base:]), ctx.lora
+        want_l = [None if a is None else (next(need_l), next(need_l)) for a in lora]
+
+        def lora_grads(p: int, dy_p: Tensor, x_p: Tensor):
+            if lora[p] is None:
+                return ()
+            if not any(want_l[p]):
+                return (None, None)
+            dA, dB = K.lora_grad(x_p, dy_p, *lora[p])
+            return (dA if want_l[p][0] else None, dB if want_l[p][1] else None)
+
         gx32, gx16 = _take_from_downstream(geo, dy)
         if geo.checkpoint:
             _, acts = _layer_forward(geo, i, ctx.saved[0], ctx.wb, True)
@@ -379,6 +451,7 @@ class _EncoderLayerFn(torch.autograd.Function):
         fused = len(ctx_wb) > 7 and ctx_wb[7]  # h is h' (interleaved columns): the Wo2 dgrad's store phase turns dg into the canonical dh
         dg = None if fused else K.linear_dgrad(gx16, Wo2_b, Wo2_t)
         dWo2 = K.linear_wgrad(gx16, g) if n_o2 else None
+        l_o2 = lora_grads(3, gx16, g)
         if fused:
             dh = K.linear_dgrad_geglu_bwd(gx16, Wo2_t, h)
         elif geo.drop is not None and geo.drop.mlp:
@@ -388,6 +461,7 @@ class _EncoderLayerFn(torch.autograd.Function):
         del dg, g
         dxn2 = K.linear_dgrad(dh, Wi_b, Wi_t)
         dWi = K.linear_wgrad(dh, xn2) if n_i else None
+        l_i = lora_grads(2, dh, xn2)
         del dh, h, xn2
         gx32, gx16, dw_mn = K.layernorm_bwd(dxn2, x_mid, w_mn, mean_m, rstd_m, gx32, True)
         del dxn2, x_mid
@@ -396,10 +470,12 @@ class _EncoderLayerFn(torch.autograd.Function):
         gt16 = gx16 if ad is None else K.dropout_f32(gx32, ad[0], ad[1], i, K.SITE_ATTN_OUT, geo.S, geo.cu, bf16_only=True)
         do = K.linear_dgrad(gt16, Wo_b, Wo_t)
         dWo = K.linear_wgrad(gt16, o) if n_o else None
+        l_o = lora_grads(1, gt16, o)
         del gt16
         dqkv = _attn_backward(geo, i, qkv, o, do, lse, ad)
         del do, o, qkv
         dWqkv = K.linear_wgrad(dqkv, xn) if n_qkv else None
+        l_qkv = lora_grads(0, dqkv, xn)
         if i == 0:
             dw_an = None
             if need[2]:
@@ -413,6 +489,7 @@ class _EncoderLayerFn(torch.autograd.Function):
         else:  # everything below this layer is frozen: the chain ends here
             dw_an = None
         grads = [dWqkv, dWo, dw_mn, dWi, dWo2] if i == 0 else [dw_an, dWqkv, dWo, dw_mn, dWi, dWo2]
+        grads += [*l_qkv, *l_o, *l_i, *l_o2]
         out = [(gw if gw.dtype == dt else gw.to(dt)) if (nd and gw is not None) else None for gw, dt, nd in zip(grads, ctx.wdtypes, need[3:])]
         return (None, None, gx32 if need[2] else None, *out)
 
@@ -611,6 +688,9 @@ class CM3PEncoder(nn.Module):
         if plan is not None:
             return False
         records = torch.is_grad_enabled() and (any(t is not None and t.requires_grad for t in inputs) or any(p.requires_grad for p in self.parameters()))
+        if records and self._train_residual_dtype is torch.bfloat16 and self.has_lora():
+            raise NotImplementedError("cm3p_amd LoRA: a training call on the bf16 residual stream (train_residual_dtype = torch.bfloat16) is not "
+                                      "supported with adapters attached; set train_residual_dtype back to None, or merge_lora() / remove_lora() first")
         return (self._train_residual_dtype if records else self._residual_dtype) is torch.bfloat16
 
     def train(self, mode: bool = True):
@@ -665,6 +745,14 @@ class CM3PEncoder(nn.Module):
             w = [layer.attn_norm.weight] if i > 0 else []
             ws.append(w + [layer.attn.Wqkv.weight, layer.attn.Wo.weight, layer.mlp_norm.weight, layer.mlp.Wi.weight, layer.mlp.Wo.weight])
         return ws
+
+    def _stack_lora(self):
+        """Per layer: the adapters (A, B, s) or None of Wqkv, Wo, Wi, Wo(mlp); None when the stack carries no adapter at all."""
+        ad = [[lora_of(lin) for lin in (layer.attn.Wqkv, layer.attn.Wo, layer.mlp.Wi, layer.mlp.Wo)] for layer in self.layers]
+        return ad if any(a is not None for row in ad for a in row) else None
+
+    def has_lora(self) -> bool:
+        return self._stack_lora() is not None
 
     def forward(self, input_ids: Optional[Tensor] = None, attention_mask: Optional[Tensor] = None,
                 position_ids: Optional[Tensor] = None, inputs_embeds: Optional[Tensor] = None,
@@ -784,8 +872,10 @@ class CM3PEncoder(nn.Module):
                 tables[is_global] = K.rope_table(pos_tok, self._inv_freq(theta, dev))
         geo.rope = [tables[cfg.is_global_layer(i)] for i in range(geo.L)]
         weights = self._stack_weights()
+        lora = self._stack_lora()
         geo.save = torch.is_grad_enabled() and (x0.requires_grad or self.final_norm.weight.requires_grad
-                                                or any(w.requires_grad for ws in weights for w in ws))
+                                                or any(w.requires_grad for ws in weights for w in ws)
+                                                or (lora is not None and any(t.requires_grad for row in lora for a in row if a is not None for t in a[:2])))
         if bf16 and geo.save and (self._train_residual_dtype is not torch.bfloat16 or plan is not None):
             # (_bf16_stream applies the same rules before the embedding ran)
             raise RuntimeError("cm3p_amd: bf16 residual stream on a call that records a backward without train_residual_dtype, or with dropout")
@@ -794,10 +884,36 @@ class CM3PEncoder(nn.Module):
             invalidate_weight_cache()  # a backward will follow, so an optimizer will: no copy made before this step may outlive it
         geo.wcast = None
         geo.fused_mlp = frozenset()
-        if geo.save and os.environ.get("CM3P_CAST_BATCHED", "1") != "0":
-            # bf16 copies + transposes of every projection weight of the stack in ONE launch (r03: 4 launches per layer)
+        geo.lora = geo.wcast_geglu = None
+        adapted = {}  # id(weight) -> (weight, A, B, s) of the projections that carry an adapter
+        if lora is not None:
+            if bf16 and geo.save:
+                raise NotImplementedError("cm3p_amd LoRA: a training call on the bf16 residual stream is not supported with adapters attached")
+            geo.lora = [tuple(None if a is None else a[2] for a in row) for row in lora]
+            for ws, row in zip(weights, lora):
+                for w, a in zip((ws[-5], ws[-4], ws[-2], ws[-1]), row):
+                    if a is not None:
+                        _check_lora_operands(w, a[0], a[1])
+                        adapted[id(w)] = (w, a[0], a[1], a[2])
+        if adapted and not geo.save:
+            # forward-only: the merged copies are kept across calls (keyed on W, A and B); a Wi whose GEMM stores GeGLU itself gets the
+            # interleaved row order instead of the canonical one
+            ents = [(w, A, B, s, False) for w, A, B, s in adapted.values()]
+            for n, ws in enumerate(weights):
+                if id(ws[-2]) in adapted and _geglu_fwd_fused(plan, x0.shape[0], ws[-2]):
+                    k = [e[0] is ws[-2] for e in ents].index(True)
+                    ents[k] = (*ents[k][:4], True)
+            copies = _lora_merged_cached(ents)
+            geo.wcast = {id(e[0]): (y, None) for e, y in zip(ents, copies) if not e[4]}
+            geo.wcast_geglu = {id(e[0]): y for e, y in zip(ents, copies) if e[4]}
+        if geo.save and (adapted or os.environ.get("CM3P_CAST_BATCHED", "1") != "0"):
+            # bf16 copies + transposes of every projection weight of the stack in ONE launch (r03: 4 launches per layer); adapted weights
+            # go through the merged form of that launch (K.lora_merge_cast_many) whatever CM3P_CAST_BATCHED says
             elig = [w for ws in weights for w in ws
-                    if w.dim() == 2 and w.dtype == torch.float32 and w.shape[0] % 8 == 0 and w.shape[1] % 8 == 0 and w.is_contiguous()]
+                    if w.dim() == 2 and w.dtype == torch.float32 and w.shape[0] % 8 == 0 and w.shape[1] % 8 == 0 and w.is_contiguous()
+                    and (id(w) in adapted or os.environ.get("CM3P_CAST_BATCHED", "1") != "0")]
+            if adapted and any(id(w) not in {id(e) for e in elig} for w, *_ in adapted.values()):
+                raise NotImplementedError("cm3p_amd LoRA: an adapted weight must be a contiguous fp32 matrix")
             if elig:
                 # GeGLU in the store phases of the Wi GEMM and the Wo2 dgrad (K.linear_geglu_fwd / K.linear_dgrad_geglu_bwd): taken by the
                 # layers whose Wi and Wo2 are cast here - the same launch then writes Wi's copy with interleaved rows; the canonical
@@ -807,15 +923,20 @@ class CM3PEncoder(nn.Module):
                         and K.mlp_geglu_fused_supported(x0.shape[0], cfg.intermediate_size, H):
                     cast = {id(w) for w in elig}
                     geo.fused_mlp = frozenset(id(ws[-2]) for ws in weights if id(ws[-2]) in cast and id(ws[-1]) in cast)
-                pairs = K.cast_bf16_with_transpose_many([w.detach() for w in elig], [id(w) in geo.fused_mlp for w in elig])
-                geo.wcast = {id(w): pair for w, pair in zip(elig, pairs)}
+                plain = [w for w in elig if id(w) not in adapted]
+                pairs = K.cast_bf16_with_transpose_many([w.detach() for w in plain], [id(w) in geo.fused_mlp for w in plain])
+                geo.wcast = {id(w): pair for w, pair in zip(plain, pairs)}
+                merged = [adapted[id(w)] for w in elig if id(w) in adapted]
+                pairs = K.lora_merge_cast_many([(w.detach(), A.detach().contiguous(), B.detach().contiguous(), s, id(w) in geo.fused_mlp) for w, A, B, s in merged])
+                geo.wcast.update({id(e[0]): pair for e, pair in zip(merged, pairs)})
         geo.handoff = None
         geo.attn_out = [] if output_attentions else None
         # output_hidden_states: the stack's input and every layer's output (TF:...modeling_modernbert.py:457-470), detached
         hiddens = [x0.detach()] if output_hidden_states else None
         x = x0
         for i in range(geo.L):
-            x = _EncoderLayerFn.apply(geo, i, x, *weights[i])
+            extra = () if lora is None else tuple(t for a in lora[i] if a is not None for t in a[:2])
+            x = _EncoderLayerFn.apply(geo, i, x, *weights[i], *extra)
             if hiddens is not None:
                 hiddens.append(x.detach())
         y = _FinalNormFn.apply(geo, x, self.final_norm.weight)

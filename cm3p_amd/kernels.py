@@ -6,6 +6,7 @@ from __future__ import annotations
 
 import math
 import os
+import struct
 from typing import Optional
 
 import torch
@@ -280,6 +281,77 @@ def cast_bf16_with_transpose_many(ws: list, geglu_rows: Optional[list] = None) -
     tab = torch.tensor(table, dtype=torch.int64).pin_memory().to(dev, non_blocking=True)
     call("cm3p_cast_f32_bf16_t_multi", ptr(tab, torch.int64), len(ws), blocks, stream(), work=8.0 * numel)
     return out
+
+
+# ------------------------------------------------------------------------------------------------ low-rank adapters (include/cm3p_lora.h)
+LORA_RANKS = (8, 16, 32, 64)
+_lib.HBM_BOUND_TAGS.update({"cm3p_lora_merge_cast_multi", "cm3p_lora_grad"})
+
+
+def lora_merge_cast_many(entries: list) -> list:
+    """[(W fp32 [N, K], A fp32 [r, K], B fp32 [N, r], s, geglu_rows)] -> [(bf16(W + s B A), its transpose)] in ONE launch
+    (cm3p_lora_merge_cast_multi): cast_bf16_with_transpose_many with the adapter folded in before the one rounding (fp32 sum over r).
+    geglu_rows: the copy of a Wi gets the row order of geglu_interleave_index; its transpose stays canonical."""
+    if not entries:
+        return []
+    dev = entries[0][0].device
+    numel = sum(e[0].numel() for e in entries)
+    store = torch.empty((2 * numel,), dtype=torch.bfloat16, device=dev)
+    base, out, table, off, blocks = store.data_ptr(), [], [], 0, 0
+    for w, a, b, s, il in entries:
+        rows, cols = w.shape
+        r = a.shape[0]
+        if r not in LORA_RANKS or tuple(a.shape) != (r, cols) or tuple(b.shape) != (rows, r):
+            raise ValueError(f"lora_merge_cast_many: W {tuple(w.shape)} needs A [r, {cols}] and B [{rows}, r] with r in {LORA_RANKS}; got {tuple(a.shape)}, {tuple(b.shape)}")
+        if rows % 8 or cols % 8 or (il and rows % 64):
+            raise ValueError(f"lora_merge_cast_many: extents must be multiples of 8 (2I a multiple of 64 for interleaved GeGLU rows), got {rows} x {cols}")
+        for t in (w, a, b):
+            ptr(t, torch.float32)  # (GPU, contiguous, fp32: the kernel reads raw addresses)
+        y = store[off:off + rows * cols].view(rows, cols)
+        yt = store[off + rows * cols:off + 2 * rows * cols].view(cols, rows)
+        s_bits = int.from_bytes(struct.pack("<f", float(s)), "little")
+        table += [w.data_ptr(), a.data_ptr(), b.data_ptr(), s_bits, -rows if il else rows, cols, r, base + 2 * off, base + 2 * (off + rows * cols), blocks]
+        out.append((y, yt))
+        off += 2 * rows * cols
+        blocks += (-(-rows // 64)) * (-(-cols // 64))
+    # (pinned host memory: see cast_bf16_with_transpose_many; the entry point validates the host copy before it launches)
+    host = torch.tensor(table, dtype=torch.int64).pin_memory()
+    tab = host.to(dev, non_blocking=True)
+    call("cm3p_lora_merge_cast_multi", host.data_ptr(), ptr(tab, torch.int64), len(entries), stream(),
+         work=float(sum(8 * e[0].numel() + 4 * (e[1].numel() + e[2].numel()) for e in entries)))
+    return out
+
+
+def _ptr_rows(t: Tensor):
+    """Device address of a 2-D bf16 operand whose rows may be pitched (unit stride inside a row)."""
+    if not t.is_cuda or t.dim() != 2 or t.dtype != torch.bfloat16 or t.stride(1) != 1 or t.stride(0) < t.shape[1]:
+        raise _lib.Cm3pHipError("cm3p_amd kernels: a pitched operand must be a 2-D bf16 GPU tensor with unit stride inside a row")
+    p = _lib._DevPtr(t.data_ptr())
+    p.dev = t.device.index
+    return p
+
+
+def lora_grad_row_block(T: int) -> int:
+    """Tokens per row block of lora_grad's token reduction (host-only query)."""
+    return query("cm3p_lora_grad_row_block", T)
+
+
+def lora_grad(x: Tensor, dy: Tensor, A: Tensor, B: Tensor, s: float):
+    """Adapter gradients of one adapted weight (cm3p_lora_grad): x [T, K] bf16, dy [T, N] bf16 (rows may be pitched), A [r, K] fp32,
+    B [N, r] fp32 -> (dA [r, K], dB [N, r]) fp32 = (s v^T x, s dy^T u) with u = bf16(x bf16(A)^T), v = bf16(dy bf16(B)); ordered sums."""
+    T, K = x.shape
+    N, r = B.shape
+    if r not in LORA_RANKS or tuple(A.shape) != (r, K) or dy.shape[0] != T or dy.shape[1] != N:
+        raise ValueError(f"lora_grad: x {tuple(x.shape)}, dy {tuple(dy.shape)}, A {tuple(A.shape)}, B {tuple(B.shape)}: need A [r, K], B [N, r], r in {LORA_RANKS}")
+    nbytes = query("cm3p_lora_grad_workspace_bytes", T, K, N, r)
+    if nbytes < 0:
+        raise ValueError(f"lora_grad: unsupported shape T {T} K {K} N {N} r {r} (T >= 1; K, N multiples of 8)")
+    ws = torch.empty((nbytes,), dtype=torch.uint8, device=x.device)
+    dA = _empty((r, K), torch.float32, x)
+    dB = _empty((N, r), torch.float32, x)
+    call("cm3p_lora_grad", _ptr_rows(x), x.stride(0), _ptr_rows(dy), dy.stride(0), ptr(A, torch.float32), ptr(B, torch.float32), float(s),
+         ptr(dA), ptr(dB), T, K, N, r, ptr(ws), nbytes, stream(), work=4.0 * T * (K + N))
+    return dA, dB
 
 
 def add_f32(a: Tensor, b: Tensor, want_bf16: bool = False, inplace: bool = True):
