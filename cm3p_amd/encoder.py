@@ -525,6 +525,122 @@ class _FinalNormFn(torch.autograd.Function):
         return None, gx32 if ctx.needs_input_grad[1] else None, dw.to(ctx.wdtype) if ctx.needs_input_grad[2] else None
 
 
+def _zero_padded_rows(t: Tensor, rows: int) -> Tensor:
+    """t [n, C] -> [rows, C] with zero rows behind (a copy, no arithmetic): a row block whose row count is not a multiple of 8 is filled
+    up for the GEMMs; zero rows change no sum."""
+    if t.shape[0] == rows:
+        return t
+    out = t.new_zeros((rows, t.shape[1]))
+    out[:t.shape[0]].copy_(t)
+    return out
+
+
+class _TakeRowsFn(torch.autograd.Function):
+    """x [R, H] fp32 or bf16 -> x[idx]; backward scatters into zeros (rows of x's dtype both ways)."""
+
+    @staticmethod
+    def forward(ctx, x: Tensor, idx: Tensor):
+        ctx.idx, ctx.rows = idx, x.shape[0]
+        return K.gather_rows(x.contiguous(), idx)
+
+    @staticmethod
+    def backward(ctx, dy: Tensor):
+        return K.scatter_rows(dy.contiguous(), ctx.idx, ctx.rows), None
+
+
+class _ClsLastLayerFn(torch.autograd.Function):
+    """The LAST encoder layer where only row 0 of every sequence is consumed (CM3PEncoder.cls_only_last_layer): x [T, H] + the layer's
+    weights -> the layer's output on the query rows alone, [Bn, H] (fp32; bf16 on the bf16 residual stream of a forward-only call).
+
+    attn_norm and the Wqkv + RoPE projection run on all T rows - K and V come from every token - with the kernels of _layer_forward;
+    attention is one query per (sequence, head) (K.attn_row_fwd); the residual rows of the queries are gathered (`qidx`: their row
+    numbers) and Wo + residual, mlp_norm, Wi, GeGLU and Wo2 + residual run on Bn rows (zero rows fill the block up to a multiple of 8).
+    The same function of the same weights as _EncoderLayerFn followed by a row selection.  The backward mirrors it: the row block's
+    chain, K.attn_row_bwd (dqkv in the full layout, its q third zero off the query rows) into the Wqkv weight and input gradients
+    unchanged, and a residual-stream gradient that is zero except on the query rows into attn_norm's backward.
+    No dropout, no adapters on this layer, no checkpointing, fp32 stream when a backward is recorded: _run_stack sends every other
+    call through the full layer."""
+
+    @staticmethod
+    def forward(ctx, geo: _Geometry, i: int, x: Tensor, qidx: Tensor, *weights: Tensor):
+        it = iter(weights)
+        w_an = None if i == 0 else _f32(next(it))
+        Wqkv, Wo, w_mn, Wi, Wo2 = next(it), next(it), _f32(next(it)), next(it), next(it)
+        pre = geo.wcast if geo.wcast is not None else {}
+        pairs = [pre.get(id(w)) or _bf16_weight_pair(w, geo.save) for w in (Wqkv, Wo, Wi, Wo2)]
+        Wqkv_b, Wo_b, Wi_b, Wo2_b = (p[0] for p in pairs)
+        B, S, nh = geo.B, geo.S, geo.nh
+        scale = geo.hd ** -0.5
+        cos, sin = geo.rope[i]
+        if i == 0:
+            xn, mean_a, rstd_a = (x if x.dtype == torch.bfloat16 else K.cast_bf16(x)), None, None
+        else:
+            _, xn, mean_a, rstd_a = K.layernorm_fwd(x, w_an, geo.eps, False, True, geo.save)
+        qkv = K.qkv_linear_rope(xn, Wqkv_b, cos, sin, S, geo.per_batch_pos, q_scale=K.SOFTMAX_Q_SCALE)
+        o, lse = K.attn_row_fwd(qkv, geo.key_mask, geo.cu, B, geo.max_s if geo.cu is not None else S, nh, geo.windows[i], scale, prescaled=True)
+        Bp = (B + 7) // 8 * 8
+        o_p = _zero_padded_rows(o, Bp)
+        x_mid = K.linear_fwd(o_p, Wo_b, resid=_zero_padded_rows(K.gather_rows(x, qidx), Bp))
+        _, xn2, mean_m, rstd_m = K.layernorm_fwd(x_mid, w_mn, geo.eps, False, True, geo.save)
+        h = K.linear_fwd(xn2, Wi_b)
+        g = K.geglu_fwd(h)
+        x_out = K.linear_fwd(g, Wo2_b, resid=x_mid)
+        if geo.save:
+            ctx.saved = (x, xn, mean_a, rstd_a, qkv, o, o_p, lse, x_mid, xn2, mean_m, rstd_m, h, g)
+            ctx.geo, ctx.i, ctx.qidx = geo, i, qidx
+            ctx.wn, ctx.wb, ctx.wt = (w_an, w_mn), (Wqkv_b, Wo_b, Wi_b, Wo2_b), tuple(p[1] for p in pairs)
+            ctx.wdtypes = [w.dtype for w in weights]
+        return x_out[:B] if Bp != B else x_out
+
+    @staticmethod
+    def backward(ctx, dy: Tensor):
+        geo, i, qidx = ctx.geo, ctx.i, ctx.qidx
+        need = ctx.needs_input_grad  # (geo, i, x, qidx, *weights)
+        need_w = list(need[4:])
+        if i == 0:
+            need_w.insert(0, False)  # (no attn_norm in layer 0)
+        n_an, n_qkv, n_o, n_mn, n_i, n_o2 = need_w
+        B, S, nh, scale = geo.B, geo.S, geo.nh, geo.hd ** -0.5
+        gx32, gx16 = _take_from_downstream(geo, dy)
+        x, xn, mean_a, rstd_a, qkv, o, o_p, lse, x_mid, xn2, mean_m, rstd_m, h, g = ctx.saved
+        (w_an, w_mn), (Wqkv_b, Wo_b, Wi_b, Wo2_b), (Wqkv_t, Wo_t, Wi_t, Wo2_t) = ctx.wn, ctx.wb, ctx.wt
+        ctx.saved = ctx.wb = ctx.wt = None
+        Bp = x_mid.shape[0]
+        gx32, gx16 = _zero_padded_rows(gx32, Bp), _zero_padded_rows(gx16, Bp)
+        # ---- the row block: x_out = x_mid + g Wo2^T, x_mid = x[qidx] + o Wo^T
+        dg = K.linear_dgrad(gx16, Wo2_b, Wo2_t)
+        dWo2 = K.linear_wgrad(gx16, g) if n_o2 else None
+        dh = K.geglu_bwd(dg, h)
+        del dg, g, h
+        dxn2 = K.linear_dgrad(dh, Wi_b, Wi_t)
+        dWi = K.linear_wgrad(dh, xn2) if n_i else None
+        del dh, xn2
+        gx32, gx16, dw_mn = K.layernorm_bwd(dxn2, x_mid, w_mn, mean_m, rstd_m, gx32, True)
+        del dxn2, x_mid
+        do = K.linear_dgrad(gx16, Wo_b, Wo_t)
+        dWo = K.linear_wgrad(gx16, o_p) if n_o else None
+        # ---- all rows: dqkv in the full layout (q third zero off the query rows), then what every layer does with it
+        dqkv = K.attn_row_bwd(qkv, o, do[:B].contiguous(), lse, geo.key_mask, geo.cu, B, geo.max_s if geo.cu is not None else S, nh, geo.windows[i], scale,
+                              geo.rope[i], geo.per_batch_pos, prescaled=True)
+        del do, o, o_p, qkv
+        dWqkv = K.linear_wgrad(dqkv, xn) if n_qkv else None
+        dw_an = None
+        gfull = None
+        if need[2] or n_an:
+            # the residual stream's own gradient: zero except on the query rows
+            gfull = K.scatter_rows(gx32[:B].contiguous(), qidx, x.shape[0])
+            dxn = K.linear_dgrad(dqkv, Wqkv_b, Wqkv_t)
+            if i == 0:
+                gfull, _ = K.add_f32(gfull, dxn, want_bf16=False)
+                _hand_upstream(geo, gfull, None)
+            else:
+                gfull, g16, dw_an = K.layernorm_bwd(dxn, x, w_an, mean_a, rstd_a, gfull, True)
+                _hand_upstream(geo, gfull, g16)
+        grads = [dWqkv, dWo, dw_mn, dWi, dWo2] if i == 0 else [dw_an, dWqkv, dWo, dw_mn, dWi, dWo2]
+        out = [(gw if gw.dtype == dt else gw.to(dt)) if (nd and gw is not None) else None for gw, dt, nd in zip(grads, ctx.wdtypes, need[4:])]
+        return (None, None, gfull if need[2] else None, None, *out)
+
+
 class _EmbedLNFn(torch.autograd.Function):
     """LayerNorm(tok_embeddings[ids]) with optional audio rows scattered over the placeholder tokens
     (TF:...modeling_modernbert.py:64-71, ref:cm3p/modeling_cm3p.py:592,603-605).  bf16: the bf16 output alone (the bf16 residual
@@ -636,6 +752,7 @@ class CM3PEncoder(nn.Module):
         self.gradient_checkpointing = False  # set by PreTrainedModel.gradient_checkpointing_enable()
         self.residual_dtype = None  # None / torch.float32: fp32 residual stream; torch.bfloat16: bf16 on forward-only calls
         self.train_residual_dtype = None  # the same choice for calls that record a backward (training steps)
+        self.cls_only_last_layer = False  # opt-in: the last layer (and the final norm) on row 0 of every sequence only
         self._inv_freq_cache = {}
         # init roles (TF:...modeling_modernbert.py:372-386): 'in'/'embedding' std = initializer_range,
         # 'out' std = initializer_range / sqrt(2 L); consumed by CM3PPreTrainedModel._init_weights
@@ -680,6 +797,27 @@ class CM3PEncoder(nn.Module):
         if dtype is not None and dtype not in (torch.float32, torch.bfloat16):
             raise ValueError(f"train_residual_dtype must be None, torch.float32 or torch.bfloat16, got {dtype!r}")
         self._train_residual_dtype = dtype
+
+    @property
+    def cls_only_last_layer(self) -> bool:
+        """Opt-in for callers whose only consumer of this encoder is the pooled CLS row h[:, 0] (`cls_embed: true` towers, a
+        `classifier_pooling == "cls"` head): the last layer and the final norm are computed for row 0 of every sequence only.
+        The encoder then returns `(B, 1, H)` for padded and `unpad` calls and `(Bn, H)` - one row per sequence of `cu_seqlens` - for
+        caller-packed rows; with `output_hidden_states` the last entry is that short tensor and the others are unchanged.  The rows are
+        the same function of the same weights as row 0 of the full result: attn_norm and the Wqkv + RoPE projection still run on
+        every token (K and V come from all of them), attention is one query per (sequence, head) (csrc/attention_row.hip), and
+        Wo, mlp_norm, the GeGLU MLP and the final norm run on B rows (_ClsLastLayerFn).  Supported on that route: the fp32 stream
+        (forward-only and training), the bf16 stream of forward-only calls, padded execution, `unpad`, caller-packed rows.
+        Where the row route has no form - an active dropout plan, adapters on the last layer, the bf16 stream of a training step,
+        head_dim other than 64, gradient checkpointing - the full layer runs and its row 0 is taken, so the output SHAPE does not
+        depend on the route (and the values are those of the switch-off call, bit for bit).  `output_attentions` raises
+        NotImplementedError.  Consumers of all rows (mean pooling, an MLM or decoder head) must leave the switch off; the model classes
+        refuse such calls.  Not part of the state dict or config; off by default, and off changes nothing."""
+        return self._cls_only_last_layer
+
+    @cls_only_last_layer.setter
+    def cls_only_last_layer(self, value) -> None:
+        self._cls_only_last_layer = bool(value)
 
     def _bf16_stream(self, plan: Optional[_DropPlan], *inputs: Optional[Tensor]) -> bool:
         """Whether this call runs the bf16 residual stream: there is no dropout plan, and the switch of the call's kind is set -
@@ -777,6 +915,10 @@ class CM3PEncoder(nn.Module):
             if output_attentions:
                 raise NotImplementedError("output_attentions needs head_dim 64")
             unpad = False
+        cls_only = self._cls_only_last_layer
+        if cls_only and output_attentions:
+            raise NotImplementedError("output_attentions with cls_only_last_layer: the last layer computes one query per sequence, there is no "
+                                      "(B, nh, S, S) probability tensor for it; switch cls_only_last_layer off for such a call")
         plan = self._dropout_plan()  # (before any launch: a refused graph capture has captured nothing)
         if output_attentions and plan is not None and plan.attn:
             raise NotImplementedError("output_attentions with attention dropout in training mode (the kernels return undropped probabilities)")
@@ -784,7 +926,8 @@ class CM3PEncoder(nn.Module):
         if cu_seqlens is not None:
             if output_attentions:
                 raise NotImplementedError("output_attentions with unpadded inputs: attention probabilities are (B, nh, S, S) tensors of a padded batch")
-            return self._forward_prepacked(input_ids, position_ids, audio_slot, audio_rows, cu_seqlens, max_seqlen, output_hidden_states, plan, bf16)
+            return self._forward_prepacked(input_ids, position_ids, audio_slot, audio_rows, cu_seqlens, max_seqlen, output_hidden_states, plan, bf16,
+                                           cls_only)
         if output_attentions:
             unpad = False  # the probabilities are laid out per padded (batch, head, query, key)
         if input_ids is not None and input_ids.dtype != torch.int64:
@@ -821,22 +964,28 @@ class CM3PEncoder(nn.Module):
             x0 = _LayerNormFn.apply(inputs_embeds.reshape(B * S, H), self.embeddings.norm.weight, cfg.norm_eps, bf16)
 
         x0 = self._embed_dropout(x0, plan, S, packed[1] if packed is not None else None)
-        y, hiddens, attns = self._run_stack(x0, B, S, attention_mask, position_ids, packed, output_hidden_states, dev, output_attentions, plan, bf16)
+        y, hiddens, attns = self._run_stack(x0, B, S, attention_mask, position_ids, packed, output_hidden_states, dev, output_attentions, plan, bf16,
+                                            cls_only)
+        short = [hiddens.pop()] if (cls_only and hiddens is not None) else []  # (the last layer's output: one row per sequence already)
         if hiddens is not None:
             if packed is not None:
                 hiddens = [K.scatter_rows(h[:n_valid].contiguous(), idx, B * S) for h in hiddens]
-            hiddens = tuple(h.view(B, S, H) for h in hiddens)
-        if packed is not None:
-            y = _PadRowsFn.apply(y, idx, n_valid, B * S)
-        y = y.view(B, S, H)
+            hiddens = tuple(h.view(B, S, H) for h in hiddens) + tuple(h.view(B, 1, H) for h in short)
+        if cls_only:
+            y = y.view(B, 1, H)
+        else:
+            if packed is not None:
+                y = _PadRowsFn.apply(y, idx, n_valid, B * S)
+            y = y.view(B, S, H)
         if output_attentions:
             return y, hiddens, attns
         return (y, hiddens) if output_hidden_states else y
 
     def _run_stack(self, x0: Tensor, B: int, S: int, attention_mask, position_ids, packed, output_hidden_states: bool, dev,
-                   output_attentions: bool = False, plan: Optional[_DropPlan] = None, bf16: bool = False):
+                   output_attentions: bool = False, plan: Optional[_DropPlan] = None, bf16: bool = False, cls_only: bool = False):
         """The L encoder layers + final norm on [rows, H]; `packed` = (idx, cu, max_s, n_valid, n_rows, pos) for unpadded execution;
-        `plan`: the call's dropout (None: none); `bf16`: x0 is bf16 and the stream stays bf16 (_bf16_stream)."""
+        `plan`: the call's dropout (None: none); `bf16`: x0 is bf16 and the stream stays bf16 (_bf16_stream); `cls_only`: y and the last
+        hidden state are the rows of query position 0 alone, [sequences, H] (cls_only_last_layer)."""
         cfg = self.config
         H = cfg.hidden_size
         geo = _Geometry()
@@ -880,6 +1029,9 @@ class CM3PEncoder(nn.Module):
             # (_bf16_stream applies the same rules before the embedding ran)
             raise RuntimeError("cm3p_amd: bf16 residual stream on a call that records a backward without train_residual_dtype, or with dropout")
         geo.bf16 = bf16
+        # cls_only_last_layer: the row route where it has a form, else the full layer and a row selection behind the final norm
+        row_route = cls_only and geo.hd == 64 and plan is None and not geo.checkpoint and not (bf16 and geo.save) \
+            and (lora is None or all(a is None for a in lora[geo.L - 1]))
         if geo.save and _eval_weights:
             invalidate_weight_cache()  # a backward will follow, so an optimizer will: no copy made before this step may outlive it
         geo.wcast = None
@@ -922,13 +1074,19 @@ class CM3PEncoder(nn.Module):
                 if not (plan is not None and plan.mlp) and os.environ.get("CM3P_GEGLU_FUSED", "1") != "0" \
                         and K.mlp_geglu_fused_supported(x0.shape[0], cfg.intermediate_size, H):
                     cast = {id(w) for w in elig}
-                    geo.fused_mlp = frozenset(id(ws[-2]) for ws in weights if id(ws[-2]) in cast and id(ws[-1]) in cast)
+                    # (not the last layer on the row route: its Wi is a plain GEMM on B rows and reads the canonical copy)
+                    geo.fused_mlp = frozenset(id(ws[-2]) for n, ws in enumerate(weights)
+                                              if id(ws[-2]) in cast and id(ws[-1]) in cast and not (row_route and n == geo.L - 1))
                 plain = [w for w in elig if id(w) not in adapted]
                 pairs = K.cast_bf16_with_transpose_many([w.detach() for w in plain], [id(w) in geo.fused_mlp for w in plain])
                 geo.wcast = {id(w): pair for w, pair in zip(plain, pairs)}
                 merged = [adapted[id(w)] for w in elig if id(w) in adapted]
                 pairs = K.lora_merge_cast_many([(w.detach(), A.detach().contiguous(), B.detach().contiguous(), s, id(w) in geo.fused_mlp) for w, A, B, s in merged])
                 geo.wcast.update({id(e[0]): pair for e, pair in zip(merged, pairs)})
+        n_seq = geo.B - (1 if (packed is not None and packed[4] != packed[3]) else 0)  # (without the pseudo-sequence of alignment rows)
+        qidx = None
+        if cls_only:  # the row of query position 0 of every sequence
+            qidx = geo.cu[:-1].to(torch.int64) if geo.cu is not None else torch.arange(B, device=dev, dtype=torch.int64) * S
         geo.handoff = None
         geo.attn_out = [] if output_attentions else None
         # output_hidden_states: the stack's input and every layer's output (TF:...modeling_modernbert.py:457-470), detached
@@ -936,16 +1094,28 @@ class CM3PEncoder(nn.Module):
         x = x0
         for i in range(geo.L):
             extra = () if lora is None else tuple(t for a in lora[i] if a is not None for t in a[:2])
-            x = _EncoderLayerFn.apply(geo, i, x, *weights[i], *extra)
+            if row_route and i == geo.L - 1:
+                x = _ClsLastLayerFn.apply(geo, i, x, qidx, *weights[i])  # [geo.B, H]
+            else:
+                x = _EncoderLayerFn.apply(geo, i, x, *weights[i], *extra)
             if hiddens is not None:
-                hiddens.append(x.detach())
+                if cls_only and i == geo.L - 1:
+                    hiddens.append((x.detach() if row_route else K.gather_rows(x.detach(), qidx))[:n_seq])
+                else:
+                    hiddens.append(x.detach())
         y = _FinalNormFn.apply(geo, x, self.final_norm.weight)
+        if cls_only:
+            if not row_route:
+                y = _TakeRowsFn.apply(y, qidx)
+            if n_seq != y.shape[0]:
+                y = y[:n_seq]
         attns = tuple(geo.attn_out) if geo.attn_out is not None else None
         geo.attn_out = None
         return y, hiddens, attns
 
     def _forward_prepacked(self, input_ids: Tensor, position_ids: Optional[Tensor], audio_slot, audio_rows, cu_seqlens: Tensor,
-                           max_seqlen: Optional[int], output_hidden_states: bool, plan: Optional[_DropPlan] = None, bf16: bool = False):
+                           max_seqlen: Optional[int], output_hidden_states: bool, plan: Optional[_DropPlan] = None, bf16: bool = False,
+                           cls_only: bool = False):
         """Caller-supplied unpadded inputs (ref:cm3p/modeling_cm3p.py:911-931 when `indices` / `cu_seqlens` / `max_seqlen` are given;
         the layout of _unpad_cm3p_input, :65-104): input_ids (total,), cu_seqlens (batch + 1,) -> last_hidden_state (total, H),
         NOT re-padded (the reference's encoder leaves caller-packed rows packed as well)."""
@@ -987,11 +1157,13 @@ class CM3PEncoder(nn.Module):
                               -1 if pad is None else pad, None if slot_p is None else slot_p.contiguous(), audio_rows, bf16)
         packed = (None, cu, max(max_s, n_rows - total), total, n_rows, pos.contiguous())
         x0 = self._embed_dropout(x0, plan, max_s, cu)
-        y, hiddens, _ = self._run_stack(x0, cu.numel() - 1, max_s, None, None, packed, output_hidden_states, dev, plan=plan, bf16=bf16)
+        y, hiddens, _ = self._run_stack(x0, cu.numel() - 1, max_s, None, None, packed, output_hidden_states, dev, plan=plan, bf16=bf16,
+                                        cls_only=cls_only)
         if n_rows != total:
-            y = y[:total]
+            if not cls_only:
+                y = y[:total]
             if hiddens is not None:
-                hiddens = [h[:total] for h in hiddens]
+                hiddens = [h[:total] for h in hiddens[:-1]] + [hiddens[-1]] if cls_only else [h[:total] for h in hiddens]
         return (y, tuple(hiddens)) if output_hidden_states else y
 
     @staticmethod

@@ -178,6 +178,20 @@ class FusedModernBertModel(ModernBertPreTrainedModel):
     def gradient_checkpointing(self, value: bool) -> None:  # (what gradient_checkpointing_enable / _disable set)
         self.encoder.gradient_checkpointing = bool(value)
 
+    @property
+    def cls_only_last_layer(self) -> bool:
+        """`CM3PEncoder.cls_only_last_layer` of this tower's encoder (opt-in, off by default): the last layer and the final norm run
+        on row 0 of every sequence only and `last_hidden_state` is (B, 1, H) - with `output_hidden_states` so is the last entry.  A
+        sequence-classification model returned by `fuse()` with `classifier_pooling == "cls"` reads `last_hidden_state[:, 0]` and runs
+        unchanged on it.  Heads that read every row must leave the switch off: `classifier_pooling == "mean"` (the HF head would
+        broadcast the one row against the mask without an error), token classification, question answering;
+        `FusedModernBertForMaskedLM` refuses the call itself."""
+        return self.encoder.cls_only_last_layer
+
+    @cls_only_last_layer.setter
+    def cls_only_last_layer(self, value: bool) -> None:
+        self.encoder.cls_only_last_layer = bool(value)
+
     def train(self, mode: bool = True):
         self.encoder.train(mode)  # dropout and per-layer recompute follow the encoder's own flag
         return super().train(mode)
@@ -301,6 +315,8 @@ class FusedModernBertForMaskedLM(ModernBertPreTrainedModel):
                 output_hidden_states: Optional[bool] = None, return_dict: Optional[bool] = None, **kwargs) -> MaskedLMOutput:
         from .modeling_cm3p import _MLMHeadFn, _MLMHeadLossFn, _TakeRowsFn
 
+        if self.model.cls_only_last_layer:
+            raise ValueError("FusedModernBertForMaskedLM with cls_only_last_layer: the MLM head reads every row of the last layer; switch it off")
         out = self.model(input_ids=input_ids, attention_mask=attention_mask, position_ids=position_ids, inputs_embeds=inputs_embeds,
                          output_attentions=output_attentions, output_hidden_states=output_hidden_states, return_dict=True)
         hs = out.last_hidden_state

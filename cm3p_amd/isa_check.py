@@ -234,8 +234,25 @@ def check_head(isa: str):
             _need(int(m.group(1)) == 0, f"{sym}: {key} = {m.group(1)} (the {tm} x {tn} outputs of a thread and its staged loads must stay in registers)")
 
 
+# ------------------------------------------------------------------------------------------------ attention_row.hip
+def check_attention_row(isa: str):
+    """The single-query kernels (attention_row.hip) are plain fp32 VALU code with ordinary vector loads and stores: both forward and all
+    four backward instances exist, none spills or has a private segment, and none stages through LDS-DMA, uses an atomic or a matrix
+    core - the file is outside the bounds audit (build.AUDIT_SOURCES) and promises equal bits for equal inputs on that basis."""
+    no_scratch(isa, "attention_row.hip")
+    for name, n in (("attn_row_fwd_kernel", 2), ("attn_row_bwd_kernel", 4)):
+        bodies = kernel_bodies(isa, name)
+        _need(len(bodies) == n, f"{name}: {len(bodies)} instances, expected {n}")
+        for sym, body in bodies.items():
+            _need(not re.search(r"\bglobal_load_lds_|\bbuffer_load_\S+\s.*\blds\b", body), f"{sym}: LDS-DMA in a kernel that is not bounds-audited")
+            _need(not re.search(r"\b(global|flat|ds|buffer)_atomic_|\bds_(add|max|min)_", body), f"{sym}: an atomic in a kernel with a fixed reduction order")
+            _need("v_mfma" not in body and "scratch_" not in body, f"{sym}: matrix-core or scratch instruction")
+            _need(re.search(r"\bglobal_load_dwordx4\b", body) and re.search(r"\bglobal_store_dwordx4\b", body) or name == "attn_row_fwd_kernel",
+                  f"{sym}: the 16-byte row loads / stores are missing")
+
+
 CHECKS = {"head.hip": check_head, "gemm8p.hip": check_gemm8p, "attention_fwd.hip": check_attention_fwd, "attention_bwd_fused.hip": check_attention_bwd_fused,
-          "attention_hd.hip": check_attention_hd}
+          "attention_hd.hip": check_attention_hd, "attention_row.hip": check_attention_row}
 
 
 def check_file(src: str, flags: list[str]) -> None:

@@ -590,6 +590,37 @@ def attn_bwd_varlen(qkv: Tensor, out: Tensor, dout: Tensor, lse: Tensor, cu: Ten
     return dqkv
 
 
+# ---- single-query attention for the pooled CLS row (include/cm3p_attn_row.h, csrc/attention_row.hip) ---------------------------------
+_lib.HBM_BOUND_TAGS.update({"attn_row_fwd_kernel", "attn_row_bwd_kernel"})  # one pass over K and V; the backward also writes all of dqkv
+
+
+def attn_row_fwd(qkv: Tensor, key_mask: Optional[Tensor], cu: Optional[Tensor], B: int, S: int, nh: int, window: int, scale: float,
+                 prescaled: bool = False):
+    """Attention of query position 0 of every sequence.  qkv [B * S, 3 * nh * 64] (or the packed rows [total, ...] with their int32
+    cu_seqlens, S = max_seqlen, no key mask) -> out [B, nh * 64] bf16, lse [B, nh] fp32."""
+    total = qkv.shape[0] if cu is not None else 0
+    out = torch.empty((B, nh * 64), dtype=torch.bfloat16, device=qkv.device)
+    lse = torch.empty((B, nh), dtype=torch.float32, device=qkv.device)
+    keys = S if window < 0 else min(S, window + 1)
+    call("cm3p_attn_row_fwd", ptr(qkv, torch.bfloat16), ptr(out), ptr(lse, torch.float32), ptr(key_mask, torch.uint8), ptr(cu, torch.int32), B, S, total,
+         nh, window, scale, int(prescaled), stream(), tag="attn_row_fwd_kernel", work=2.0 * B * nh * keys * 128)
+    return out, lse
+
+
+def attn_row_bwd(qkv: Tensor, out: Tensor, dout: Tensor, lse: Tensor, key_mask: Optional[Tensor], cu: Optional[Tensor], B: int, S: int, nh: int,
+                 window: int, scale: float, rope: Optional[tuple] = None, per_batch: bool = False, prescaled: bool = False) -> Tensor:
+    """-> dqkv in qkv's full layout, every element written: the q third is zero off the query rows.  rope = (cos, sin): also applies the
+    inverse rotary rotation to dq / dk (per-token tables in the packed form)."""
+    total = qkv.shape[0] if cu is not None else 0
+    dqkv = torch.empty_like(qkv)
+    cos, sin = rope if rope is not None else (None, None)
+    rows = total if cu is not None else B * S
+    call("cm3p_attn_row_bwd", ptr(qkv, torch.bfloat16), ptr(out, torch.bfloat16), ptr(dout, torch.bfloat16), ptr(lse, torch.float32), ptr(dqkv),
+         ptr(key_mask, torch.uint8), ptr(cu, torch.int32), B, S, total, nh, window, scale, ptr(cos, torch.float32), ptr(sin, torch.float32),
+         S if (per_batch and cu is None) else 0, int(prescaled), stream(), tag="attn_row_bwd_kernel", work=5.0 * rows * nh * 128)
+    return dqkv
+
+
 def _rows_as_f32(src: Tensor) -> Tensor:
     """bf16 rows [n, H] (H even) as fp32 rows [n, H / 2] of the same bits: the row copies below move them unchanged."""
     return src.view(torch.float32) if src.dtype == torch.bfloat16 else src

@@ -379,6 +379,26 @@ class CM3PPreTrainedModel(PreTrainedModel):
     _supports_sdpa = True
     _supports_flex_attn = False
 
+    def _pooled_towers(self):
+        return [t for t in (getattr(self, "beatmap_model", None), getattr(self, "metadata_model", None)) if t is not None]
+
+    @property
+    def cls_only_last_layer(self) -> bool:
+        """Opt-in for `cls_embed: true` towers (CM3PEncoder.cls_only_last_layer): the last encoder layer and the final norm of the
+        beatmap and metadata towers run on the pooled CLS row of every sequence only; `last_hidden_state` is then (B, 1, H) (with
+        (B, V, L) metadata: (B, V, 1, H); caller-packed rows: (Bn, H)) and the pooled outputs, embeddings, logits, loss and gradients
+        are those of the full layer.  Set on every pooled tower this model owns (the audio encoder has no pooling and no switch), True
+        when all of them have it.  A call whose consumer needs all rows - mean pooling (`cls_embed` false) with a pooled output, the
+        MLM / decoder head (`has_decoder_head`, `output_logits`, CM3PForMaskedLM) - raises ValueError before any launch, and
+        `output_attentions` NotImplementedError.  Off by default; not part of the state dict or config."""
+        towers = self._pooled_towers()
+        return bool(towers) and all(t.cls_only_last_layer for t in towers)
+
+    @cls_only_last_layer.setter
+    def cls_only_last_layer(self, value: bool):
+        for t in self._pooled_towers():
+            t.cls_only_last_layer = bool(value)
+
     def set_residual_dtype(self, dtype: Optional[torch.dtype], training: bool = False):
         """Set `residual_dtype` on every encoder this model owns (beatmap, metadata and audio towers): torch.bfloat16 runs the
         residual stream of forward-only calls in bf16, the reference's inference recipe (a bf16 model called under no_grad);
@@ -432,13 +452,44 @@ def _pool_packed(h: Tensor, cu_seqlens: Tensor, max_seqlen: Optional[int], cls: 
     return _PoolPackedFn.apply(h, cu_seqlens, int(max_seqlen), cls)
 
 
+def _cls_only_call(tower, output_attentions, output_pooler: bool) -> bool:
+    """Whether this tower call runs with cls_only_last_layer; the calls the switch has no form for are refused here, before any launch."""
+    if not tower.encoder.cls_only_last_layer:
+        return False
+    if output_attentions:
+        raise NotImplementedError("output_attentions with cls_only_last_layer: the last layer computes one query per sequence; switch "
+                                  "cls_only_last_layer off for such a call")
+    if output_pooler and not tower.config.cls_embed:
+        raise ValueError("cls_only_last_layer with mean pooling (cls_embed = False): the pooled output reads every row of the last layer; "
+                         "switch cls_only_last_layer off on this tower")
+    return True
+
+
+def _pool_cls_rows(h: Tensor) -> Tensor:
+    """Pooled output of a tower that ran with cls_only_last_layer: its rows as they are, (B, 1, H) or (Bn, H) -> [B, H] fp32."""
+    if h.dim() == 3:
+        return _PoolFn.apply(h, None, True)
+    return h if h.dtype == torch.float32 else _WidenRowsFn.apply(h)
+
+
+class _TowerSwitches:
+    @property
+    def cls_only_last_layer(self) -> bool:
+        """CM3PEncoder.cls_only_last_layer of this tower's encoder."""
+        return self.encoder.cls_only_last_layer
+
+    @cls_only_last_layer.setter
+    def cls_only_last_layer(self, value: bool):
+        self.encoder.cls_only_last_layer = bool(value)
+
+
 def _require_gpu(t: Tensor, what: str):
     if not t.is_cuda:
         raise RuntimeError(f"cm3p_amd: {what} must be on the GPU; this build has no CPU path (use the reference package on CPU)")
 
 
 # ----------------------------------------------------------------------------------------------- towers
-class CM3PMetadataTransformer(nn.Module):
+class CM3PMetadataTransformer(_TowerSwitches, nn.Module):
     """ref:cm3p/modeling_cm3p.py:300-403."""
 
     def __init__(self, config: CM3PMetadataConfig):
@@ -462,6 +513,7 @@ class CM3PMetadataTransformer(nn.Module):
         fp32 (one row per sequence of `cu_seqlens`), while `last_hidden_state` stays (total_nnz, H)."""
         if input_ids is None:
             raise ValueError("You have to specify input_ids")
+        cls_only = _cls_only_call(self, output_attentions, output_pooler)
         if indices is not None or cu_seqlens is not None:
             # caller-supplied unpadded rows (ref:cm3p/modeling_cm3p.py:359-372): the encoder runs packed; the reference has no pooling
             # for them in this tower (ref:cm3p/modeling_cm3p.py:383-384)
@@ -476,7 +528,10 @@ class CM3PMetadataTransformer(nn.Module):
             hiddens = None
             if output_hidden_states:
                 h, hiddens = h
-            pooled = _pool_packed(h, cu_seqlens, max_seqlen, bool(self.config.cls_embed)) if output_pooler else None
+            if cls_only:
+                pooled = _pool_cls_rows(h) if output_pooler else None
+            else:
+                pooled = _pool_packed(h, cu_seqlens, max_seqlen, bool(self.config.cls_embed)) if output_pooler else None
             return BaseModelOutputWithPooling(last_hidden_state=h, pooler_output=pooled, hidden_states=hiddens, attentions=None)
         _require_gpu(input_ids, "input_ids")
         is_3d = input_ids.dim() == 3
@@ -498,7 +553,10 @@ class CM3PMetadataTransformer(nn.Module):
             h, hiddens, attns = h
         elif output_hidden_states:
             h, hiddens = h
-        pooled = _PoolFn.apply(h, am2, bool(self.config.cls_embed)) if output_pooler else None
+        if cls_only:
+            pooled = _pool_cls_rows(h) if output_pooler else None
+        else:
+            pooled = _PoolFn.apply(h, am2, bool(self.config.cls_embed)) if output_pooler else None
         if is_3d:
             h = h.view(B0, -1, h.size(-2), h.size(-1))
             if pooled is not None:
@@ -547,7 +605,7 @@ class CM3PAudioEncoder(nn.Module):
         return CM3PAudioModelOutput(audio_embeds=audio_embeds, last_hidden_state=h, hidden_states=None, attentions=attns)
 
 
-class CM3PBeatmapTransformer(nn.Module):
+class CM3PBeatmapTransformer(_TowerSwitches, nn.Module):
     """ref:cm3p/modeling_cm3p.py:531-650."""
 
     def __init__(self, config: CM3PBeatmapConfig):
@@ -571,6 +629,7 @@ class CM3PBeatmapTransformer(nn.Module):
         audio_out = None
         ohs = bool(output_hidden_states)
         oat = bool(output_attentions)
+        cls_only = _cls_only_call(self, oat, output_pooler)  # (before the audio encoder runs)
         if oat and (indices is not None or cu_seqlens is not None):
             raise NotImplementedError("output_attentions with unpadded inputs: attention probabilities are (B, nh, S, S) tensors of a padded batch")
         if indices is not None or cu_seqlens is not None:
@@ -599,7 +658,9 @@ class CM3PBeatmapTransformer(nn.Module):
             if ohs:
                 h, hiddens = h
             pooled = None
-            if output_pooler and not self.config.cls_embed:
+            if output_pooler and cls_only:
+                pooled = _pool_cls_rows(h)
+            elif output_pooler and not self.config.cls_embed:
                 pooled = _pool_packed(h, cu_seqlens, max_seqlen, False)
             elif output_pooler:
                 first = cu_seqlens[:-1].to(device=h.device, dtype=torch.int64).contiguous()
@@ -636,7 +697,10 @@ class CM3PBeatmapTransformer(nn.Module):
             h, hiddens, attns = h
         elif ohs:
             h, hiddens = h
-        pooled = _PoolFn.apply(h, attention_mask, bool(self.config.cls_embed)) if output_pooler else None
+        if cls_only:
+            pooled = _pool_cls_rows(h) if output_pooler else None
+        else:
+            pooled = _PoolFn.apply(h, attention_mask, bool(self.config.cls_embed)) if output_pooler else None
         return CM3PBeatmapModelOutput(last_hidden_state=h, pooler_output=pooled, hidden_states=hiddens, attentions=attns,
                                       audio_model_output=audio_out)
 
@@ -805,6 +869,14 @@ class CM3PModel(CM3PPreTrainedModel):
             raise ValueError("When providing multiple metadata variations, metadata_variation_classes must be provided in order to compute loss correctly.")
         if output_logits and not self.config.has_decoder_head:
             raise ValueError("Cannot return logits when the model is not configured with a decoder head.")
+        # cls_only_last_layer: every consumer of all rows is refused before either tower launches anything
+        if output_logits and self.beatmap_model.cls_only_last_layer:
+            raise ValueError("cls_only_last_layer with the MLM head (has_decoder_head / output_logits): the head reads every row of the beatmap "
+                             "tower's last layer; switch cls_only_last_layer off on the beatmap tower")
+        if input_ids is not None:
+            _cls_only_call(self.beatmap_model, output_attentions, True)
+        if metadata_ids is not None:
+            _cls_only_call(self.metadata_model, output_attentions, True)
 
         beatmap_embeds = beatmap_outputs = metadata_embeds = metadata_outputs = beatmap_pending = None
         logits_per_beatmap = logits_per_metadata = None
@@ -1062,6 +1134,8 @@ class CM3PForMaskedLM(CM3PPreTrainedModel):
                 max_seqlen=None, batch_size=None, seq_len=None, output_attentions=None, output_hidden_states=None, **kwargs):
         from transformers.modeling_outputs import MaskedLMOutput
 
+        if self.beatmap_model.cls_only_last_layer:
+            raise ValueError("CM3PForMaskedLM with cls_only_last_layer: the MLM head reads every row of the last layer; switch it off")
         out = self.beatmap_model(input_ids=input_ids, input_features=input_features, attention_mask=attention_mask,
                                  position_ids=position_ids, inputs_embeds=inputs_embeds, indices=indices, cu_seqlens=cu_seqlens,
                                  output_attentions=output_attentions, output_hidden_states=output_hidden_states, output_pooler=False)
