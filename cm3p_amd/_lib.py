@@ -139,6 +139,14 @@ ROW_SIGNATURES = {
 }
 ATTN_ROW_ABI_VERSION = 1
 
+# name -> argtypes of include/cm3p_attn_qrows.h (attention for a list of query rows), one to one; again a table and a version of its own.
+QROWS_SIGNATURES = {
+    "cm3p_attn_qrows_abi_version": [],
+    "cm3p_attn_qrows_fwd": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _L, _I, _I, _F, _I, _P],
+    "cm3p_attn_qrows_bwd": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _L, _I, _I, _F, _P, _P, _L, _I, _P],
+}
+ATTN_QROWS_ABI_VERSION = 1
+
 _lib = None
 
 
@@ -157,7 +165,7 @@ def load() -> ctypes.CDLL:
             "cm3p_amd has no CPU or PyTorch fallback."
         )
     lib = ctypes.CDLL(LIB_PATH)
-    for name, argtypes in (*SIGNATURES.items(), *EXT_SIGNATURES.items(), *ROW_SIGNATURES.items()):
+    for name, argtypes in (*SIGNATURES.items(), *EXT_SIGNATURES.items(), *ROW_SIGNATURES.items(), *QROWS_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if a declared symbol is not exported
         fn.argtypes = argtypes
         fn.restype = c_int64 if name in _RETURNS_INT64 else c_int
@@ -167,6 +175,8 @@ def load() -> ctypes.CDLL:
         raise Cm3pHipError(f"cm3p_lora.h ABI mismatch: library {lib.cm3p_lora_abi_version()} vs binding {LORA_ABI_VERSION}; rebuild")
     if lib.cm3p_attn_row_abi_version() != ATTN_ROW_ABI_VERSION:
         raise Cm3pHipError(f"cm3p_attn_row.h ABI mismatch: library {lib.cm3p_attn_row_abi_version()} vs binding {ATTN_ROW_ABI_VERSION}; rebuild")
+    if lib.cm3p_attn_qrows_abi_version() != ATTN_QROWS_ABI_VERSION:
+        raise Cm3pHipError(f"cm3p_attn_qrows.h ABI mismatch: library {lib.cm3p_attn_qrows_abi_version()} vs binding {ATTN_QROWS_ABI_VERSION}; rebuild")
     if lib.cm3p_build_ablation_flags() != 0 and os.environ.get("CM3P_ALLOW_ABLATED_LIB") != "1":
         raise Cm3pHipError(
             f"{LIB_PATH} was built with timing-only ablation macros (mask {lib.cm3p_build_ablation_flags():#x}): its results are wrong by "

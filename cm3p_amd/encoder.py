@@ -548,6 +548,39 @@ class _TakeRowsFn(torch.autograd.Function):
         return K.scatter_rows(dy.contiguous(), ctx.idx, ctx.rows), None
 
 
+def _row_block_forward(geo: "_Geometry", o_p: Tensor, x_rows: Tensor, Wo_b: Tensor, w_mn: Tensor, Wi_b: Tensor, Wo2_b: Tensor):
+    """The part of a layer behind attention on a block of rows (_ClsLastLayerFn, _RowsLastLayerFn): o_p the attention output and x_rows
+    the residual rows of the block, both filled up with zero rows -> x_out = x_mid + GeGLU(mlp_norm(x_mid) Wi^T) Wo2^T with
+    x_mid = x_rows + o_p Wo^T, and what the backward reads."""
+    x_mid = K.linear_fwd(o_p, Wo_b, resid=x_rows)
+    _, xn2, mean_m, rstd_m = K.layernorm_fwd(x_mid, w_mn, geo.eps, False, True, geo.save)
+    h = K.linear_fwd(xn2, Wi_b)
+    g = K.geglu_fwd(h)
+    x_out = K.linear_fwd(g, Wo2_b, resid=x_mid)
+    return x_out, (x_mid, xn2, mean_m, rstd_m, h, g)
+
+
+def _row_block_backward(gx32: Tensor, gx16: Tensor, acts, w_mn: Tensor, wb, wt, need):
+    """Backward of _row_block_forward: the block's output gradient (fp32 and its bf16 twin, not yet filled up) -> the gradient of
+    x_rows (fp32, filled up), do = the gradient of o_p, and the weight gradients dWo, dw_mn, dWi, dWo2 (None where not needed)."""
+    o_p, x_mid, xn2, mean_m, rstd_m, h, g = acts
+    (Wo_b, Wi_b, Wo2_b), (Wo_t, Wi_t, Wo2_t), (n_o, n_i, n_o2) = wb, wt, need
+    Bp = x_mid.shape[0]
+    gx32, gx16 = _zero_padded_rows(gx32, Bp), _zero_padded_rows(gx16, Bp)
+    dg = K.linear_dgrad(gx16, Wo2_b, Wo2_t)
+    dWo2 = K.linear_wgrad(gx16, g) if n_o2 else None
+    dh = K.geglu_bwd(dg, h)
+    del dg, g, h
+    dxn2 = K.linear_dgrad(dh, Wi_b, Wi_t)
+    dWi = K.linear_wgrad(dh, xn2) if n_i else None
+    del dh, xn2
+    gx32, gx16, dw_mn = K.layernorm_bwd(dxn2, x_mid, w_mn, mean_m, rstd_m, gx32, True)
+    del dxn2, x_mid
+    do = K.linear_dgrad(gx16, Wo_b, Wo_t)
+    dWo = K.linear_wgrad(gx16, o_p) if n_o else None
+    return gx32, do, dWo, dw_mn, dWi, dWo2
+
+
 class _ClsLastLayerFn(torch.autograd.Function):
     """The LAST encoder layer where only row 0 of every sequence is consumed (CM3PEncoder.cls_only_last_layer): x [T, H] + the layer's
     weights -> the layer's output on the query rows alone, [Bn, H] (fp32; bf16 on the bf16 residual stream of a forward-only call).
@@ -580,11 +613,7 @@ class _ClsLastLayerFn(torch.autograd.Function):
         o, lse = K.attn_row_fwd(qkv, geo.key_mask, geo.cu, B, geo.max_s if geo.cu is not None else S, nh, geo.windows[i], scale, prescaled=True)
         Bp = (B + 7) // 8 * 8
         o_p = _zero_padded_rows(o, Bp)
-        x_mid = K.linear_fwd(o_p, Wo_b, resid=_zero_padded_rows(K.gather_rows(x, qidx), Bp))
-        _, xn2, mean_m, rstd_m = K.layernorm_fwd(x_mid, w_mn, geo.eps, False, True, geo.save)
-        h = K.linear_fwd(xn2, Wi_b)
-        g = K.geglu_fwd(h)
-        x_out = K.linear_fwd(g, Wo2_b, resid=x_mid)
+        x_out, (x_mid, xn2, mean_m, rstd_m, h, g) = _row_block_forward(geo, o_p, _zero_padded_rows(K.gather_rows(x, qidx), Bp), Wo_b, w_mn, Wi_b, Wo2_b)
         if geo.save:
             ctx.saved = (x, xn, mean_a, rstd_a, qkv, o, o_p, lse, x_mid, xn2, mean_m, rstd_m, h, g)
             ctx.geo, ctx.i, ctx.qidx = geo, i, qidx
@@ -605,30 +634,107 @@ class _ClsLastLayerFn(torch.autograd.Function):
         x, xn, mean_a, rstd_a, qkv, o, o_p, lse, x_mid, xn2, mean_m, rstd_m, h, g = ctx.saved
         (w_an, w_mn), (Wqkv_b, Wo_b, Wi_b, Wo2_b), (Wqkv_t, Wo_t, Wi_t, Wo2_t) = ctx.wn, ctx.wb, ctx.wt
         ctx.saved = ctx.wb = ctx.wt = None
-        Bp = x_mid.shape[0]
-        gx32, gx16 = _zero_padded_rows(gx32, Bp), _zero_padded_rows(gx16, Bp)
         # ---- the row block: x_out = x_mid + g Wo2^T, x_mid = x[qidx] + o Wo^T
-        dg = K.linear_dgrad(gx16, Wo2_b, Wo2_t)
-        dWo2 = K.linear_wgrad(gx16, g) if n_o2 else None
-        dh = K.geglu_bwd(dg, h)
-        del dg, g, h
-        dxn2 = K.linear_dgrad(dh, Wi_b, Wi_t)
-        dWi = K.linear_wgrad(dh, xn2) if n_i else None
-        del dh, xn2
-        gx32, gx16, dw_mn = K.layernorm_bwd(dxn2, x_mid, w_mn, mean_m, rstd_m, gx32, True)
-        del dxn2, x_mid
-        do = K.linear_dgrad(gx16, Wo_b, Wo_t)
-        dWo = K.linear_wgrad(gx16, o_p) if n_o else None
+        gx32, do, dWo, dw_mn, dWi, dWo2 = _row_block_backward(gx32, gx16, (o_p, x_mid, xn2, mean_m, rstd_m, h, g), w_mn, (Wo_b, Wi_b, Wo2_b),
+                                                              (Wo_t, Wi_t, Wo2_t), (n_o, n_i, n_o2))
+        del o_p, x_mid, xn2, h, g
         # ---- all rows: dqkv in the full layout (q third zero off the query rows), then what every layer does with it
         dqkv = K.attn_row_bwd(qkv, o, do[:B].contiguous(), lse, geo.key_mask, geo.cu, B, geo.max_s if geo.cu is not None else S, nh, geo.windows[i], scale,
                               geo.rope[i], geo.per_batch_pos, prescaled=True)
-        del do, o, o_p, qkv
+        del do, o, qkv
         dWqkv = K.linear_wgrad(dqkv, xn) if n_qkv else None
         dw_an = None
         gfull = None
         if need[2] or n_an:
             # the residual stream's own gradient: zero except on the query rows
             gfull = K.scatter_rows(gx32[:B].contiguous(), qidx, x.shape[0])
+            dxn = K.linear_dgrad(dqkv, Wqkv_b, Wqkv_t)
+            if i == 0:
+                gfull, _ = K.add_f32(gfull, dxn, want_bf16=False)
+                _hand_upstream(geo, gfull, None)
+            else:
+                gfull, g16, dw_an = K.layernorm_bwd(dxn, x, w_an, mean_a, rstd_a, gfull, True)
+                _hand_upstream(geo, gfull, g16)
+        grads = [dWqkv, dWo, dw_mn, dWi, dWo2] if i == 0 else [dw_an, dWqkv, dWo, dw_mn, dWi, dWo2]
+        out = [(gw if gw.dtype == dt else gw.to(dt)) if (nd and gw is not None) else None for gw, dt, nd in zip(grads, ctx.wdtypes, need[4:])]
+        return (None, None, gfull if need[2] else None, None, *out)
+
+
+class _RowSel:
+    """A validated list of last-layer rows (CM3PEncoder.forward's last_layer_rows): idx int64 [n] - the rows in the numbering of the
+    stack's row axis (the packed rows on unpadded execution) -, rows the same as int32, qcu int32 [sequences + 1] their split by
+    sequence, qmax the largest per-sequence count."""
+
+    __slots__ = ("idx", "rows", "qcu", "qmax", "n")
+
+    def __init__(self, idx: Tensor, qcu: Tensor, qmax: int):
+        self.idx, self.rows, self.qcu, self.qmax, self.n = idx, idx.to(torch.int32), qcu, int(qmax), idx.numel()
+
+
+class _RowsLastLayerFn(torch.autograd.Function):
+    """The LAST encoder layer where only a list of rows is consumed (CM3PEncoder.forward's last_layer_rows: the CLS rows and the rows
+    that carry a masked-LM label): x [T, H] + the layer's weights -> the layer's output on the listed rows alone, [n, H].
+
+    _ClsLastLayerFn's chain with a list in place of row 0: attn_norm and the Wqkv + RoPE projection on all T rows, attention for the
+    listed queries against all keys on the matrix cores (K.attn_qrows_fwd), then the row block (_row_block_forward) on n rows, filled
+    up with zero rows to K.row_block_rows.  The backward mirrors _ClsLastLayerFn.backward with K.attn_qrows_bwd (dqkv in the full
+    layout, its q third zero off the list, dk / dv summed over the listed queries).  The same limits: _run_stack sends every other call
+    through the full layer."""
+
+    @staticmethod
+    def forward(ctx, geo: _Geometry, i: int, x: Tensor, sel: _RowSel, *weights: Tensor):
+        it = iter(weights)
+        w_an = None if i == 0 else _f32(next(it))
+        Wqkv, Wo, w_mn, Wi, Wo2 = next(it), next(it), _f32(next(it)), next(it), next(it)
+        pre = geo.wcast if geo.wcast is not None else {}
+        pairs = [pre.get(id(w)) or _bf16_weight_pair(w, geo.save) for w in (Wqkv, Wo, Wi, Wo2)]
+        Wqkv_b, Wo_b, Wi_b, Wo2_b = (p[0] for p in pairs)
+        B, S, nh = geo.B, geo.S, geo.nh
+        scale = geo.hd ** -0.5
+        cos, sin = geo.rope[i]
+        if i == 0:
+            xn, mean_a, rstd_a = (x if x.dtype == torch.bfloat16 else K.cast_bf16(x)), None, None
+        else:
+            _, xn, mean_a, rstd_a = K.layernorm_fwd(x, w_an, geo.eps, False, True, geo.save)
+        qkv = K.qkv_linear_rope(xn, Wqkv_b, cos, sin, S, geo.per_batch_pos, q_scale=K.SOFTMAX_Q_SCALE)
+        o, lse = K.attn_qrows_fwd(qkv, sel.rows, sel.qcu, sel.qmax, geo.key_mask, geo.cu, B, geo.max_s if geo.cu is not None else S, nh, geo.windows[i],
+                                  scale, prescaled=True)
+        n = sel.n
+        Np = K.row_block_rows(n, geo.H, geo.I)
+        o_p = _zero_padded_rows(o, Np)
+        x_out, (x_mid, xn2, mean_m, rstd_m, h, g) = _row_block_forward(geo, o_p, _zero_padded_rows(K.gather_rows(x, sel.idx), Np), Wo_b, w_mn, Wi_b, Wo2_b)
+        if geo.save:
+            ctx.saved = (x, xn, mean_a, rstd_a, qkv, o, o_p, lse, x_mid, xn2, mean_m, rstd_m, h, g)
+            ctx.geo, ctx.i, ctx.sel = geo, i, sel
+            ctx.wn, ctx.wb, ctx.wt = (w_an, w_mn), (Wqkv_b, Wo_b, Wi_b, Wo2_b), tuple(p[1] for p in pairs)
+            ctx.wdtypes = [w.dtype for w in weights]
+        return x_out[:n] if Np != n else x_out
+
+    @staticmethod
+    def backward(ctx, dy: Tensor):
+        geo, i, sel = ctx.geo, ctx.i, ctx.sel
+        need = ctx.needs_input_grad  # (geo, i, x, sel, *weights)
+        need_w = list(need[4:])
+        if i == 0:
+            need_w.insert(0, False)  # (no attn_norm in layer 0)
+        n_an, n_qkv, n_o, n_mn, n_i, n_o2 = need_w
+        B, S, nh, scale, n = geo.B, geo.S, geo.nh, geo.hd ** -0.5, sel.n
+        gx32, gx16 = _take_from_downstream(geo, dy)
+        x, xn, mean_a, rstd_a, qkv, o, o_p, lse, x_mid, xn2, mean_m, rstd_m, h, g = ctx.saved
+        (w_an, w_mn), (Wqkv_b, Wo_b, Wi_b, Wo2_b), (Wqkv_t, Wo_t, Wi_t, Wo2_t) = ctx.wn, ctx.wb, ctx.wt
+        ctx.saved = ctx.wb = ctx.wt = None
+        gx32, do, dWo, dw_mn, dWi, dWo2 = _row_block_backward(gx32, gx16, (o_p, x_mid, xn2, mean_m, rstd_m, h, g), w_mn, (Wo_b, Wi_b, Wo2_b),
+                                                              (Wo_t, Wi_t, Wo2_t), (n_o, n_i, n_o2))
+        del o_p, x_mid, xn2, h, g
+        # ---- all rows: dqkv in the full layout (q third zero off the list), then what every layer does with it
+        dqkv = K.attn_qrows_bwd(qkv, o, do[:n].contiguous(), lse, sel.rows, sel.qcu, sel.qmax, geo.key_mask, geo.cu, B, geo.max_s if geo.cu is not None else S,
+                                nh, geo.windows[i], scale, geo.rope[i], geo.per_batch_pos, prescaled=True)
+        del do, o, qkv
+        dWqkv = K.linear_wgrad(dqkv, xn) if n_qkv else None
+        dw_an = None
+        gfull = None
+        if need[2] or n_an:
+            gfull = K.scatter_rows(gx32[:n].contiguous(), sel.idx, x.shape[0])  # the residual stream's own gradient: zero off the list
             dxn = K.linear_dgrad(dqkv, Wqkv_b, Wqkv_t)
             if i == 0:
                 gfull, _ = K.add_f32(gfull, dxn, want_bf16=False)
@@ -896,7 +1002,7 @@ class CM3PEncoder(nn.Module):
                 position_ids: Optional[Tensor] = None, inputs_embeds: Optional[Tensor] = None,
                 audio_slot: Optional[Tensor] = None, audio_rows: Optional[Tensor] = None, unpad: bool = False,
                 output_hidden_states: bool = False, cu_seqlens: Optional[Tensor] = None, max_seqlen: Optional[int] = None,
-                output_attentions: bool = False):
+                output_attentions: bool = False, last_layer_rows: Optional[Tensor] = None):
         """-> last_hidden_state (B, S, H) fp32 (bf16 on the bf16 residual stream, see residual_dtype) [, tuple of L+1 detached hidden states (the stack's input and every layer's output,
         TF:...modeling_modernbert.py:457-470) when output_hidden_states].  Exactly one of input_ids / inputs_embeds.
         output_attentions: -> (last_hidden_state, hidden states or None, tuple of L attention-probability tensors (B, nh, S, S) fp32,
@@ -904,7 +1010,18 @@ class CM3PEncoder(nn.Module):
 
         unpad: run the stack on the valid tokens only, packed back to back (what the reference's flash_attention_2 path does,
         ref:cm3p/modeling_cm3p.py:911-931); padding positions of the result are zero.  Used when the mask is a right-padded
-        one with at least one padded position; otherwise the padded path runs (same values on the valid positions)."""
+        one with at least one padded position; otherwise the padded path runs (same values on the valid positions).
+
+        last_layer_rows: an int64 device tensor [n] of strictly ascending GLOBAL row numbers (b * S + position of a (B, S) batch, with
+        or without `unpad`; the packed row with `cu_seqlens`) for callers that consume only those rows of the result - the CLS rows and
+        the rows that carry a masked-LM label.  The last layer and the final norm are computed for them alone and the output is
+        (n, H), in list order; with `output_hidden_states` the last entry is that short tensor.  The same function of the same
+        weights as those rows of the full result: attn_norm and the Wqkv + RoPE projection still run on every token, attention
+        runs for the listed queries against all keys (csrc/attention_qrows.hip), Wo, mlp_norm, the GeGLU MLP and the final norm on n
+        rows (_RowsLastLayerFn).  ONE host read validates the list (ascending, in range, with `unpad` every row on a valid token)
+        and gives the grid its size; a wrong list raises ValueError.  Where the row route has no form - the cases cls_only_last_layer
+        names - the full layer runs and the rows are gathered: the output shape does not depend on the route.  Wins over
+        cls_only_last_layer when both are given.  `output_attentions` with it raises NotImplementedError."""
         cfg = self.config
         if (input_ids is None) == (inputs_embeds is None):
             raise ValueError("You must specify exactly one of input_ids or inputs_embeds")
@@ -915,7 +1032,10 @@ class CM3PEncoder(nn.Module):
             if output_attentions:
                 raise NotImplementedError("output_attentions needs head_dim 64")
             unpad = False
-        cls_only = self._cls_only_last_layer
+        cls_only = self._cls_only_last_layer and last_layer_rows is None  # (the explicit argument wins)
+        if last_layer_rows is not None and output_attentions:
+            raise NotImplementedError("output_attentions with last_layer_rows: the last layer computes the listed queries only, there is no "
+                                      "(B, nh, S, S) probability tensor for it")
         if cls_only and output_attentions:
             raise NotImplementedError("output_attentions with cls_only_last_layer: the last layer computes one query per sequence, there is no "
                                       "(B, nh, S, S) probability tensor for it; switch cls_only_last_layer off for such a call")
@@ -927,7 +1047,7 @@ class CM3PEncoder(nn.Module):
             if output_attentions:
                 raise NotImplementedError("output_attentions with unpadded inputs: attention probabilities are (B, nh, S, S) tensors of a padded batch")
             return self._forward_prepacked(input_ids, position_ids, audio_slot, audio_rows, cu_seqlens, max_seqlen, output_hidden_states, plan, bf16,
-                                           cls_only)
+                                           cls_only, last_layer_rows)
         if output_attentions:
             unpad = False  # the probabilities are laid out per padded (batch, head, query, key)
         if input_ids is not None and input_ids.dtype != torch.int64:
@@ -943,6 +1063,9 @@ class CM3PEncoder(nn.Module):
         if unpad and attention_mask is not None and input_ids is not None:
             packed = self._plan_unpadded(attention_mask.reshape(B, S), position_ids)
 
+        sel = None
+        if last_layer_rows is not None:  # (before any launch of the stack: a wrong list has computed nothing)
+            sel = self._plan_last_layer_rows(last_layer_rows, B, S, B * S, packed[1] if packed is not None else None, repack=packed is not None)
         if packed is not None:
             idx, cu, max_s, n_valid, n_rows, pos = packed
             ids = input_ids.contiguous().view(-1)[idx]  # integer row selection (the reference's _unpad_cm3p_input)
@@ -965,15 +1088,15 @@ class CM3PEncoder(nn.Module):
 
         x0 = self._embed_dropout(x0, plan, S, packed[1] if packed is not None else None)
         y, hiddens, attns = self._run_stack(x0, B, S, attention_mask, position_ids, packed, output_hidden_states, dev, output_attentions, plan, bf16,
-                                            cls_only)
-        short = [hiddens.pop()] if (cls_only and hiddens is not None) else []  # (the last layer's output: one row per sequence already)
+                                            cls_only, sel)
+        short = [hiddens.pop()] if ((cls_only or sel is not None) and hiddens is not None) else []  # (the last layer's output: short already)
         if hiddens is not None:
             if packed is not None:
                 hiddens = [K.scatter_rows(h[:n_valid].contiguous(), idx, B * S) for h in hiddens]
-            hiddens = tuple(h.view(B, S, H) for h in hiddens) + tuple(h.view(B, 1, H) for h in short)
+            hiddens = tuple(h.view(B, S, H) for h in hiddens) + tuple(h if sel is not None else h.view(B, 1, H) for h in short)
         if cls_only:
             y = y.view(B, 1, H)
-        else:
+        elif sel is None:  # (with last_layer_rows y is (n, H), in list order, as it is)
             if packed is not None:
                 y = _PadRowsFn.apply(y, idx, n_valid, B * S)
             y = y.view(B, S, H)
@@ -982,10 +1105,12 @@ class CM3PEncoder(nn.Module):
         return (y, hiddens) if output_hidden_states else y
 
     def _run_stack(self, x0: Tensor, B: int, S: int, attention_mask, position_ids, packed, output_hidden_states: bool, dev,
-                   output_attentions: bool = False, plan: Optional[_DropPlan] = None, bf16: bool = False, cls_only: bool = False):
+                   output_attentions: bool = False, plan: Optional[_DropPlan] = None, bf16: bool = False, cls_only: bool = False,
+                   sel: Optional[_RowSel] = None):
         """The L encoder layers + final norm on [rows, H]; `packed` = (idx, cu, max_s, n_valid, n_rows, pos) for unpadded execution;
         `plan`: the call's dropout (None: none); `bf16`: x0 is bf16 and the stream stays bf16 (_bf16_stream); `cls_only`: y and the last
-        hidden state are the rows of query position 0 alone, [sequences, H] (cls_only_last_layer)."""
+        hidden state are the rows of query position 0 alone, [sequences, H] (cls_only_last_layer); `sel`: they are the listed rows alone, [n, H]
+        (last_layer_rows; never together with cls_only)."""
         cfg = self.config
         H = cfg.hidden_size
         geo = _Geometry()
@@ -1030,8 +1155,10 @@ class CM3PEncoder(nn.Module):
             raise RuntimeError("cm3p_amd: bf16 residual stream on a call that records a backward without train_residual_dtype, or with dropout")
         geo.bf16 = bf16
         # cls_only_last_layer: the row route where it has a form, else the full layer and a row selection behind the final norm
-        row_route = cls_only and geo.hd == 64 and plan is None and not geo.checkpoint and not (bf16 and geo.save) \
+        has_route = geo.hd == 64 and plan is None and not geo.checkpoint and not (bf16 and geo.save) \
             and (lora is None or all(a is None for a in lora[geo.L - 1]))
+        row_route = cls_only and has_route
+        rows_route = sel is not None and sel.n > 0 and has_route  # (an empty list: the full layer and an empty gather)
         if geo.save and _eval_weights:
             invalidate_weight_cache()  # a backward will follow, so an optimizer will: no copy made before this step may outlive it
         geo.wcast = None
@@ -1076,7 +1203,7 @@ class CM3PEncoder(nn.Module):
                     cast = {id(w) for w in elig}
                     # (not the last layer on the row route: its Wi is a plain GEMM on B rows and reads the canonical copy)
                     geo.fused_mlp = frozenset(id(ws[-2]) for n, ws in enumerate(weights)
-                                              if id(ws[-2]) in cast and id(ws[-1]) in cast and not (row_route and n == geo.L - 1))
+                                              if id(ws[-2]) in cast and id(ws[-1]) in cast and not ((row_route or rows_route) and n == geo.L - 1))
                 plain = [w for w in elig if id(w) not in adapted]
                 pairs = K.cast_bf16_with_transpose_many([w.detach() for w in plain], [id(w) in geo.fused_mlp for w in plain])
                 geo.wcast = {id(w): pair for w, pair in zip(plain, pairs)}
@@ -1096,14 +1223,20 @@ class CM3PEncoder(nn.Module):
             extra = () if lora is None else tuple(t for a in lora[i] if a is not None for t in a[:2])
             if row_route and i == geo.L - 1:
                 x = _ClsLastLayerFn.apply(geo, i, x, qidx, *weights[i])  # [geo.B, H]
+            elif rows_route and i == geo.L - 1:
+                x = _RowsLastLayerFn.apply(geo, i, x, sel, *weights[i])  # [n, H]
             else:
                 x = _EncoderLayerFn.apply(geo, i, x, *weights[i], *extra)
             if hiddens is not None:
                 if cls_only and i == geo.L - 1:
                     hiddens.append((x.detach() if row_route else K.gather_rows(x.detach(), qidx))[:n_seq])
+                elif sel is not None and i == geo.L - 1:
+                    hiddens.append(x.detach() if rows_route else K.gather_rows(x.detach(), sel.idx))
                 else:
                     hiddens.append(x.detach())
         y = _FinalNormFn.apply(geo, x, self.final_norm.weight)
+        if sel is not None and not rows_route:
+            y = _TakeRowsFn.apply(y, sel.idx)
         if cls_only:
             if not row_route:
                 y = _TakeRowsFn.apply(y, qidx)
@@ -1115,7 +1248,7 @@ class CM3PEncoder(nn.Module):
 
     def _forward_prepacked(self, input_ids: Tensor, position_ids: Optional[Tensor], audio_slot, audio_rows, cu_seqlens: Tensor,
                            max_seqlen: Optional[int], output_hidden_states: bool, plan: Optional[_DropPlan] = None, bf16: bool = False,
-                           cls_only: bool = False):
+                           cls_only: bool = False, last_layer_rows: Optional[Tensor] = None):
         """Caller-supplied unpadded inputs (ref:cm3p/modeling_cm3p.py:911-931 when `indices` / `cu_seqlens` / `max_seqlen` are given;
         the layout of _unpad_cm3p_input, :65-104): input_ids (total,), cu_seqlens (batch + 1,) -> last_hidden_state (total, H),
         NOT re-padded (the reference's encoder leaves caller-packed rows packed as well)."""
@@ -1138,6 +1271,9 @@ class CM3PEncoder(nn.Module):
         max_s = int(mx) if max_seqlen is None else int(max_seqlen)
         if max_s < mx:
             raise ValueError(f"max_seqlen {max_s} is smaller than the longest sequence ({mx})")
+        sel = None
+        if last_layer_rows is not None:  # (rows of the packed axis; the pseudo-sequence of alignment rows added below owns none)
+            sel = self._plan_last_layer_rows(last_layer_rows, cu.numel() - 1, max_s, total, cu, repack=False, n_seq=cu.numel() - 1 + (total % 64 != 0))
         n_rows = (total + 63) // 64 * 64  # alignment rows: one pseudo-sequence of pad tokens, no gradient flows into it
         if position_ids is None:
             pos = torch.arange(total, device=dev) - torch.repeat_interleave(cu[:-1].to(torch.int64), lens.to(torch.int64))
@@ -1158,13 +1294,52 @@ class CM3PEncoder(nn.Module):
         packed = (None, cu, max(max_s, n_rows - total), total, n_rows, pos.contiguous())
         x0 = self._embed_dropout(x0, plan, max_s, cu)
         y, hiddens, _ = self._run_stack(x0, cu.numel() - 1, max_s, None, None, packed, output_hidden_states, dev, plan=plan, bf16=bf16,
-                                        cls_only=cls_only)
+                                        cls_only=cls_only, sel=sel)
         if n_rows != total:
-            if not cls_only:
+            short = cls_only or sel is not None
+            if not short:
                 y = y[:total]
             if hiddens is not None:
-                hiddens = [h[:total] for h in hiddens[:-1]] + [hiddens[-1]] if cls_only else [h[:total] for h in hiddens]
+                hiddens = [h[:total] for h in hiddens[:-1]] + [hiddens[-1]] if short else [h[:total] for h in hiddens]
         return (y, tuple(hiddens)) if output_hidden_states else y
+
+    @staticmethod
+    def _plan_last_layer_rows(rows: Tensor, B: int, S: int, total: int, cu: Optional[Tensor], repack: bool, n_seq: Optional[int] = None) -> _RowSel:
+        """Validates `last_layer_rows` and splits it by sequence, on the device plus ONE host read (validity and the largest per-sequence
+        count).  rows number the (B, S) batch (cu None, or `repack`: the stack then runs on the packed rows of `cu` and the list is
+        renumbered; every row must sit on a valid token) or the caller's packed axis of `total` rows (cu given, not repack).
+        n_seq: the sequences the stack will see (with the pseudo-sequence of alignment rows), default cu's or B."""
+        if not isinstance(rows, Tensor) or rows.dtype != torch.int64 or rows.dim() != 1 or not rows.is_cuda:
+            raise ValueError("last_layer_rows must be a 1-D int64 CUDA/HIP tensor of ascending global row numbers")
+        if n_seq is None:
+            n_seq = B if cu is None else cu.numel() - 1
+        n = rows.numel()
+        if n == 0:
+            return _RowSel(rows.contiguous(), torch.zeros(n_seq + 1, dtype=torch.int32, device=rows.device), 0)
+        rows = rows.contiguous()
+        limit = B * S if (cu is None or repack) else total
+        ok = (rows[0] >= 0) & (rows[-1] < limit)
+        if n > 1:
+            ok = ok & (rows[1:] > rows[:-1]).all()
+        rc = rows.clamp(0, limit - 1)  # (a wrong list is refused below, before anything reads through it)
+        if cu is None or repack:
+            seq = rc // S
+            idx = rc
+            if repack:
+                pos = rc - seq * S
+                cu64 = cu.to(torch.int64)
+                ok = ok & (pos < (cu64[1:] - cu64[:-1])[seq]).all()
+                idx = cu64[seq] + pos
+        else:
+            seq = torch.searchsorted(cu[1:].to(torch.int64).contiguous(), rc, right=True).clamp(max=B - 1)
+            idx = rc
+        counts = torch.bincount(seq, minlength=n_seq)
+        good, qmax = torch.stack((ok.to(torch.int64), counts.max())).tolist()
+        if not good:
+            raise ValueError(f"last_layer_rows must be strictly ascending row numbers in [0, {limit})" + (" on valid (unmasked) tokens" if repack else ""))
+        qcu = torch.zeros(n_seq + 1, dtype=torch.int32, device=rows.device)
+        qcu[1:] = torch.cumsum(counts, 0)
+        return _RowSel(idx.contiguous(), qcu, qmax)
 
     @staticmethod
     def _plan_unpadded(mask: Tensor, position_ids: Optional[Tensor]):

@@ -225,8 +225,9 @@ class FusedModernBertModel(ModernBertPreTrainedModel):
 
     def forward(self, input_ids: Optional[Tensor] = None, attention_mask: Optional[Tensor] = None, position_ids: Optional[Tensor] = None,
                 inputs_embeds: Optional[Tensor] = None, output_attentions: Optional[bool] = None, output_hidden_states: Optional[bool] = None,
-                return_dict: Optional[bool] = None, **kwargs) -> BaseModelOutput:
-        """-> BaseModelOutput(last_hidden_state (B, S, H), hidden_states: L + 1 tensors when asked for - the stack's input, the output of
+                return_dict: Optional[bool] = None, last_layer_rows: Optional[Tensor] = None, **kwargs) -> BaseModelOutput:
+        """last_layer_rows: CM3PEncoder.forward's argument, passed through - last_hidden_state (and the last hidden state) are then (n, H).
+        -> BaseModelOutput(last_hidden_state (B, S, H), hidden_states: L + 1 tensors when asked for - the stack's input, the output of
         layers 0 .. L-2 (detached) and, as the installed ModernBertModel reports it, last_hidden_state itself in the last place -,
         attentions: the L eager-semantics probability tensors (B, nh, S, S) fp32 when asked for).  CPU inputs raise."""
         cfg = self.config
@@ -244,7 +245,7 @@ class FusedModernBertModel(ModernBertPreTrainedModel):
             enc.residual_dtype = torch.bfloat16 if pdtype == torch.bfloat16 else None
         out = enc(input_ids=input_ids, attention_mask=attention_mask, position_ids=position_ids, inputs_embeds=inputs_embeds,
                   unpad=bool(self.unpad_inputs) and not output_attentions, output_hidden_states=output_hidden_states,
-                  output_attentions=output_attentions)
+                  output_attentions=output_attentions, last_layer_rows=last_layer_rows)
         hiddens = attns = None
         if output_attentions:
             y, hiddens, attns = out
@@ -290,6 +291,9 @@ class FusedModernBertForMaskedLM(ModernBertPreTrainedModel):
         self.head.dense._cm3p_init = self.decoder._cm3p_init = (config.initializer_range / (2.0 * config.num_hidden_layers) ** 0.5, cutoff)
         self.sparse_prediction = bool(config.sparse_prediction)
         self.sparse_pred_ignore_index = int(config.sparse_pred_ignore_index)
+        # opt-in (not in config or state dict): with sparse_prediction, in training mode with labels, the tower's last layer runs on the
+        # labelled rows only (CM3PEncoder.forward's last_layer_rows) instead of on all rows followed by the row selection
+        self.labelled_rows_last_layer = False
         self.post_init()
 
     def get_output_embeddings(self):
@@ -317,18 +321,26 @@ class FusedModernBertForMaskedLM(ModernBertPreTrainedModel):
 
         if self.model.cls_only_last_layer:
             raise ValueError("FusedModernBertForMaskedLM with cls_only_last_layer: the MLM head reads every row of the last layer; switch it off")
-        out = self.model(input_ids=input_ids, attention_mask=attention_mask, position_ids=position_ids, inputs_embeds=inputs_embeds,
-                         output_attentions=output_attentions, output_hidden_states=output_hidden_states, return_dict=True)
-        hs = out.last_hidden_state
-        Bq, Sq, Hq = hs.shape
-        V = self.config.vocab_size
-        rows = hs.reshape(Bq * Sq, Hq)
         sparse = self.sparse_prediction and labels is not None
+        idx = None
         if sparse:  # keep the labelled tokens only (row selection by index; the count needs one host read, as in the HF model)
             labels = labels.reshape(-1)
             idx = torch.nonzero(labels != self.sparse_pred_ignore_index).flatten()
-            rows = _TakeRowsFn.apply(rows, idx)
             labels = labels[idx]
+        oat = bool(self.config.output_attentions if output_attentions is None else output_attentions)
+        on_rows = sparse and self.labelled_rows_last_layer and self.training and not oat
+        out = self.model(input_ids=input_ids, attention_mask=attention_mask, position_ids=position_ids, inputs_embeds=inputs_embeds,
+                         output_attentions=output_attentions, output_hidden_states=output_hidden_states, return_dict=True,
+                         last_layer_rows=idx if on_rows else None)
+        hs = out.last_hidden_state
+        V = self.config.vocab_size
+        if on_rows:
+            rows = hs  # (n, H): the labelled rows already
+        else:
+            Bq, Sq, Hq = hs.shape
+            rows = hs.reshape(Bq * Sq, Hq)
+            if sparse:
+                rows = _TakeRowsFn.apply(rows, idx)
         head_args = (rows, self.head.dense.weight, self.head.dense.bias, self.head.norm.weight, self.decoder.weight, self.decoder.bias,
                      self.config.norm_eps)
         loss = None

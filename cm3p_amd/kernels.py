@@ -237,6 +237,22 @@ def linear_wgrad(dy: Tensor, x: Tensor) -> Tensor:
     return gemm(dy, x, N, K, T, False, False, EPI_F32, split_k=_wgrad_splits(N, K, T))
 
 
+def row_block_rows(n: int, H: int, I: int) -> int:
+    """How many rows a block of n token rows is filled up to (with zero rows) for the GEMMs of a layer's row block: a multiple of 8,
+    the GEMMs' constraint - or of 64 where the library's routing rule (cm3p_gemm_route) then gives the block's largest
+    token-contraction GEMM, the weight gradient dWi [2 I, H] = dh^T xn2, a 256 x 256 kernel that it does not get otherwise (those
+    kernels take the contraction in 64-deep tiles)."""
+    n8, n64 = (n + 7) // 8 * 8, (n + 63) // 64 * 64
+    if n8 == n64:
+        return n8
+
+    def kernel(T):
+        code = query("cm3p_gemm_route", 2 * I, H, T, 2 * I, H, 0, 0, EPI_F32, _wgrad_splits(2 * I, H, T), 0, 0)
+        return code & 3 if code >= 0 else 0
+
+    return n64 if kernel(n64) > kernel(n8) else n8
+
+
 def cast_bf16(x: Tensor) -> Tensor:
     y = torch.empty(x.shape, dtype=torch.bfloat16, device=x.device)
     call("cm3p_cast_f32_bf16", ptr(x, torch.float32), ptr(y), x.numel(), stream())
@@ -618,6 +634,41 @@ def attn_row_bwd(qkv: Tensor, out: Tensor, dout: Tensor, lse: Tensor, key_mask: 
     call("cm3p_attn_row_bwd", ptr(qkv, torch.bfloat16), ptr(out, torch.bfloat16), ptr(dout, torch.bfloat16), ptr(lse, torch.float32), ptr(dqkv),
          ptr(key_mask, torch.uint8), ptr(cu, torch.int32), B, S, total, nh, window, scale, ptr(cos, torch.float32), ptr(sin, torch.float32),
          S if (per_batch and cu is None) else 0, int(prescaled), stream(), tag="attn_row_bwd_kernel", work=5.0 * rows * nh * 128)
+    return dqkv
+
+
+# ---- attention for a list of query rows (include/cm3p_attn_qrows.h, csrc/attention_qrows.hip) ------------------------------------------
+def attn_qrows_fwd(qkv: Tensor, qrows: Tensor, qcu: Tensor, qmax: int, key_mask: Optional[Tensor], cu: Optional[Tensor], B: int, S: int, nh: int,
+                   window: int, scale: float, prescaled: bool = False):
+    """Attention of the listed query rows against all keys.  qkv [B * S, 3 * nh * 64] (or the packed rows [total, ...] with their int32
+    cu_seqlens, S = max_seqlen, no key mask); qrows int32 [n] ascending global rows, qcu int32 [B + 1] their split by sequence, qmax the
+    largest per-sequence count -> out [n, nh * 64] bf16, lse [nh, n] fp32, compact in list order."""
+    n = qrows.numel()
+    out = torch.empty((n, nh * 64), dtype=torch.bfloat16, device=qkv.device)
+    lse = torch.empty((nh, n), dtype=torch.float32, device=qkv.device)
+    if n == 0:
+        return out, lse
+    keys = S if window < 0 else min(S, 2 * window + 1)
+    call("cm3p_attn_qrows_fwd", ptr(qkv, torch.bfloat16), ptr(out), ptr(lse, torch.float32), ptr(key_mask, torch.uint8), ptr(cu, torch.int32),
+         ptr(qrows, torch.int32), ptr(qcu, torch.int32), n, qmax, B, S, qkv.shape[0], nh, window, scale, int(prescaled), stream(),
+         tag="attn_qrows_fwd_kernel", work=2.0 * 2.0 * n * nh * keys * 64)
+    return out, lse
+
+
+def attn_qrows_bwd(qkv: Tensor, out: Tensor, dout: Tensor, lse: Tensor, qrows: Tensor, qcu: Tensor, qmax: int, key_mask: Optional[Tensor],
+                   cu: Optional[Tensor], B: int, S: int, nh: int, window: int, scale: float, rope: Optional[tuple] = None, per_batch: bool = False,
+                   prescaled: bool = False) -> Tensor:
+    """-> dqkv in qkv's full layout, every element written: the q third is zero off the listed rows, dk / dv sum over the listed queries.
+    rope = (cos, sin): also applies the inverse rotary rotation to dq / dk (per-token tables in the packed form)."""
+    n = qrows.numel()
+    dqkv = torch.empty_like(qkv)
+    cos, sin = rope if rope is not None else (None, None)
+    keys = S if window < 0 else min(S, 2 * window + 1)
+    live = n > 0
+    call("cm3p_attn_qrows_bwd", ptr(qkv, torch.bfloat16), ptr(out, torch.bfloat16) if live else None, ptr(dout, torch.bfloat16) if live else None,
+         ptr(lse, torch.float32) if live else None, ptr(dqkv), ptr(key_mask, torch.uint8), ptr(cu, torch.int32), ptr(qrows, torch.int32) if live else None,
+         ptr(qcu, torch.int32), n, qmax, B, S, qkv.shape[0], nh, window, scale, ptr(cos, torch.float32), ptr(sin, torch.float32),
+         S if (per_batch and cu is None) else 0, int(prescaled), stream(), tag="attn_qrows_bwd_kernel", work=2.0 * 8.0 * n * nh * keys * 64)
     return dqkv
 
 

@@ -42,6 +42,7 @@ class CM3PAudioModelOutput(BaseModelOutput):
 class CM3PBeatmapModelOutput(BaseModelOutputWithPooling):
     beatmap_embeds: Optional[torch.FloatTensor] = None
     audio_model_output: Optional[CM3PAudioModelOutput] = None
+    selected_rows: Optional[Tensor] = None  # the rows last_hidden_state holds when the tower ran with last_layer_rows (else None)
 
 
 @dataclass
@@ -625,11 +626,22 @@ class CM3PBeatmapTransformer(_TowerSwitches, nn.Module):
     def forward(self, input_ids: Optional[Tensor] = None, input_features: Optional[Tensor] = None,
                 attention_mask: Optional[Tensor] = None, sliding_window_mask=None, position_ids: Optional[Tensor] = None,
                 inputs_embeds: Optional[Tensor] = None, indices=None, cu_seqlens=None, max_seqlen=None, batch_size=None,
-                seq_len=None, output_attentions=None, output_hidden_states=None, output_pooler: bool = True) -> CM3PBeatmapModelOutput:
+                seq_len=None, output_attentions=None, output_hidden_states=None, output_pooler: bool = True,
+                last_layer_rows: Optional[Tensor] = None) -> CM3PBeatmapModelOutput:
+        """last_layer_rows (CM3PEncoder.forward): the last layer, the final norm and last_hidden_state - then (n, H) - on the listed
+        rows only, returned as `selected_rows`; padded (B, S) batches, with or without unpad_inputs.  With output_pooler the tower must
+        pool the CLS row (`cls_embed`) and the list must hold row b * S of every sequence b: pooling takes those entries."""
         audio_out = None
         ohs = bool(output_hidden_states)
         oat = bool(output_attentions)
-        cls_only = _cls_only_call(self, oat, output_pooler)  # (before the audio encoder runs)
+        if last_layer_rows is not None:  # (before the audio encoder runs)
+            if oat:
+                raise NotImplementedError("output_attentions with last_layer_rows: the last layer computes the listed queries only")
+            if indices is not None or cu_seqlens is not None:
+                raise NotImplementedError("last_layer_rows with caller-packed rows is not supported on the tower; call the encoder")
+            if output_pooler and not self.config.cls_embed:
+                raise ValueError("last_layer_rows with mean pooling (cls_embed = False): the pooled output reads every row of the last layer")
+        cls_only = last_layer_rows is None and _cls_only_call(self, oat, output_pooler)  # (before the audio encoder runs)
         if oat and (indices is not None or cu_seqlens is not None):
             raise NotImplementedError("output_attentions with unpadded inputs: attention probabilities are (B, nh, S, S) tensors of a padded batch")
         if indices is not None or cu_seqlens is not None:
@@ -674,7 +686,7 @@ class CM3PBeatmapTransformer(_TowerSwitches, nn.Module):
                 raise NotImplementedError("input_features together with inputs_embeds is not supported")
             _require_gpu(inputs_embeds, "inputs_embeds")
             h = self.encoder(inputs_embeds=inputs_embeds, attention_mask=attention_mask, position_ids=position_ids,
-                             output_hidden_states=ohs, output_attentions=oat)
+                             output_hidden_states=ohs, output_attentions=oat, last_layer_rows=last_layer_rows)
         else:
             _require_gpu(input_ids, "input_ids")
             slot = rows = None
@@ -691,18 +703,27 @@ class CM3PBeatmapTransformer(_TowerSwitches, nn.Module):
             unpad = self.unpad_inputs if self.unpad_inputs is not None else \
                 getattr(self.config, "_attn_implementation", None) == "flash_attention_2"
             h = self.encoder(input_ids=input_ids, attention_mask=attention_mask, position_ids=position_ids, audio_slot=slot,
-                             audio_rows=rows, unpad=bool(unpad), output_hidden_states=ohs, output_attentions=oat)
+                             audio_rows=rows, unpad=bool(unpad), output_hidden_states=ohs, output_attentions=oat,
+                             last_layer_rows=last_layer_rows)
         hiddens = attns = None
         if oat:
             h, hiddens, attns = h
         elif ohs:
             h, hiddens = h
-        if cls_only:
+        if last_layer_rows is not None:
+            pooled = None
+            if output_pooler:  # the list's entries b * S (ascending list: a search, no host read)
+                ref = input_ids if input_ids is not None else inputs_embeds
+                first = torch.arange(ref.shape[0], device=h.device, dtype=torch.int64) * ref.shape[1]
+                pooled = _TakeRowsFn.apply(h, torch.searchsorted(last_layer_rows, first).clamp(max=h.shape[0] - 1))
+                if pooled.dtype != torch.float32:
+                    pooled = _WidenRowsFn.apply(pooled)
+        elif cls_only:
             pooled = _pool_cls_rows(h) if output_pooler else None
         else:
             pooled = _PoolFn.apply(h, attention_mask, bool(self.config.cls_embed)) if output_pooler else None
         return CM3PBeatmapModelOutput(last_hidden_state=h, pooler_output=pooled, hidden_states=hiddens, attentions=attns,
-                                      audio_model_output=audio_out)
+                                      audio_model_output=audio_out, selected_rows=last_layer_rows)
 
 
 class CM3PPredictionHead(nn.Module):
@@ -804,7 +825,27 @@ class CM3PModel(CM3PPreTrainedModel):
         # metadata always, (B, V, L) metadata variations in training mode (eval scores them rank-locally; cm3p_amd/dist.py).
         self.gather_negatives = False
         self.unpad_inputs = None  # True / False overrides the reference's rule (unpad iff attn_implementation is flash_attention_2)
+        self._labelled_rows_last_layer = False
         self.post_init()
+
+    @property
+    def labelled_rows_last_layer(self) -> bool:
+        """Opt-in for training steps of the recipe with CLS pooling and the decoder head: the beatmap tower's last layer, its final
+        norm and the MLM head run on the rows that are consumed - row 0 of every sequence (pooling) and every position with a label
+        (the loss) - instead of all B x S rows (CM3PEncoder.forward's last_layer_rows).  Takes effect only on calls in training mode
+        with `labels`, `return_loss` and the logits of a model with `has_decoder_head` on a padded (B, S) batch (with or without
+        unpad_inputs) of a `cls_embed` beatmap tower; every other call - evaluation, no labels, caller-packed rows - runs as without it.
+        On such a call `logits` is (n, vocab) and `beatmap_model_output.last_hidden_state` (n, H) in the order of
+        `beatmap_model_output.selected_rows`; loss, embeddings and every gradient are those of the full call.  Setting it on a model
+        whose beatmap tower pools the mean raises ValueError.  Not part of the state dict or config; off by default."""
+        return self._labelled_rows_last_layer
+
+    @labelled_rows_last_layer.setter
+    def labelled_rows_last_layer(self, value: bool):
+        if value and not self.config.beatmap_config.cls_embed:
+            raise ValueError("labelled_rows_last_layer with mean pooling (beatmap_config.cls_embed = False): the pooled output reads every row "
+                             "of the last layer")
+        self._labelled_rows_last_layer = bool(value)
 
     @property
     def pool_unpadded(self) -> bool:
@@ -905,9 +946,18 @@ class CM3PModel(CM3PPreTrainedModel):
             with torch.cuda.stream(side):
                 metadata_outputs, metadata_embeds = run_metadata()
 
+        # labelled_rows_last_layer: the rows this training step consumes - every sequence's row 0 and the labelled positions
+        sel_rows = sel_labels = None
+        if (self._labelled_rows_last_layer and self.training and labels is not None and return_loss and output_logits and self.config.has_decoder_head
+                and self.config.beatmap_config.cls_embed and input_ids is not None and input_ids.dim() == 2 and indices is None and cu_seqlens is None
+                and labels.numel() == input_ids.numel()):
+            want = labels.reshape(input_ids.shape) != -100
+            want[:, 0] = True
+            sel_rows = torch.nonzero(want.flatten()).flatten()  # ascending, deduplicated by construction
+            sel_labels = labels.reshape(-1)[sel_rows]           # (an unlabelled CLS row keeps its -100)
         if input_ids is not None:
             try:
-                beatmap_outputs = self.beatmap_model(input_ids=input_ids, input_features=input_features, attention_mask=attention_mask,
+                beatmap_outputs = self.beatmap_model(input_ids=input_ids, last_layer_rows=sel_rows, input_features=input_features, attention_mask=attention_mask,
                                                      position_ids=position_ids, inputs_embeds=inputs_embeds, indices=indices,
                                                      cu_seqlens=cu_seqlens, max_seqlen=max_seqlen, batch_size=batch_size, seq_len=seq_len,
                                                      output_attentions=output_attentions, output_hidden_states=output_hidden_states)
@@ -977,6 +1027,15 @@ class CM3PModel(CM3PPreTrainedModel):
                 raise ValueError("output_logits needs input_ids")
             hs = beatmap_outputs.last_hidden_state
             V = self.config.beatmap_config.vocab_size
+            n_sel = None
+            if sel_rows is not None:  # the head on the row block: zero rows (label -100) fill it up as in the last layer
+                n_sel = hs.shape[0]
+                bc = self.config.beatmap_config
+                n_pad = K.row_block_rows(n_sel, bc.hidden_size, bc.intermediate_size)
+                if n_pad != n_sel:
+                    hs = _ZeroPadRowsFn.apply(hs, n_pad)
+                    sel_labels = torch.cat((sel_labels, sel_labels.new_full((n_pad - n_sel,), -100)))
+                labels = sel_labels
             head_args = (hs.reshape(-1, hs.size(-1)), self.head.dense.weight, self.head.dense.bias, self.head.norm.weight,
                          self.decoder.weight, self.decoder.bias, self.config.beatmap_config.norm_eps)
             mlm = None
@@ -989,7 +1048,7 @@ class CM3PModel(CM3PPreTrainedModel):
             else:
                 # caller-supplied unpadded rows: logits (total_nnz, V), re-padded like the reference's flash_attention_2 branch
                 # (_pad_cm3p_output, ref:cm3p/modeling_cm3p.py:999-1001) when the padded geometry was given
-                logits = lp[:, :V]
+                logits = lp[:, :V] if n_sel is None else lp[:n_sel, :V]  # (labelled_rows_last_layer: the selected rows, in their order)
                 if indices is not None and batch_size is not None and seq_len is not None:
                     idx64 = indices.to(device=lp.device, dtype=torch.int64).reshape(-1).contiguous()
                     rows = int(batch_size) * int(seq_len)
@@ -1090,6 +1149,21 @@ class _TakeRowsFn(torch.autograd.Function):
         return K.scatter_rows(dy.contiguous(), ctx.idx, ctx.rows), None
 
 
+class _ZeroPadRowsFn(torch.autograd.Function):
+    """x [n, H] -> [rows, H] with zero rows behind (a copy); backward: the first n rows of the gradient."""
+
+    @staticmethod
+    def forward(ctx, x: Tensor, rows: int):
+        ctx.n = x.shape[0]
+        out = x.new_zeros((rows, x.shape[1]))
+        out[:ctx.n].copy_(x)
+        return out
+
+    @staticmethod
+    def backward(ctx, dy: Tensor):
+        return dy[:ctx.n].contiguous(), None
+
+
 class _WidenRowsFn(torch.autograd.Function):
     """bf16 rows -> the same values as fp32 (exact; dtype plumbing of the pooled CLS rows of caller-packed inputs); backward: the
     fp32 gradient rounded once to bf16 by cm3p_cast_f32_bf16, the dtype the bf16 residual stream takes its gradient in."""
@@ -1117,6 +1191,9 @@ class CM3PForMaskedLM(CM3PPreTrainedModel):
         self.decoder = nn.Linear(config.hidden_size, config.vocab_size, bias=config.decoder_bias)
         self.sparse_prediction = bool(getattr(config, "sparse_prediction", False))
         self.sparse_pred_ignore_index = int(getattr(config, "sparse_pred_ignore_index", -100))
+        # opt-in (not in config or state dict): with sparse_prediction, in training mode with labels, the tower's last layer runs on the
+        # labelled rows only (CM3PEncoder.forward's last_layer_rows) instead of on all rows followed by the row selection
+        self.labelled_rows_last_layer = False
         self.post_init()
 
     def get_output_embeddings(self):
@@ -1136,19 +1213,26 @@ class CM3PForMaskedLM(CM3PPreTrainedModel):
 
         if self.beatmap_model.cls_only_last_layer:
             raise ValueError("CM3PForMaskedLM with cls_only_last_layer: the MLM head reads every row of the last layer; switch it off")
-        out = self.beatmap_model(input_ids=input_ids, input_features=input_features, attention_mask=attention_mask,
-                                 position_ids=position_ids, inputs_embeds=inputs_embeds, indices=indices, cu_seqlens=cu_seqlens,
-                                 output_attentions=output_attentions, output_hidden_states=output_hidden_states, output_pooler=False)
-        hs = out.last_hidden_state
-        Bq, Sq, Hq = hs.shape
-        V = self.config.vocab_size
-        rows = hs.reshape(Bq * Sq, Hq)
         sparse = self.sparse_prediction and labels is not None
+        idx = None
         if sparse:  # keep the labelled tokens only (row selection by index; the count needs one host read, as in the reference)
             labels = labels.reshape(-1)
             idx = torch.nonzero(labels != self.sparse_pred_ignore_index).flatten()
-            rows = _TakeRowsFn.apply(rows, idx)
             labels = labels[idx]
+        on_rows = sparse and self.labelled_rows_last_layer and self.training and indices is None and cu_seqlens is None and not output_attentions
+        out = self.beatmap_model(input_ids=input_ids, input_features=input_features, attention_mask=attention_mask,
+                                 position_ids=position_ids, inputs_embeds=inputs_embeds, indices=indices, cu_seqlens=cu_seqlens,
+                                 output_attentions=output_attentions, output_hidden_states=output_hidden_states, output_pooler=False,
+                                 last_layer_rows=idx if on_rows else None)
+        hs = out.last_hidden_state
+        V = self.config.vocab_size
+        if on_rows:
+            rows = hs  # (n, H): the labelled rows already
+        else:
+            Bq, Sq, Hq = hs.shape
+            rows = hs.reshape(Bq * Sq, Hq)
+            if sparse:
+                rows = _TakeRowsFn.apply(rows, idx)
         head_args = (rows, self.head.dense.weight, self.head.dense.bias, self.head.norm.weight, self.decoder.weight, self.decoder.bias,
                      self.config.norm_eps)
         loss = None
