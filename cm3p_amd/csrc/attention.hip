@@ -795,6 +795,7 @@ static bool fwd_takes_pipelined(int S, int nh, int window, int pre) {
 template <typename... Drop>
 static int launch_attn_fwd(const void* qkv, void* out, float* lse, const uint8_t* key_mask, int B, int S, int nh, int window,
                            float scale, VarLen vl, int pre, hipStream_t s, Drop... drop) {
+    window = window < 0 ? -1 : (window < S ? window : S);  // (a wider band is the whole axis; keeps row + window inside int)
     if constexpr (sizeof...(Drop) == 0) {
         if (fwd_takes_pipelined(S, nh, window, pre))
             return cm3p_launch_attn_fwd_global(qkv, out, lse, key_mask, B, S, nh, vl.cu, vl.total, s);
@@ -819,6 +820,7 @@ template <typename... Drop>
 static int launch_attn_bwd(const void* qkv, const void* out, const void* dout, const float* lse, float* delta, void* dqkv,
                            const uint8_t* key_mask, int B, int S, int nh, int window, float scale, const float* cos_tab,
                            const float* sin_tab, int64_t pos_batch_stride, VarLen vl, int stages, int pre, hipStream_t s, Drop... drop) {
+    window = window < 0 ? -1 : (window < S ? window : S);  // (a wider band is the whole axis; keeps row + window inside int)
     const dim3 grid(((S + 127) / 128) * nh * B);  // 1-D: decode_block() maps it XCD-aware
     if (stages & CM3P_ATTN_BWD_DQ) {
 #define CM3P_DQ_ARGS (const uint16_t*)qkv, (const uint16_t*)dout, (const uint16_t*)out, lse, delta, (uint16_t*)dqkv, key_mask, S, nh, window, scale, cos_tab, sin_tab, pos_batch_stride, vl, drop...

@@ -296,6 +296,7 @@ static bool gen_bwd_args_ok(const void* qkv, const void* out, const void* dout, 
 template <typename... Drop>
 static int launch_gen_fwd(const void* qkv, void* out, float* lse, const uint8_t* key_mask, int B, int S, int nh, int head_dim, int window, float scale,
                           hipStream_t s, Drop... drop) {
+    window = window < 0 ? -1 : (window < S ? window : S);  // (a wider band is the whole axis; keeps row + window inside int)
     if (cm3p_attn_hd_supported(head_dim)) {
         if constexpr (sizeof...(Drop) == 0) return cm3p_attn_hd_fwd((const uint16_t*)qkv, (uint16_t*)out, lse, key_mask, B, S, nh, head_dim, window, scale, s);
         else return CM3P_ERR_INVALID;
@@ -314,6 +315,7 @@ static int launch_gen_fwd(const void* qkv, void* out, float* lse, const uint8_t*
 template <typename... Drop>
 static int launch_gen_bwd(const void* qkv, const void* out, const void* dout, const float* lse, float* delta, void* dqkv, const uint8_t* key_mask, int B,
                           int S, int nh, int head_dim, int window, float scale, hipStream_t s, Drop... drop) {
+    window = window < 0 ? -1 : (window < S ? window : S);  // (a wider band is the whole axis; keeps row + window inside int)
     if (cm3p_attn_hd_supported(head_dim)) {
         if constexpr (sizeof...(Drop) == 0)
             return cm3p_attn_hd_bwd((const uint16_t*)qkv, (const uint16_t*)out, (const uint16_t*)dout, lse, delta, (uint16_t*)dqkv, key_mask, B, S, nh,

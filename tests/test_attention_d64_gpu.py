@@ -218,6 +218,18 @@ def test_band_equals_global_when_the_window_covers_everything():
             assert bool(((gg[nm].double() - gb[nm].double()).abs() <= 2.0 * ref["bound"][nm]).all()), nm
 
 
+def test_the_largest_window_is_the_window_s_in_bits():
+    """window = 2^31 - 1: the launchers clamp a window to S before the band kernels do arithmetic with it (qrow + window, Q1 + window
+    and q0 + QW - 1 + window would leave int), so the call is the window = S call bit for bit, forward and backward."""
+    for pre in (False, True):
+        case = AR.BY_NAME[f"A-S300-w300-pad-{'pre' if pre else 'plain'}"]
+        out, lse, dqkv, delta, guards = _direct(case, window=2 ** 31 - 1)
+        out_s, lse_s, dqkv_s, delta_s, _ = _direct(case, window=case.S)
+        assert torch.equal(out, out_s) and torch.equal(lse, lse_s) and torch.equal(dqkv, dqkv_s) and torch.equal(delta, delta_s)
+        assert all(guards.values())
+        assert not AR.check_float64(_reference(case), _split(case, out, lse, dqkv))[1]
+
+
 @pytest.mark.parametrize("window", [1, 33, 96, 200])
 def test_varlen_equals_padded(window):
     """cm3p_attn_fwd_varlen / cm3p_attn_bwd_varlen on the packed sequences give the bits of the padded call on every valid row (masked keys

@@ -1,13 +1,15 @@
-"""Which test checks each C-ABI entry point against a reference.  Every function include/cm3p_hip.h declares is either in LEDGER,
-with the test functions that compare its results with a reference restatement (node ids without parameters), or in EXEMPT with the
-reason it has none (host-side size queries, ablation and audit hooks).  A new entry point cannot land without one or the other.
+"""Which test checks each C-ABI entry point against a reference.  Every function the public headers (include/cm3p_hip.h, cm3p_lora.h,
+cm3p_attn_row.h, cm3p_attn_qrows.h) declare is either in LEDGER, with the test functions that compare its results with a reference
+restatement (node ids without parameters), or in EXEMPT with the reason it has none (host-side size and version queries, ablation and
+audit hooks).  A new entry point cannot land without one or the other; every header under include/ is read, so neither can a new header.
 No GPU needed: the tests named here are found by parsing their files."""
 import ast
+import glob
 import os
 import re
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "cm3p_hip.h")
+HEADERS = sorted(glob.glob(os.path.join(ROOT, "include", "*.h")))  # every public header, also one a later change adds
 
 KG = "tests/test_kernels_gpu.py::"
 CH = "tests/test_conv_head_kernels_gpu.py::"
@@ -19,6 +21,10 @@ GK = "tests/test_gemm_kernels_gpu.py::"
 AD = "tests/test_attention_d64_gpu.py::"
 MK = "tests/test_muon_kernels_gpu.py::"
 LH = "tests/test_loss_head_gpu.py::"
+AG = "tests/test_attn_generic_gpu.py::"
+LK = "tests/test_lora_kernels_gpu.py::"
+AW = "tests/test_attn_row_kernels_gpu.py::"
+AQ = "tests/test_attn_qrows_kernels_gpu.py::"
 
 LEDGER = {
     "cm3p_layernorm_fwd": [KG + "test_layernorm_fwd_bwd", CH + "test_layernorm_with_many_rows_per_wave",
@@ -55,15 +61,25 @@ LEDGER = {
     "cm3p_rope_apply": [KG + "test_rope_matches_reference_formula",
                         RK + "test_rope_apply_against_the_float64_rotation"],
     "cm3p_attn_fwd": [KG + "test_attention_global_nopad", KG + "test_attention_random_shapes", KG + "test_attention_sliding_window",
-                      AD + "test_matches_float64", AD + "test_exact_conditions", AD + "test_count_probe", AD + "test_window0_copies_v_and_dout"],
+                      AD + "test_matches_float64", AD + "test_exact_conditions", AD + "test_count_probe", AD + "test_window0_copies_v_and_dout",
+                      AD + "test_the_largest_window_is_the_window_s_in_bits"],
     "cm3p_attn_probs": [MG + "test_output_attentions_matches_the_reference_eager_probabilities",
                         AD + "test_probs"],
     "cm3p_attn_bwd": [KG + "test_attention_global_backward_both_implementations", KG + "test_attention_random_shapes",
-                      AD + "test_matches_float64", AD + "test_exact_conditions", AD + "test_count_probe", AD + "test_band_equals_global_when_the_window_covers_everything"],
-    "cm3p_attn_fwd_generic": [KG + "test_generic_attention_matches_fp32_reference"],
-    "cm3p_attn_bwd_generic": [KG + "test_generic_attention_matches_fp32_reference"],
-    "cm3p_attn_fwd_generic_dropout": [DR + "test_generic_attention_dropout_matches_fp32_restatement"],
-    "cm3p_attn_bwd_generic_dropout": [DR + "test_generic_attention_dropout_matches_fp32_restatement"],
+                      AD + "test_matches_float64", AD + "test_exact_conditions", AD + "test_count_probe", AD + "test_band_equals_global_when_the_window_covers_everything",
+                      AD + "test_the_largest_window_is_the_window_s_in_bits"],
+    "cm3p_attn_fwd_generic": [KG + "test_generic_attention_matches_fp32_reference",
+                              AG + "test_matches_float64", AG + "test_count_probe", AG + "test_window0_copies_v_and_dout",
+                              AG + "test_a_window_that_covers_the_axis_is_the_global_mask_in_bits",
+                              AG + "test_head_64_both_kernel_families_meet_their_own_float64_bounds"],
+    "cm3p_attn_bwd_generic": [KG + "test_generic_attention_matches_fp32_reference",
+                              AG + "test_matches_float64", AG + "test_count_probe", AG + "test_window0_copies_v_and_dout",
+                              AG + "test_a_window_that_covers_the_axis_is_the_global_mask_in_bits",
+                              AG + "test_head_64_both_kernel_families_meet_their_own_float64_bounds"],
+    "cm3p_attn_fwd_generic_dropout": [DR + "test_generic_attention_dropout_matches_fp32_restatement",
+                                      AG + "test_dropout", AG + "test_dropout_at_a_window_that_covers_the_axis"],
+    "cm3p_attn_bwd_generic_dropout": [DR + "test_generic_attention_dropout_matches_fp32_restatement",
+                                      AG + "test_dropout", AG + "test_dropout_at_a_window_that_covers_the_axis"],
     "cm3p_rope_apply_generic": [KG + "test_generic_rope_is_the_reference_rotation_and_its_transpose",
                                 RK + "test_rope_apply_against_the_float64_rotation"],
     "cm3p_attn_bwd_fused": [KG + "test_attention_global_backward_both_implementations",
@@ -136,6 +152,21 @@ LEDGER = {
     "cm3p_muon_apply": [MU + "test_steps_match_the_reference_fixture", MU + "test_model_sized_group_against_the_oracle",
                         MK + "test_stage_kernels_against_their_references", MK + "test_an_all_zero_matrix_stays_zero_and_leaves_its_group_alone", MK + "test_two_steps_of_the_class_at_the_block_seams_aligned_and_not"],
     "cm3p_adamw_multi": [MU + "test_steps_match_the_reference_fixture", MK + "test_adamw_multi_against_float64"],
+    # include/cm3p_lora.h
+    "cm3p_lora_merge_cast_multi": [LK + "test_merged_cast_against_float64", LK + "test_merged_cast_table_of_several_matrices",
+                                   LK + "test_merged_cast_with_zero_b_is_the_plain_cast_in_bits"],
+    "cm3p_lora_grad": [LK + "test_adapter_gradients_against_float64", LK + "test_adapter_gradients_over_three_row_blocks_and_pitched_rows",
+                       LK + "test_adapter_gradients_with_zero_scale_are_exact_zeros"],
+    # include/cm3p_attn_row.h
+    "cm3p_attn_row_fwd": [AW + "test_row_kernels_against_float64", AW + "test_row_kernels_exact_conditions",
+                          AW + "test_row_forward_agrees_with_row_0_of_the_full_forward"],
+    "cm3p_attn_row_bwd": [AW + "test_row_kernels_against_float64", AW + "test_row_kernels_exact_conditions",
+                          AW + "test_row_backward_agrees_with_the_full_backward_fed_a_one_row_dout"],
+    # include/cm3p_attn_qrows.h
+    "cm3p_attn_qrows_fwd": [AQ + "test_qrows_kernels_against_float64", AQ + "test_qrows_kernels_exact_conditions",
+                            AQ + "test_every_row_listed_agrees_with_the_full_kernels"],
+    "cm3p_attn_qrows_bwd": [AQ + "test_qrows_kernels_against_float64", AQ + "test_qrows_kernels_exact_conditions",
+                            AQ + "test_backward_agrees_with_the_full_backward_fed_a_dout_that_is_zero_off_the_list"],
 }
 
 EXEMPT = {
@@ -155,13 +186,24 @@ EXEMPT = {
     "cm3p_pool_chunks": "host query: workspace size of cm3p_pool_fwd",
     "cm3p_ce_masked_dlogits_blocks": "host query: partial rows of cm3p_ce_masked_dlogits_bf16",
     "cm3p_colsum_blocks": "host query: partial rows of cm3p_colsum_f32",
+    "cm3p_lora_abi_version": "host query: cm3p_lora.h's version number (tests/test_lora_host.py compares it with the binding)",
+    "cm3p_lora_grad_workspace_bytes": "host query: workspace size of cm3p_lora_grad (tests/test_lora_host.py restates its formula)",
+    "cm3p_lora_grad_row_block": "host query: row block of cm3p_lora_grad (tests/test_lora_host.py restates its rule)",
+    "cm3p_attn_row_abi_version": "host query: cm3p_attn_row.h's version number (tests/test_attn_row_refs_host.py compares it with the binding)",
+    "cm3p_attn_qrows_abi_version": "host query: cm3p_attn_qrows.h's version number (tests/test_attn_qrows_refs_host.py compares it with the binding)",
 }
 
 
 def _declared():
     """The same parse as tests/test_cabi.py::_declared."""
-    text = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    return set(re.findall(r"\b(?:int|int64_t)\s+(cm3p_[a-z0-9_]+)\s*\(", text))
+    declared = set()
+    assert {os.path.basename(h) for h in HEADERS} >= {"cm3p_hip.h", "cm3p_lora.h", "cm3p_attn_row.h", "cm3p_attn_qrows.h"}
+    for header in HEADERS:
+        text = re.sub(r"/\*.*?\*/", "", open(header).read(), flags=re.S)
+        found = set(re.findall(r"\b(?:int|int64_t)\s+(cm3p_[a-z0-9_]+)\s*\(", text))
+        assert found, f"no entry point parsed from {header}"
+        declared |= found
+    return declared
 
 
 def _test_functions(relpath):
@@ -173,7 +215,8 @@ def test_every_declared_entry_point_is_in_the_ledger_or_exempt():
     declared = _declared()
     covered = set(LEDGER) | set(EXEMPT)
     assert not declared - covered, f"entry points with neither a test nor an exemption: {sorted(declared - covered)}"
-    assert not covered - declared, f"ledger names no longer in the header: {sorted(covered - declared)}"
+    assert not covered - declared, f"ledger names no longer in a header: {sorted(covered - declared)}"
+    assert {"cm3p_attn_fwd", "cm3p_lora_grad", "cm3p_attn_row_fwd", "cm3p_attn_qrows_bwd"} <= declared  # one of each header
 
 
 def test_ledger_and_exempt_are_disjoint_and_nonempty():
