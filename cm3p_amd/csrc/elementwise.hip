@@ -328,6 +328,7 @@ __global__ __launch_bounds__(256) void dropout_f32_kernel(const float* x, const 
     const int h8 = H / 8;
     const int64_t n = rows * h8;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+#pragma clang fp contract(off)  // the contract is two roundings, fl(fl(x scale) + resid): never one fused multiply-add
         const int64_t t = i / h8;
         const uint32_t m = drop_keep8(d, t, (uint32_t)(i - t * h8));
         f32x4 v0 = reinterpret_cast<const f32x4*>(x)[2 * i], v1 = reinterpret_cast<const f32x4*>(x)[2 * i + 1];
@@ -738,7 +739,7 @@ int cm3p_geglu_bwd(const void* dg, const void* h, void* dh, int64_t T, int I, vo
 
 // row layout of the dropout entries: padded rows of S positions (cu_seqlens null) or n_seqs packed sequences
 #define CM3P_DROP_REQUIRE()                                                                                                          \
-    CM3P_REQUIRE(thr >= 0 && thr <= 65536 && layer >= 0 && site >= 0 && site <= 3 && layer < (1 << 29));                          \
+    CM3P_REQUIRE(site >= 0 && site <= 3 && cm3p_drop::cfg_args_ok(layer, thr));                                                    \
     CM3P_REQUIRE(cu_seqlens ? n_seqs > 0 : S > 0)
 
 int cm3p_dropout_f32(const float* x, const float* resid, float* y_f32, void* y_bf16, int64_t rows, int H, int S, const int* cu_seqlens, int n_seqs,
@@ -778,7 +779,8 @@ int cm3p_geglu_bwd_dropout(const void* dg, const void* h, void* dh, int64_t T, i
 }
 
 int cm3p_dropout_keep(uint8_t* keep, int n2, int n1, int n0, int layer, int site, int thr, uint64_t seed, void* stream) {
-    CM3P_REQUIRE(keep && n2 > 0 && n1 > 0 && n0 > 0 && thr >= 0 && thr <= 65536 && layer >= 0 && site >= 0 && site <= 3);
+    // (the layer bound of every dropout entry: past it counter word 3 would wrap and the mask would be another layer's)
+    CM3P_REQUIRE(keep && n2 > 0 && n1 > 0 && n0 > 0 && site >= 0 && site <= 3 && cm3p_drop::cfg_args_ok(layer, thr));
     const int64_t items = (int64_t)n2 * n1 * ((n0 + 7) / 8);
     dropout_keep_kernel<<<ew_grid(items), 256, 0, static_cast<hipStream_t>(stream)>>>(keep, n2, n1, n0, seed,
                                                                                        cm3p_drop::site_word(layer, (uint32_t)site), (uint32_t)thr);

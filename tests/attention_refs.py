@@ -1,7 +1,10 @@
 """Float64 reference, derived per-element bounds, case table, CPU emulation and index-arithmetic restatement of the head-64 attention
 kernels (csrc/attention.hip, attention_fwd.hip, attention_bwd_fused.hip), shared by tests/test_attention_d64_gpu.py (the kernels
 against them) and tests/test_attention_refs_host.py (the emulation must pass every check, wrong evaluations must fail them, the table
-must reach every branch of the band arithmetic).  No GPU and no cm3p_amd import here.
+must reach every branch of the band arithmetic).  The dropout forms (cm3p_attn_fwd_dropout / cm3p_attn_bwd_dropout and their packed
+relatives) run TABLE_DROP x DROPOUT_PS with the host's Philox mask (tests/dropout_refs.py::attention_keep) in
+tests/test_dropout_kernels_gpu.py; tests/test_dropout_refs_host.py holds the emulation and WRONG_DROP to them.  No GPU and no cm3p_amd
+import here.
 
 Tensors are [B, NH, S, 64] (lse: [B, NH, S]) on this side; the GPU test converts from the packed layouts.
 
@@ -95,13 +98,21 @@ TABLE_P = ([Case(t, 300, w, LENS_A if t == "A" else None, pre, True) for t in "A
            + [Case("A", 300, w, LENS_A, False, True) for w in WINDOWS_A if w not in PROBE_WINDOWS])
 TABLE = TABLE_A + TABLE_B + TABLE_C + TABLE_G
 BY_NAME = {c.name: c for c in TABLE + TABLE_P}
+# attention-probability dropout (cm3p_attn_fwd_dropout / cm3p_attn_bwd_dropout: the band kernels at every window, -1 included): table A
+# at the windows where a row sees one key (0), three (1), the tile seam (63, 64, 65) and everything (300), the holes of table C, the
+# global instances of table G and the no-mask instances of table B at one tile, five and eight (the ring wraps); both q modes
+WINDOWS_A_DROP = (0, 1, 63, 64, 65, 300)
+CASES_B_DROP = ((64, 31), (257, 127), (449, 449))
+TABLE_DROP = ([c for c in TABLE_A if c.window in WINDOWS_A_DROP] + TABLE_C + TABLE_G + [c for c in TABLE_B if (c.S, c.window) in CASES_B_DROP])
+DROPOUT_PS = (0.1, 0.5)
 
 
-def instances(case):
-    """The kernel instances of csrc/attention.hip a case's cm3p_attn_fwd + cm3p_attn_bwd calls run (launch_attn_fwd / launch_attn_bwd)."""
+def instances(case, drop=False):
+    """The kernel instances of csrc/attention.hip a case's cm3p_attn_fwd + cm3p_attn_bwd calls run (launch_attn_fwd / launch_attn_bwd).
+    drop: the _dropout entries, whose global pre-scaled forward is the band kernel too (the pipelined one has no dropout instance)."""
     masked = key_mask(case) is not None
     p = "true" if case.pre else "false"
-    fwd = "attn_fwd_g_kernel" if (case.window < 0 and case.pre) else f"attn_fwd_kernel<1, {p}, {'true' if case.window >= 0 else 'false'}>"
+    fwd = "attn_fwd_g_kernel" if (case.window < 0 and case.pre and not drop) else f"attn_fwd_kernel<1, {p}, {'true' if case.window >= 0 else 'false'}>"
     return {fwd, f"attn_bwd_dq_kernel<{p}, {'true' if masked else 'false'}>", f"attn_bwd_dkv_kernel<{p}>"}
 
 
@@ -216,10 +227,11 @@ def _backward_bounds(x, p, dS, ds_floor, derr):
     return bq, bk, fused
 
 
-def reference(case, keep=None, p_drop=0.0):
+def reference(case, keep=None, p_drop=0.0, x=None):
     """float64 autograd of softmax(scale q k^T + mask) v [with P o Z, Z = keep / (1 - p_drop)] and the componentwise bounds of the
-    module docstring.  Dead rows: exact zeros, lse = -inf (the kernels store +inf)."""
-    x = inputs(case)
+    module docstring.  Dead rows: exact zeros, lse = -inf (the kernels store +inf).  x: inputs(case) with another dO (the packed
+    entry points have no padded query rows: their dO is zero)."""
+    x = x or inputs(case)
     q, k, v = (x[n].clone().requires_grad_(True) for n in "qkv")
     xx = dict(x, q=q, k=k, v=v)
     vis, dead, s, p = softmax64(case, xx)
@@ -242,15 +254,16 @@ def reference(case, keep=None, p_drop=0.0):
         derr = (do.abs() * b_out).sum(-1, keepdim=True)
         b_dq, b_dk, fused = _backward_bounds(x, p, dS, ds_floor, derr)
     return dict(out=out, lse=lse, dq=q.grad, dk=k.grad, dv=v.grad, dead=dead.expand(-1, NH, -1).clone(), nvis=vis.sum(-1).expand(-1, NH, -1).clone(),
-                bound=dict(out=b_out, dq=b_dq, dk=b_dk, dv=b_dv), bound_fused_dq=b_dq + fused, e32=e32)
+                bound=dict(out=b_out, dq=b_dq, dk=b_dk, dv=b_dv), bound_fused_dq=b_dq + fused, e32=e32,
+                l2_rows=rel_l2_rows(vis) if keep is not None else None)
 
 
-def conditioned(case, out_got, keep=None, p_drop=0.0):
+def conditioned(case, out_got, keep=None, p_drop=0.0, x=None):
     """dq and dk of the float64 backward that takes delta from the out the kernels STORED (what band_dq_block and the fused prep
     kernel do), and their bounds without the delta term: what is left is (1) and (2) of the module docstring and the floors.  A
     backward whose dq and dk do not use one and the same delta - the published one - fails this where the rounding of out matters
     most: rows whose softmax is nearly one-hot (dS small next to the rounding of delta)."""
-    x = inputs(case)
+    x = x or inputs(case)
     with torch.no_grad():
         vis, dead, s, p = softmax64(case, x)
         zmax = 1.0 / (1.0 - p_drop)
@@ -265,16 +278,36 @@ def conditioned(case, out_got, keep=None, p_drop=0.0):
 
 
 # ================================================================================================ the checks both test files run
-def _ratio(got, want, bound):
+def ratio(got, want, bound):
+    """-> (worst error / bound, the number of elements outside their bound; NaN fails)."""
     err = (got.double() - want).abs()
     r = err / bound
     bad = ~(err <= bound)  # (NaN fails)
     return (float("inf") if bool(torch.isnan(r).any()) else r.max().item()), int(bad.sum())
 
 
+_ratio = ratio
+
+
+def rel_l2_rows(vis):
+    """The rows the tensor-wide bound GRAD_REL_L2 is taken over in a dropout call -> dict(dq=, dk= bool [B, NH, S]).  A live row with ONE
+    visible key has P = 1, out = Z v and dS = Z dP - delta = 0 in exact arithmetic: its dq, and the dk of a key that only such rows
+    see, are identically zero in the reference.  The kernels take delta from the stored out = bf16(Z v), so unless Z v is a bf16 number
+    (Z = 1 without dropout, Z = 2 at p = 0.5) their dS there is the rounding of out times |dO|.  The componentwise bounds count exactly
+    that (the P derr term of the module docstring) and are asserted on those elements like on all others; a norm over the whole tensor
+    would add their error to a reference that has nothing there (a sequence of one valid key - table A's third, table C's sequence 2 -
+    puts S such rows on one key: 1.1e-2 on A-S300-w300 at p = 0.1 in the CPU emulation, 2.4e-3 at p = 0 and 0.5).  So the norm is
+    taken over the complement: the dq rows that see more than one key and the dk rows of keys that such a row sees (or that no row
+    sees), on every case."""
+    one_key = vis.sum(-1, keepdim=True) == 1                 # [B, 1, S, 1]
+    only_one_key_rows = vis.any(-2) & ~(vis & ~one_key).any(-2)  # [B, 1, S]: keys seen, but by one-key rows alone
+    return dict(dq=(~one_key[..., 0]).expand(-1, NH, -1), dk=(~only_one_key_rows).expand(-1, NH, -1))
+
+
 def check_float64(ref, got, fused=False, quantities=("out", "lse", "dq", "dk", "dv")):
     """-> (measured: {quantity: worst error / bound, d*_rel_l2, lse_max_abs}, failures: [str]).  got: out, dq, dk, dv [B, NH, S, 64] and
-    lse [B, NH, S] (any of `quantities`)."""
+    lse [B, NH, S] (any of `quantities`).  The relative L2 error of a gradient is taken over the whole tensor, or, against a dropout
+    reference, over rel_l2_rows."""
     seen, fails = {}, []
     for nm in quantities:
         if nm == "lse":
@@ -290,9 +323,11 @@ def check_float64(ref, got, fused=False, quantities=("out", "lse", "dq", "dk", "
         if nbad:
             fails.append(f"{nm}: {nbad} elements outside the bound, worst error / bound = {seen[nm]:.3f}")
         if nm != "out":
-            n = ref[nm].norm().item()
+            rows = (ref.get("l2_rows") or {}).get(nm)
+            g, w = (got[nm], ref[nm]) if rows is None else (got[nm][rows], ref[nm][rows])
+            n = w.norm().item()
             if n > 0.0:
-                seen[f"{nm}_rel_l2"] = ((got[nm].double() - ref[nm]).norm() / n).item()
+                seen[f"{nm}_rel_l2"] = ((g.double() - w).norm() / n).item()
                 if not seen[f"{nm}_rel_l2"] < GRAD_REL_L2:
                     fails.append(f"{nm}: relative L2 error {seen[f'{nm}_rel_l2']:.3e}")
     return seen, fails
@@ -399,13 +434,37 @@ def wrong_visibility(case, wrong):
 
 
 WRONG = ("widen_right", "narrow_left", "drop_half_tile", "mask_ignored_last_tile", "ragged_keys", "dead_mean", "delta_split")
+# mistakes of the dropout forms (they need a keep mask).  keep_group_shifted: on the last 64-key tile the decisions of an 8-key group are
+# those of the neighbouring group (the next one; the previous one where the next would leave the sequence) - in the forward, the dQ
+# sweep and the dK/dV sweep, which each regenerate the mask with index arithmetic of their own, or in one of the three alone.
+WRONG_DROP = ("l_dropped", "keep_transposed", "keep_group_shifted", "keep_group_shifted_fwd", "keep_group_shifted_dq", "keep_group_shifted_dkv",
+              "ds_no_z", "dv_no_z", "delta_from_undropped_out", "scale_missing_fwd")
+
+
+def last_tile_start(S):
+    return 64 * ((S - 1) // 64)
+
+
+def shift_keep_groups(keep):
+    """keep [..., S, S] with the key groups of the last 64-key tile taken from their neighbours (WRONG_DROP's keep_group_shifted)."""
+    S = keep.shape[-1]
+    k = torch.arange(S)
+    src = torch.where(k + 8 < S, k + 8, k - 8)
+    src = torch.where(k >= last_tile_start(S), src, k)
+    return keep[..., src]
+
+
+def all_dropped_rows(case, keep):
+    """bool [B, NH, S]: live query rows whose visible keys are all dropped - out is exact zeros there while lse is finite."""
+    vis = visible(case)
+    return vis.any(-1).expand(-1, NH, -1) & ~(vis & keep).any(-1)
 
 
 def emulate(case, keep=None, p_drop=0.0, wrong=None, fused=False):
     """A torch fp32 restatement of the kernels' documented arithmetic: fp32 scores of the device's q (exp2 units), p~ = exp2(s - m),
     l = sum p~, bf16(p~ o keep) V / l [/ (1 - p)] stored as bf16; backward p = exp2(s - lse log2 e), delta from the STORED out,
     dS = p (Z dP - delta) and p o Z rounded to bf16, bf16 stores; fused: one bf16 partial dq per 256-key block, pairs added in bf16.
-    wrong: one of WRONG - the same arithmetic with one mistake."""
+    wrong: one of WRONG or (with a keep mask) WRONG_DROP - the same arithmetic with one mistake."""
     x = inputs(case)
     S = case.S
     qkv = x["qkv_dev"].float()
@@ -417,9 +476,19 @@ def emulate(case, keep=None, p_drop=0.0, wrong=None, fused=False):
         k = torch.cat([k, k[:, :, S - 1:S].expand(-1, -1, Sk - S, -1)], 2)
         v = torch.cat([v, v[:, :, S - 1:S].expand(-1, -1, Sk - S, -1)], 2)
     zs = 1.0 / (1.0 - p_drop)
-    keepf = keep.float() if keep is not None else None
-    if keepf is not None and Sk > S:
-        keepf = torch.cat([keepf, torch.ones(case.B, NH, S, Sk - S)], 3)
+    # the three sweeps' masks: forward, dQ, dK/dV
+    keepf = keepq = keepk = keep.float() if keep is not None else None
+    if keep is not None:
+        if Sk > S:
+            keepf = keepq = keepk = torch.cat([keepf, torch.ones(case.B, NH, S, Sk - S)], 3)
+        if wrong == "keep_transposed":
+            keepf = keepq = keepk = keep.float().transpose(-1, -2)
+        if wrong in ("keep_group_shifted", "keep_group_shifted_fwd"):
+            keepf = shift_keep_groups(keep.float())
+        if wrong in ("keep_group_shifted", "keep_group_shifted_dq"):
+            keepq = shift_keep_groups(keep.float())
+        if wrong in ("keep_group_shifted", "keep_group_shifted_dkv"):
+            keepk = shift_keep_groups(keep.float())
     s2 = qd @ k.transpose(-1, -2)
     if not case.pre:
         s2 = s2 * SOFTMAX_Q_SCALE
@@ -427,10 +496,10 @@ def emulate(case, keep=None, p_drop=0.0, wrong=None, fused=False):
     dead = ~vis.any(-1).expand(-1, NH, -1)
     m = s2.amax(-1, keepdim=True).masked_fill(dead[..., None], 0.0)
     pt = torch.exp2(s2 - m)
-    l = pt.sum(-1, keepdim=True)
-    inv = torch.where(l > 0, 1.0 / l, torch.zeros_like(l))
     ptz = pt * keepf if keepf is not None else pt
-    o32 = (_bf(ptz) @ v) * (inv * zs if keepf is not None else inv)
+    l = (ptz if wrong == "l_dropped" else pt).sum(-1, keepdim=True)
+    inv = torch.where(l > 0, 1.0 / l, torch.zeros_like(l))
+    o32 = (_bf(ptz) @ v) * (inv * zs if (keepf is not None and wrong != "scale_missing_fwd") else inv)
     out = o32.to(torch.bfloat16)
     lse = ((m + torch.log2(l)) * LN2)[..., 0].masked_fill(dead, float("inf"))
     if wrong == "dead_mean":
@@ -439,10 +508,15 @@ def emulate(case, keep=None, p_drop=0.0, wrong=None, fused=False):
     lse2 = (lse * LOG2E)[..., None]
     p = torch.exp2(s2 - lse2).masked_fill(~vis, 0.0).masked_fill(dead[..., None], 0.0)
     delta = (do * out.float()).sum(-1, keepdim=True)
+    if wrong == "delta_from_undropped_out":
+        delta = (do * ((_bf(pt) @ v) * inv).to(torch.bfloat16).float()).sum(-1, keepdim=True)
     dP = do @ v.transpose(-1, -2)
-    zdp = dP * keepf * zs if keepf is not None else dP
-    dS = p * (zdp - delta)
-    dS_q = p * (zdp - (do * o32).sum(-1, keepdim=True)) if wrong == "delta_split" else dS
+
+    def z_dp(kx):
+        return dP * kx * zs if (kx is not None and wrong != "ds_no_z") else dP
+
+    dS = p * (z_dp(keepk) - delta)
+    dS_q = p * (z_dp(keepq) - ((do * o32).sum(-1, keepdim=True) if wrong == "delta_split" else delta))
     ds16, dsq16 = _bf(dS), _bf(dS_q)
     if fused:
         parts = [_bf(dsq16[..., j:j + 256] @ k[:, :, j:j + 256]) for j in range(0, Sk, 256)]
@@ -452,7 +526,7 @@ def emulate(case, keep=None, p_drop=0.0, wrong=None, fused=False):
         dq_acc = dsq16 @ k
     dq = (dq_acc * SCALE).to(torch.bfloat16)
     dk = ((ds16.transpose(-1, -2) @ qd) * (LN2 if case.pre else SCALE)).to(torch.bfloat16)[:, :, :S]
-    pz16 = _bf(p * keepf * zs) if keepf is not None else _bf(p)
+    pz16 = _bf(p * keepk * zs) if (keepk is not None and wrong != "dv_no_z") else _bf(p)
     dv = (pz16.transpose(-1, -2) @ do).to(torch.bfloat16)[:, :, :S]
     return dict(out=out, lse=lse, dq=dq, dk=dk, dv=dv, delta=delta[..., 0])
 

@@ -223,18 +223,25 @@ GELU_FIT_REL = 3.3e-6  # csrc/common.h: the erfcc fit of Phi "3.3e-6 as evaluate
 GELU_MARGIN = 2.0      # twice that: the products a Phi(a) and (.) b add one fp32 rounding each (2u = 1.2e-7 of the result)
 
 
-def geglu_fwd_ref(h):
-    """h [R, 2I] float64 (bf16 values) -> (ref, bound) of y = gelu_erf(a) b rounded to bf16, a = h[:, :I], b = h[:, I:]."""
+def geglu_fwd_ref32(h):
+    """h [R, 2I] float64 (bf16 values) -> (ref, e32): y = gelu_erf(a) b, a = h[:, :I], b = h[:, I:], and the error of the kernel's
+    fp32 value before it is rounded to bf16 (tests/dropout_refs.py multiplies both by the dropout factor before that rounding)."""
     I = h.shape[1] // 2
     a, b = h[:, :I], h[:, I:]
     ref = gelu64(a) * b
-    return ref, bf16_bound(ref, GELU_MARGIN * GELU_FIT_REL * ref.abs() + FTZ)
+    return ref, GELU_MARGIN * GELU_FIT_REL * ref.abs() + FTZ
 
 
-def geglu_bwd_ref(dg, h):
-    """-> (ref [R, 2I], bound): d/da = dg b gelu'(a), d/db = dg gelu(a), each rounded to bf16.  gelu'(a) = Phi(a) + a phi(a) can
-    vanish (a ~ -0.75) where neither of its terms does, so its fp32 error is taken against Phi(a) + |a| phi(a): both terms come out
-    of exponentials of the same fp32 argument -a^2 / 2 log2 e, the source of the fit's 3.3e-6."""
+def geglu_fwd_ref(h):
+    """-> (ref, bound) of y = gelu_erf(a) b rounded to bf16."""
+    ref, e32 = geglu_fwd_ref32(h)
+    return ref, bf16_bound(ref, e32)
+
+
+def geglu_bwd_ref32(dg, h):
+    """-> (ref [R, 2I], e32): d/da = dg b gelu'(a), d/db = dg gelu(a) and the error of the kernel's fp32 values.  gelu'(a) =
+    Phi(a) + a phi(a) can vanish (a ~ -0.75) where neither of its terms does, so its fp32 error is taken against Phi(a) + |a| phi(a):
+    both terms come out of exponentials of the same fp32 argument -a^2 / 2 log2 e, the source of the fit's 3.3e-6."""
     I = h.shape[1] // 2
     a, b = h[:, :I], h[:, I:]
     pdf = torch.exp(-0.5 * a * a) / math.sqrt(2.0 * math.pi)
@@ -242,7 +249,13 @@ def geglu_bwd_ref(dg, h):
     db = dg * gelu64(a)
     e_da = GELU_MARGIN * GELU_FIT_REL * (dg * b).abs() * (phi_cdf(a) + a.abs() * pdf) + FTZ
     e_db = GELU_MARGIN * GELU_FIT_REL * db.abs() + FTZ
-    return torch.cat([da, db], 1), torch.cat([bf16_bound(da, e_da), bf16_bound(db, e_db)], 1)
+    return torch.cat([da, db], 1), torch.cat([e_da, e_db], 1)
+
+
+def geglu_bwd_ref(dg, h):
+    """-> (ref [R, 2I], bound), each half rounded to bf16."""
+    ref, e32 = geglu_bwd_ref32(dg, h)
+    return ref, bf16_bound(ref, e32)
 
 
 def geglu_h(T, I, g):

@@ -14,6 +14,7 @@ HEADERS = sorted(glob.glob(os.path.join(ROOT, "include", "*.h")))  # every publi
 KG = "tests/test_kernels_gpu.py::"
 CH = "tests/test_conv_head_kernels_gpu.py::"
 DR = "tests/test_dropout_gpu.py::"
+DK = "tests/test_dropout_kernels_gpu.py::"
 MU = "tests/test_muon_gpu.py::"
 MG = "tests/test_model_gpu.py::"
 RK = "tests/test_row_kernels_gpu.py::"
@@ -85,21 +86,30 @@ LEDGER = {
     "cm3p_attn_bwd_fused": [KG + "test_attention_global_backward_both_implementations",
                             AD + "test_matches_float64"],
     "cm3p_attn_fwd_dropout": [DR + "test_attention_dropout_matches_fp32_restatement",
-                              AD + "test_dropout_at_other_windows"],
+                              AD + "test_dropout_at_other_windows",
+                              DK + "test_attention_dropout_matches_float64", DK + "test_attention_dropout_with_a_top_bit_seed_and_another_layer"],
     "cm3p_attn_bwd_dropout": [DR + "test_attention_dropout_matches_fp32_restatement",
-                              AD + "test_dropout_at_other_windows"],
-    "cm3p_attn_fwd_dropout_varlen": [DR + "test_attention_dropout_varlen_equals_padded"],
-    "cm3p_attn_bwd_dropout_varlen": [DR + "test_attention_dropout_varlen_equals_padded"],
+                              AD + "test_dropout_at_other_windows",
+                              DK + "test_attention_dropout_matches_float64", DK + "test_attention_dropout_with_a_top_bit_seed_and_another_layer"],
+    "cm3p_attn_fwd_dropout_varlen": [DR + "test_attention_dropout_varlen_equals_padded",
+                                     DK + "test_packed_attention_dropout_matches_float64"],
+    "cm3p_attn_bwd_dropout_varlen": [DR + "test_attention_dropout_varlen_equals_padded",
+                                     DK + "test_packed_attention_dropout_matches_float64"],
     "cm3p_geglu_fwd": [KG + "test_geglu_and_gelu",
                        RK + "test_geglu_against_float64"],
     "cm3p_gemm_geglu": [KG + "test_wi_gemm_with_geglu_in_its_store_phase_equals_the_two_kernels",
                         GK + "test_geglu_epilogue_against_float64_and_the_two_kernel_chain"],
     "cm3p_geglu_bwd": [KG + "test_geglu_and_gelu",
                        RK + "test_geglu_against_float64"],
-    "cm3p_dropout_f32": [DR + "test_dropout_f32_matches_the_mask_and_packed_equals_padded"],
-    "cm3p_geglu_fwd_dropout": [DR + "test_geglu_dropout_forward_and_backward"],
-    "cm3p_geglu_bwd_dropout": [DR + "test_geglu_dropout_forward_and_backward"],
-    "cm3p_dropout_keep": [DR + "test_materialiser_equals_the_restatement"],
+    "cm3p_dropout_f32": [DR + "test_dropout_f32_matches_the_mask_and_packed_equals_padded",
+                         DK + "test_dropout_f32_every_output_form_at_one_group_per_row", DK + "test_dropout_f32_past_the_grid",
+                         DK + "test_dropout_f32_every_site_and_the_edge_thresholds", DK + "test_dropout_f32_packed_layouts"],
+    "cm3p_geglu_fwd_dropout": [DR + "test_geglu_dropout_forward_and_backward",
+                               DK + "test_geglu_dropout_against_float64", DK + "test_geglu_dropout_at_the_edge_thresholds"],
+    "cm3p_geglu_bwd_dropout": [DR + "test_geglu_dropout_forward_and_backward",
+                               DK + "test_geglu_dropout_against_float64", DK + "test_geglu_dropout_at_the_edge_thresholds"],
+    "cm3p_dropout_keep": [DR + "test_materialiser_equals_the_restatement",
+                          DK + "test_materialiser_in_bits"],
     "cm3p_philox4x32_10_host": ["tests/test_dropout_host.py::test_philox_known_answers", "tests/test_dropout_host.py::test_philox_matches_python_restatement"],
     "cm3p_gelu_fwd": [KG + "test_gelu_on_every_finite_bf16_input_against_float64",
                       RK + "test_gelu_element_kernels_past_the_grid"],
