@@ -147,6 +147,18 @@ QROWS_SIGNATURES = {
 }
 ATTN_QROWS_ABI_VERSION = 1
 
+# name -> argtypes of include/ext/cm3p_mlm_loss.h (the masked-LM loss without the logits tensor), one to one; a table and a version of
+# its own as above.
+MLM_LOSS_SIGNATURES = {
+    "cm3p_mlm_loss_abi_version": [],
+    "cm3p_mlm_lse": [_P, _P, _P, _P, _L, _L, _L, _L, _L, _P, _P, _P, _L, _P],
+    "cm3p_mlm_lse_workspace_bytes": [_L, _L],
+    "cm3p_mlm_dlogits": [_P, _P, _P, _P, _L, _P, _P, _P, _L, _L, _L, _L, _P, _P, _I, _P, _L, _P],
+    "cm3p_mlm_dlogits_workspace_bytes": [_L, _L],
+}
+MLM_LOSS_ABI_VERSION = 1
+_RETURNS_INT64.update({"cm3p_mlm_lse_workspace_bytes", "cm3p_mlm_dlogits_workspace_bytes"})
+
 _lib = None
 
 
@@ -165,7 +177,8 @@ def load() -> ctypes.CDLL:
             "cm3p_amd has no CPU or PyTorch fallback."
         )
     lib = ctypes.CDLL(LIB_PATH)
-    for name, argtypes in (*SIGNATURES.items(), *EXT_SIGNATURES.items(), *ROW_SIGNATURES.items(), *QROWS_SIGNATURES.items()):
+    for name, argtypes in (*SIGNATURES.items(), *EXT_SIGNATURES.items(), *ROW_SIGNATURES.items(), *QROWS_SIGNATURES.items(),
+                           *MLM_LOSS_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if a declared symbol is not exported
         fn.argtypes = argtypes
         fn.restype = c_int64 if name in _RETURNS_INT64 else c_int
@@ -177,6 +190,8 @@ def load() -> ctypes.CDLL:
         raise Cm3pHipError(f"cm3p_attn_row.h ABI mismatch: library {lib.cm3p_attn_row_abi_version()} vs binding {ATTN_ROW_ABI_VERSION}; rebuild")
     if lib.cm3p_attn_qrows_abi_version() != ATTN_QROWS_ABI_VERSION:
         raise Cm3pHipError(f"cm3p_attn_qrows.h ABI mismatch: library {lib.cm3p_attn_qrows_abi_version()} vs binding {ATTN_QROWS_ABI_VERSION}; rebuild")
+    if lib.cm3p_mlm_loss_abi_version() != MLM_LOSS_ABI_VERSION:
+        raise Cm3pHipError(f"ext/cm3p_mlm_loss.h ABI mismatch: library {lib.cm3p_mlm_loss_abi_version()} vs binding {MLM_LOSS_ABI_VERSION}; rebuild")
     if lib.cm3p_build_ablation_flags() != 0 and os.environ.get("CM3P_ALLOW_ABLATED_LIB") != "1":
         raise Cm3pHipError(
             f"{LIB_PATH} was built with timing-only ablation macros (mask {lib.cm3p_build_ablation_flags():#x}): its results are wrong by "

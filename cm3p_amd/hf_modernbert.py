@@ -294,6 +294,10 @@ class FusedModernBertForMaskedLM(ModernBertPreTrainedModel):
         # opt-in (not in config or state dict): with sparse_prediction, in training mode with labels, the tower's last layer runs on the
         # labelled rows only (CM3PEncoder.forward's last_layer_rows) instead of on all rows followed by the row selection
         self.labelled_rows_last_layer = False
+        # opt-in (not in config or state dict): in training mode with labels the loss comes from _MLMHeadLogitFreeLossFn, which never
+        # stores the [rows, vocab] logits (13.2 GB at 8 x 8192 tokens of the default vocabulary), and the output's `logits` is None;
+        # evaluation and calls without labels return logits as ever
+        self.logit_free_mlm_loss = False
         self.post_init()
 
     def get_output_embeddings(self):
@@ -317,7 +321,7 @@ class FusedModernBertForMaskedLM(ModernBertPreTrainedModel):
     def forward(self, input_ids: Optional[Tensor] = None, attention_mask: Optional[Tensor] = None, position_ids: Optional[Tensor] = None,
                 inputs_embeds: Optional[Tensor] = None, labels: Optional[Tensor] = None, output_attentions: Optional[bool] = None,
                 output_hidden_states: Optional[bool] = None, return_dict: Optional[bool] = None, **kwargs) -> MaskedLMOutput:
-        from .modeling_cm3p import _MLMHeadFn, _MLMHeadLossFn, _TakeRowsFn
+        from .modeling_cm3p import _MLMHeadFn, _MLMHeadLogitFreeLossFn, _MLMHeadLossFn, _TakeRowsFn
 
         if self.model.cls_only_last_layer:
             raise ValueError("FusedModernBertForMaskedLM with cls_only_last_layer: the MLM head reads every row of the last layer; switch it off")
@@ -344,11 +348,15 @@ class FusedModernBertForMaskedLM(ModernBertPreTrainedModel):
         head_args = (rows, self.head.dense.weight, self.head.dense.bias, self.head.norm.weight, self.decoder.weight, self.decoder.bias,
                      self.config.norm_eps)
         loss = None
-        if labels is not None:
-            lp, loss = _MLMHeadLossFn.apply(*head_args, labels, kwargs.get("num_items_in_batch"))
+        if labels is not None and self.logit_free_mlm_loss and self.training:
+            loss = _MLMHeadLogitFreeLossFn.apply(*head_args, labels, kwargs.get("num_items_in_batch"))
+            logits = None  # (never formed: the Trainer reads `loss`)
         else:
-            lp = _MLMHeadFn.apply(*head_args)
-        logits = lp[..., :V] if sparse else lp.view(Bq, Sq, -1)[..., :V]
+            if labels is not None:
+                lp, loss = _MLMHeadLossFn.apply(*head_args, labels, kwargs.get("num_items_in_batch"))
+            else:
+                lp = _MLMHeadFn.apply(*head_args)
+            logits = lp[..., :V] if sparse else lp.view(Bq, Sq, -1)[..., :V]
         ret_dict = bool(getattr(self.config, "return_dict", True) if return_dict is None else return_dict)
         if not ret_dict:
             return tuple(v for v in (loss, logits, out.hidden_states, out.attentions) if v is not None)

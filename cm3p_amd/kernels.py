@@ -1010,6 +1010,39 @@ def ce_masked_dlogits_bf16(logits: Tensor, cols: int, target: Tensor, ignore_ind
     return dl, colsum
 
 
+def mlm_lse(y: Tensor, w: Tensor, bias: Optional[Tensor], cols: int, target: Tensor, ignore_index: int):
+    """The decoder GEMM and ce_masked_stats in one, without the logits (include/ext/cm3p_mlm_loss.h): y [T, H] bf16, w [Vp, H] bf16,
+    bias [Vp] fp32 or None, cols = V <= Vp -> (loss_rows, lse_rows), zero for ignored rows."""
+    T, H = y.shape
+    Vp = w.shape[0]
+    loss_rows = torch.empty((T,), dtype=torch.float32, device=y.device)
+    lse_rows = torch.empty((T,), dtype=torch.float32, device=y.device)
+    nbytes = query("cm3p_mlm_lse_workspace_bytes", T, Vp)
+    ws = torch.empty((max(nbytes, 16),), dtype=torch.uint8, device=y.device)
+    call("cm3p_mlm_lse", ptr(y, torch.bfloat16), ptr(w, torch.bfloat16), ptr(bias, torch.float32) if bias is not None else None, ptr(target, torch.int64), ignore_index,
+         T, H, cols, Vp, ptr(loss_rows), ptr(lse_rows), ptr(ws), ws.numel(), stream(), tag="cm3p_mlm_lse", work=2.0 * T * Vp * H)
+    return loss_rows, lse_rows
+
+
+def mlm_dlogits(y: Tensor, w: Tensor, bias: Optional[Tensor], cols: int, target: Tensor, ignore_index: int, lse_rows: Tensor, scale_a: Tensor,
+                scale_b: Tensor, colsum: Optional[Tensor] = None, accumulate: bool = False, out: Optional[Tensor] = None):
+    """ce_masked_dlogits_bf16 from recomputed logit tiles: -> (dlogits bf16 [T, Vp], column sums fp32 [Vp]).  accumulate: the sums are
+    added to `colsum` (the row chunks of one batch); out: a [>= T, Vp] bf16 buffer whose first T rows are written."""
+    T, H = y.shape
+    Vp = w.shape[0]
+    dl = torch.empty((T, Vp), dtype=torch.bfloat16, device=y.device) if out is None else out[:T]
+    if colsum is None:
+        if accumulate:
+            raise ValueError("mlm_dlogits: accumulate needs the colsum to add to")
+        colsum = torch.empty((Vp,), dtype=torch.float32, device=y.device)
+    nbytes = query("cm3p_mlm_dlogits_workspace_bytes", T, Vp)
+    ws = torch.empty((max(nbytes, 16),), dtype=torch.uint8, device=y.device)
+    call("cm3p_mlm_dlogits", ptr(y, torch.bfloat16), ptr(w, torch.bfloat16), ptr(bias, torch.float32) if bias is not None else None, ptr(target, torch.int64), ignore_index,
+         ptr(lse_rows, torch.float32), ptr(scale_a, torch.float32), ptr(scale_b, torch.float32), T, H, cols, Vp, ptr(dl, torch.bfloat16), ptr(colsum, torch.float32),
+         int(accumulate), ptr(ws), ws.numel(), stream(), tag="cm3p_mlm_dlogits", work=2.0 * T * Vp * H)
+    return dl, colsum
+
+
 def inv_valid_count(target: Tensor, ignore_index: int) -> Tensor:
     out = torch.empty((1,), dtype=torch.float32, device=target.device)
     call("cm3p_inv_valid_count", ptr(target, torch.int64), target.numel(), ignore_index, ptr(out), stream())

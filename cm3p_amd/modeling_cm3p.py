@@ -238,12 +238,10 @@ def cm3p_loss_hip(logits_per_metadata: Tensor, metadata_variation_classes: Optio
     return _CrossEntropySumFn.apply(specs, L)
 
 
-def _mlm_head_forward(h: Tensor, Wd: Tensor, bd: Optional[Tensor], norm_w: Tensor, Wdec: Tensor, bdec: Optional[Tensor], eps: float):
-    """decoder(norm(gelu(dense(h)))) (CM3PPredictionHead + decoder, ref:cm3p/modeling_cm3p.py:991,1229-1238) -> (fp32 logits
-    [T, Vp], what the backward needs, parameter dtypes); Vp = vocab rounded up to a multiple of 64, so that the decoder's input-
-    gradient GEMM, which contracts over Vp, runs on the 256 x 256 kernel (pad columns hold the zero pad weights' product;
-    callers slice)."""
-    from ._lib import EPI_F32, EPI_F32_BIAS
+def _mlm_head_trunk(h: Tensor, Wd: Tensor, bd: Optional[Tensor], norm_w: Tensor, Wdec: Tensor, bdec: Optional[Tensor], eps: float):
+    """norm(gelu(dense(h))) and the decoder's operands: what _mlm_head_forward and the logit-free node share -> (what the backward
+    needs, the decoder bias padded to Vp in fp32 | None, parameter dtypes); Vp = vocab rounded up to a multiple of 64."""
+    from ._lib import EPI_F32
     from .encoder import _bf16_weight
 
     T, H = h.shape
@@ -263,27 +261,50 @@ def _mlm_head_forward(h: Tensor, Wd: Tensor, bd: Optional[Tensor], norm_w: Tenso
     z = K.gemm(hb, Wd_b, T, H, H, True, True, EPI_F32)
     _, a32 = K.bias_gelu_fwd(z, bd32, False, True)
     _, y, mean, rstd = K.layernorm_fwd(a32, w32, eps, False, True)
-    if bdec is not None:  # the decoder bias is added while the GEMM stores its tiles (no extra pass over [T, Vp])
+    bp = None
+    if bdec is not None:
         bp = torch.zeros((Vp,), dtype=torch.float32, device=h.device)
         bp[:V].copy_(_f32(bdec.detach()))
+    pack = (hb, Wd_b, Wdec_b, bd32, w32, z, a32, y, mean, rstd, V)
+    meta = (Wd.dtype, bd.dtype if bd is not None else None, norm_w.dtype, Wdec.dtype, bdec.dtype if bdec is not None else None, h.dtype)
+    return pack, bp, meta
+
+
+def _mlm_head_forward(h: Tensor, Wd: Tensor, bd: Optional[Tensor], norm_w: Tensor, Wdec: Tensor, bdec: Optional[Tensor], eps: float):
+    """decoder(norm(gelu(dense(h)))) (CM3PPredictionHead + decoder, ref:cm3p/modeling_cm3p.py:991,1229-1238) -> (fp32 logits
+    [T, Vp], what the backward needs, parameter dtypes); Vp = vocab rounded up to a multiple of 64, so that the decoder's input-
+    gradient GEMM, which contracts over Vp, runs on the 256 x 256 kernel (pad columns hold the zero pad weights' product;
+    callers slice)."""
+    from ._lib import EPI_F32, EPI_F32_BIAS
+
+    pack, bp, meta = _mlm_head_trunk(h, Wd, bd, norm_w, Wdec, bdec, eps)
+    Wdec_b, y = pack[2], pack[7]
+    T, H = y.shape
+    Vp = Wdec_b.shape[0]
+    if bp is not None:  # the decoder bias is added while the GEMM stores its tiles (no extra pass over [T, Vp])
         logits = K.gemm(y, Wdec_b, T, Vp, H, True, True, EPI_F32_BIAS, resid=bp)
     else:
         logits = K.gemm(y, Wdec_b, T, Vp, H, True, True, EPI_F32)
-    pack = (hb, Wd_b, Wdec_b, bd32, w32, z, a32, y, mean, rstd, V)
-    meta = (Wd.dtype, bd.dtype if bd is not None else None, norm_w.dtype, Wdec.dtype, bdec.dtype if bdec is not None else None, h.dtype)
     return logits, pack, meta
 
 
 def _mlm_head_backward(pack, meta, need_dh: bool, dlb: Tensor, dbdec_full: Optional[Tensor]):
     """dlb: bf16 [T, Vp] gradient of the padded logits; dbdec_full: its fp32 column sums.  -> gradients of
     (h, Wd, bd, norm_w, Wdec, bdec); dh has the dtype of h (bf16 rows of a bf16 residual stream: the dgrad GEMM stores bf16)."""
+    Wdec_b, y = pack[2], pack[7]
+    dy = K.linear_dgrad(dlb, Wdec_b)
+    dWdec_full = K.linear_wgrad(dlb, y)
+    return _mlm_head_backward_below(pack, meta, need_dh, dy, dWdec_full, dbdec_full)
+
+
+def _mlm_head_backward_below(pack, meta, need_dh: bool, dy: Tensor, dWdec_full: Tensor, dbdec_full: Optional[Tensor]):
+    """Everything below the decoder: dy bf16 [T, H] (the decoder's input gradient), dWdec_full fp32 [Vp, H], dbdec_full fp32 [Vp]."""
     from ._lib import EPI_BF16, EPI_F32
 
     hb, Wd_b, Wdec_b, bd32, w32, z, a32, y, mean, rstd, V = pack
     dWd_t, dbd_t, dnw_t, dWdec_t, dbdec_t, h_t = meta
     T, H = hb.shape
-    dy = K.linear_dgrad(dlb, Wdec_b)
-    dWdec = K.linear_wgrad(dlb, y)[:V]
+    dWdec = dWdec_full[:V]
     dbdec = dbdec_full[:V] if dbdec_t is not None else None
     da, _, dnw = K.layernorm_bwd(dy, a32, w32, mean, rstd, None, False, inplace=False)
     dz, dbd = K.bias_gelu_bwd(da, z, bd32)
@@ -351,6 +372,73 @@ class _MLMHeadLossFn(torch.autograd.Function):
         if dlb is None:
             return (None,) * 9
         return (*_mlm_head_backward(ctx.pack, ctx.meta, ctx.needs_input_grad[0], dlb, colsum), None, None, None)
+
+
+# Bytes of the bf16 logit gradient _MLMHeadLogitFreeLossFn.backward holds at a time: it works in chunks of the largest multiple of 128
+# rows whose [rows, Vp] bf16 block fits (at least 128 rows).  Tests set MLM_LOGIT_FREE_CHUNK_ROWS to force several chunks.
+MLM_LOGIT_FREE_CHUNK_BYTES = 256 << 20
+MLM_LOGIT_FREE_CHUNK_ROWS: Optional[int] = None
+
+
+def _mlm_logit_free_chunk_rows(Vp: int) -> int:
+    if MLM_LOGIT_FREE_CHUNK_ROWS is not None:
+        rows = int(MLM_LOGIT_FREE_CHUNK_ROWS)
+        if rows < 128 or rows % 128:
+            raise ValueError(f"MLM_LOGIT_FREE_CHUNK_ROWS must be a positive multiple of 128, got {rows}")
+        return rows
+    return max(128, MLM_LOGIT_FREE_CHUNK_BYTES // (Vp * 2) // 128 * 128)
+
+
+class _MLMHeadLogitFreeLossFn(torch.autograd.Function):
+    """_MLMHeadLossFn without the logits (`logit_free_mlm_loss`): same arguments, returns the loss only.  The forward runs the head's
+    trunk and cm3p_mlm_lse, which consumes the decoder's logit tiles where they are computed; the backward recomputes them in
+    cm3p_mlm_dlogits, a chunk of rows at a time, so that the largest [rows, Vp] tensor of the step is one bf16 chunk
+    (MLM_LOGIT_FREE_CHUNK_BYTES).  Per chunk: the decoder's dgrad rows, its weight gradient (summed in fp32 over the chunks) and the
+    bias gradient (summed by the kernel's accumulate flag); everything below the decoder then runs once on the full dy."""
+
+    @staticmethod
+    def forward(ctx, h: Tensor, Wd: Tensor, bd: Optional[Tensor], norm_w: Tensor, Wdec: Tensor, bdec: Optional[Tensor], eps: float,
+                labels: Tensor, num_items: Optional[Tensor]):
+        ctx.pack, bp, ctx.meta = _mlm_head_trunk(h, Wd, bd, norm_w, Wdec, bdec, eps)
+        Wdec_b, y = ctx.pack[2], ctx.pack[7]
+        V = Wdec.shape[0]
+        lab = labels.reshape(-1).contiguous().to(torch.int64)
+        if lab.numel() != y.shape[0]:
+            raise ValueError(f"labels have {lab.numel()} entries, the head {y.shape[0]} rows")
+        if num_items is None:
+            inv = K.inv_valid_count(lab, -100)
+        else:
+            n = num_items if torch.is_tensor(num_items) else torch.tensor(float(num_items))
+            inv = (1.0 / n.to(device=y.device, dtype=torch.float32)).reshape(1).contiguous()  # scalar plumbing
+        loss_rows, lse_rows = K.mlm_lse(y, Wdec_b, bp, V, lab, -100)
+        loss = K.scale_by(K.sum_f32(loss_rows, 1.0), inv)
+        ctx.ce = (bp, lab, lse_rows, inv)
+        ctx.set_materialize_grads(False)
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, dloss: Optional[Tensor]):
+        from ._lib import EPI_BF16
+
+        if dloss is None:
+            return (None,) * 9
+        bp, lab, lse_rows, inv = ctx.ce
+        Wdec_b, y, V = ctx.pack[2], ctx.pack[7], ctx.pack[10]
+        T, H = y.shape
+        Vp = Wdec_b.shape[0]
+        g = dloss.reshape(1).contiguous().float()
+        rows = min(_mlm_logit_free_chunk_rows(Vp), max(T + 127, 128) // 128 * 128)
+        buf = torch.empty((rows, Vp), dtype=torch.bfloat16, device=y.device)
+        dy = torch.empty((T, H), dtype=torch.bfloat16, device=y.device)
+        colsum = torch.empty((Vp,), dtype=torch.float32, device=y.device)
+        dWdec = None
+        for r0 in range(0, T, rows):
+            r1 = min(r0 + rows, T)
+            dlb, _ = K.mlm_dlogits(y[r0:r1], Wdec_b, bp, V, lab[r0:r1], -100, lse_rows[r0:r1], g, inv, colsum=colsum, accumulate=r0 > 0, out=buf)
+            K.gemm(dlb, Wdec_b, r1 - r0, H, Vp, True, False, EPI_BF16, out=dy[r0:r1])
+            dW = K.linear_wgrad(dlb, y[r0:r1])
+            dWdec = dW if dWdec is None else K.add_f32(dWdec, dW)[0]
+        return (*_mlm_head_backward_below(ctx.pack, ctx.meta, ctx.needs_input_grad[0], dy, dWdec, colsum), None, None, None)
 
 
 class _AddScaledFn(torch.autograd.Function):
@@ -826,6 +914,10 @@ class CM3PModel(CM3PPreTrainedModel):
         self.gather_negatives = False
         self.unpad_inputs = None  # True / False overrides the reference's rule (unpad iff attn_implementation is flash_attention_2)
         self._labelled_rows_last_layer = False
+        # Opt-in (not in config or state dict): a training-mode call with labels and return_loss takes the masked-LM loss from the
+        # decoder's logit tiles without storing them (_MLMHeadLogitFreeLossFn); the output's `logits` is then None.  Every other call -
+        # evaluation, no labels - returns logits as without it.
+        self.logit_free_mlm_loss = False
         self.post_init()
 
     @property
@@ -1038,14 +1130,16 @@ class CM3PModel(CM3PPreTrainedModel):
                 labels = sel_labels
             head_args = (hs.reshape(-1, hs.size(-1)), self.head.dense.weight, self.head.dense.bias, self.head.norm.weight,
                          self.decoder.weight, self.decoder.bias, self.config.beatmap_config.norm_eps)
-            mlm = None
-            if labels is not None and return_loss:
+            mlm = lp = None
+            if labels is not None and return_loss and self.logit_free_mlm_loss and self.training:
+                mlm = _MLMHeadLogitFreeLossFn.apply(*head_args, labels, kwargs.get("num_items_in_batch"))  # (logits stays None)
+            elif labels is not None and return_loss:
                 lp, mlm = _MLMHeadLossFn.apply(*head_args, labels, kwargs.get("num_items_in_batch"))
             else:
                 lp = _MLMHeadFn.apply(*head_args)
-            if hs.dim() == 3:
+            if lp is not None and hs.dim() == 3:
                 logits = lp.view(hs.size(0), hs.size(1), -1)[..., :V]
-            else:
+            elif lp is not None:
                 # caller-supplied unpadded rows: logits (total_nnz, V), re-padded like the reference's flash_attention_2 branch
                 # (_pad_cm3p_output, ref:cm3p/modeling_cm3p.py:999-1001) when the padded geometry was given
                 logits = lp[:, :V] if n_sel is None else lp[:n_sel, :V]  # (labelled_rows_last_layer: the selected rows, in their order)
@@ -1194,6 +1288,9 @@ class CM3PForMaskedLM(CM3PPreTrainedModel):
         # opt-in (not in config or state dict): with sparse_prediction, in training mode with labels, the tower's last layer runs on the
         # labelled rows only (CM3PEncoder.forward's last_layer_rows) instead of on all rows followed by the row selection
         self.labelled_rows_last_layer = False
+        # opt-in (not in config or state dict): in training mode with labels the loss comes from _MLMHeadLogitFreeLossFn, which never
+        # stores the [rows, vocab] logits, and the output's `logits` is None; evaluation and calls without labels return logits as ever
+        self.logit_free_mlm_loss = False
         self.post_init()
 
     def get_output_embeddings(self):
@@ -1236,6 +1333,9 @@ class CM3PForMaskedLM(CM3PPreTrainedModel):
         head_args = (rows, self.head.dense.weight, self.head.dense.bias, self.head.norm.weight, self.decoder.weight, self.decoder.bias,
                      self.config.norm_eps)
         loss = None
+        if labels is not None and self.logit_free_mlm_loss and self.training:
+            loss = _MLMHeadLogitFreeLossFn.apply(*head_args, labels, kwargs.get("num_items_in_batch"))
+            return MaskedLMOutput(loss=loss, logits=None, hidden_states=out.hidden_states, attentions=out.attentions)
         if labels is not None:
             lp, loss = _MLMHeadLossFn.apply(*head_args, labels, kwargs.get("num_items_in_batch"))
         else:
