@@ -7,7 +7,9 @@
 The nn.Linear / nn.LayerNorm / nn.Embedding members are parameter containers only; their torch forward is never
 called.  Every encoder layer is ONE autograd node (`_EncoderLayerFn`; `_FinalNormFn` closes the stack) whose forward and
 backward are sequences of C-ABI launches (cm3p_amd/kernels.py), restating
-TF:models/modernbert/modeling_modernbert.py:262-333,434-478:
+TF:models/modernbert/modeling_modernbert.py:262-333,434-478; a last layer of which only some rows are consumed runs as
+`_LastLayerRowsFn`, the same layer body (`_pre_attn_*`, `_post_attn_*`: written once, both nodes call them) with attention and what
+follows it on those rows:
 
     per layer:  xn = LN(x) [identity for layer 0] -> qkv = xn Wqkv^T -> RoPE(q,k) -> flash attention (global, or
                 |i-j| <= 64 band; key padding) -> x += o Wo^T -> xn = LN(x) -> h = xn Wi^T -> g = gelu(h[:I]) * h[I:]
@@ -260,42 +262,121 @@ def _take_bf16_from_downstream(geo: _Geometry, dy: Tensor) -> Tensor:
     return g
 
 
-def _layer_forward(geo: _Geometry, i: int, x: Tensor, wb, want_stats: bool):
-    """One encoder layer on [T, H] rows: -> (x_out, activations needed by its backward)."""
-    w_an, Wqkv_b, Wo_b, w_mn, Wi_b, Wo2_b = wb[:6]
-    B, S, nh = geo.B, geo.S, geo.nh
-    scale = geo.hd ** -0.5
+# ---- the layer body, written once for both layer nodes (_EncoderLayerFn: every row; _LastLayerRowsFn: attention and what follows it on
+# a block of query rows): the operands, and a forward and a backward each of the part in front of attention and the part behind it
+def _layer_operands(geo: _Geometry, i: int, weights, mlp_rows: Optional[int]):
+    """A layer node's `weights` (in the order of CM3PEncoder._stack_weights, then its adapter tensors) -> (wb, wt, adapters):
+    wb = (w_an, Wqkv, Wo, w_mn, Wi, Wo2 as bf16 GEMM operands - the norm weights fp32 -, Wi with GeGLU-interleaved rows for the
+    forward-only fused kernel or None, whether this Wi is the fused training pair's), wt the four W^T copies the input-gradient GEMMs
+    read (None where there is none), adapters (A, B, s) or None per projection in the order Wqkv, Wo, Wi, Wo2.
+    mlp_rows: the rows the MLP runs on, which the forward-only fused Wi + GeGLU kernel's shape rule is asked about; None: a row block,
+    whose MLP is the plain chain (as _run_stack keeps the fused training pair away from it)."""
+    it = iter(weights)
+    w_an = None if i == 0 else _f32(next(it))
+    Wqkv, Wo, w_mn, Wi, Wo2 = next(it), next(it), _f32(next(it)), next(it), next(it)
+    # low-rank adapters (cm3p_amd.lora): (A, B, s) per projection in the order Wqkv, Wo, Wi, Wo2; their tensors follow the weights
+    spec = geo.lora[i] if geo.lora is not None else (None,) * 4
+    adapters = [None if sc is None else (next(it).detach(), next(it).detach(), sc) for sc in spec]
+    # forward-only and a shape of the ring kernel: the Wi GEMM stores gelu(h) * g itself (CM3P_GEGLU_FUSED=0: the two-kernel path)
+    fuse_geglu = (not geo.save) and mlp_rows is not None and _geglu_fwd_fused(geo.drop, mlp_rows, Wi)
+    # (training: the casts of every layer were made in one launch at the top of the stack, _run_stack; adapted weights: their merged
+    # copies bf16(W + s B A) were made there on every kind of call)
+    pre = geo.wcast if geo.wcast is not None else {}
+    pairs = [pre.get(id(w)) or _bf16_weight_pair(w, geo.save) if not (fuse_geglu and w is Wi) else (None, None) for w in (Wqkv, Wo, Wi, Wo2)]
+    # training step, fused pair (_run_stack decided; CM3P_GEGLU_FUSED=0: the two-kernel path): this Wi's copy has interleaved rows
+    fused_train = geo.save and id(Wi) in geo.fused_mlp
+    Wi_geglu = None
+    if fuse_geglu:
+        Wi_geglu = geo.wcast_geglu[id(Wi)] if adapters[2] is not None else _bf16_weight_cached(Wi, True)
+    wb = (w_an, pairs[0][0], pairs[1][0], w_mn, pairs[2][0], pairs[3][0], Wi_geglu, fused_train)
+    return wb, tuple(p[1] for p in pairs), adapters
+
+
+def _backward_needs(i: int, need, adapters):
+    """need: a layer node's needs_input_grad behind x -> ((n_an, n_qkv, n_o, n_mn, n_i, n_o2), lora_grads).  lora_grads(p, dy_p, x_p): the
+    adapter gradients (dA, dB) of projection p from the operands its weight-gradient GEMM reads; () when it carries no adapter."""
+    n_base = 5 if i == 0 else 6
+    need_w = list(need[:n_base])
+    if i == 0:
+        need_w.insert(0, False)  # (no attn_norm in layer 0)
+    need_l = iter(need[n_base:])
+    want_l = [None if a is None else (next(need_l), next(need_l)) for a in adapters]
+
+    def lora_grads(p: int, dy_p: Tensor, x_p: Tensor):
+        if adapters[p] is None:
+            return ()
+        if not any(want_l[p]):
+            return (None, None)
+        dA, dB = K.lora_grad(x_p, dy_p, *adapters[p])
+        return (dA if want_l[p][0] else None, dB if want_l[p][1] else None)
+
+    return need_w, lora_grads
+
+
+def _weight_grads(i: int, dw_an, grads: list, dtypes, need) -> list:
+    """What a layer node returns behind x: the gradients in the order of its weights (and adapter tensors), in their dtypes."""
+    grads = grads if i == 0 else [dw_an, *grads]
+    return [(gw if gw.dtype == dt else gw.to(dt)) if (nd and gw is not None) else None for gw, dt, nd in zip(grads, dtypes, need)]
+
+
+def _attn_drop(geo: _Geometry, i: int) -> Optional[tuple]:
+    """Layer i's attention dropout (probabilities and out_drop, TF:...modeling_modernbert.py:292,300): (thr, seed, layer), or None."""
+    return (geo.drop.attn, geo.drop.seed, i) if geo.drop is not None and geo.drop.attn else None
+
+
+def _pre_attn_forward(geo: _Geometry, i: int, x: Tensor, wb, want_stats: bool):
+    """attn_norm (the cast in layer 0) and the Wqkv + RoPE projection on every row: -> (xn, mean_a, rstd_a, qkv)."""
     cos, sin = geo.rope[i]
-    # attention dropout (probabilities and out_drop, TF:...modeling_modernbert.py:292,300): (thr, seed, layer), or None
-    ad = (geo.drop.attn, geo.drop.seed, i) if geo.drop is not None and geo.drop.attn else None
     if i == 0:  # (bf16 stream: the embedding output is layer 0's GEMM operand as it is)
         xn, mean_a, rstd_a = (x if x.dtype == torch.bfloat16 else K.cast_bf16(x)), None, None
     else:
-        _, xn, mean_a, rstd_a = K.layernorm_fwd(x, w_an, geo.eps, False, True, want_stats)
+        _, xn, mean_a, rstd_a = K.layernorm_fwd(x, wb[0], geo.eps, False, True, want_stats)
     if geo.hd != 64:
         # head sizes 16 / 32: plain projection, rotary embedding as its own pass (fp32 on the bf16 projection, one rounding: the
         # reference's order), attention on the generic kernels (csrc/attention_generic.hip); padded execution only
-        qkv = K.linear_fwd(xn, Wqkv_b)
-        K.rope_apply_generic_(qkv, cos, sin, B, S, nh, geo.hd, geo.per_batch_pos)
-        o, lse = K.attn_fwd_generic(qkv, geo.key_mask, B, S, nh, geo.hd, geo.windows[i], scale, drop=ad)
-    # projection + RoPE in one kernel; the q third also takes the softmax's scale * log2(e) before its one bf16 rounding, so the
-    # attention kernels exponentiate the MFMA's scores as they come (prescaled=True everywhere below)
-    elif geo.cu is not None:  # unpadded batch: packed rows, per-token rotary tables
-        qkv = K.qkv_linear_rope(xn, Wqkv_b, cos, sin, S, geo.per_batch_pos, q_scale=K.SOFTMAX_Q_SCALE)
-        o, lse = K.attn_fwd_varlen(qkv, geo.cu, B, geo.max_s, nh, geo.windows[i], scale, prescaled=True, drop=ad)
+        qkv = K.linear_fwd(xn, wb[1])
+        K.rope_apply_generic_(qkv, cos, sin, geo.B, geo.S, geo.nh, geo.hd, geo.per_batch_pos)
     else:
-        qkv = K.qkv_linear_rope(xn, Wqkv_b, cos, sin, S, geo.per_batch_pos, q_scale=K.SOFTMAX_Q_SCALE)
-        o, lse = K.attn_fwd(qkv, geo.key_mask, B, S, nh, geo.windows[i], scale, prescaled=True, drop=ad)
-        if geo.attn_out is not None and len(geo.attn_out) == i:  # output_attentions (not again when a checkpointed layer is recomputed)
-            geo.attn_out.append(K.attn_probs(qkv, lse, geo.key_mask, B, S, nh, geo.windows[i], scale, prescaled=True))
+        # projection + RoPE in one kernel; the q third also takes the softmax's scale * log2(e) before its one bf16 rounding, so the
+        # attention kernels exponentiate the MFMA's scores as they come (prescaled=True everywhere behind it)
+        qkv = K.qkv_linear_rope(xn, wb[1], cos, sin, geo.S, geo.per_batch_pos, q_scale=K.SOFTMAX_Q_SCALE)
+    return xn, mean_a, rstd_a, qkv
+
+
+def _pre_attn_backward(geo: _Geometry, i: int, dqkv: Tensor, g32_of, acts, wb, Wqkv_t, need_x: bool, n_an: bool, n_qkv: bool, lora_grads):
+    """Backward of _pre_attn_forward: dqkv and the residual stream's own fp32 gradient -> (dWqkv, Wqkv's adapter gradients, dw_an, the
+    fp32 gradient of x or None), and the handoff to the node below.  g32_of() gives that incoming gradient; it is called once, behind the
+    weight gradient's launches, and only when something goes upstream (need_x) or into attn_norm's weight - the row node scatters its
+    block's gradient into zeros there, no sooner and not where the chain ends.  Nothing is handed up when nothing is returned."""
+    x, xn, mean_a, rstd_a = acts
+    dWqkv = K.linear_wgrad(dqkv, xn) if n_qkv else None
+    l_qkv = lora_grads(0, dqkv, xn)
+    dw_an = g32 = None
+    if need_x or n_an:  # (else: everything below this layer is frozen, the chain ends here; layer 0 has no attn_norm, n_an is False)
+        g32 = g32_of()
+        dxn = K.linear_dgrad(dqkv, wb[1], Wqkv_t)
+        if i == 0:
+            g32, _ = K.add_f32(g32, dxn, want_bf16=False)
+            _hand_upstream(geo, g32, None)
+        else:
+            g32, g16, dw_an = K.layernorm_bwd(dxn, x, wb[0], mean_a, rstd_a, g32, True)
+            _hand_upstream(geo, g32, g16)
+    return dWqkv, l_qkv, dw_an, g32
+
+
+def _post_attn_forward(geo: _Geometry, i: int, o: Tensor, x: Tensor, wb, want_stats: bool):
+    """The part of a layer behind attention, on every row or on a block of rows (o the attention output, x the residual rows):
+    -> x_out = x_mid + GeGLU(mlp_norm(x_mid) Wi^T) Wo2^T with x_mid = x + o Wo^T, and (x_mid, xn2, mean_m, rstd_m, h, g) for the backward."""
+    Wo_b, w_mn, Wi_b, Wo2_b, Wi_geglu, fused_train = wb[2:]
+    ad = _attn_drop(geo, i)
     if ad is not None:  # out_drop: Wo writes fp32 t, then x_mid = x + Z o t
         x_mid = K.dropout_f32(K.linear_fwd_f32(o, Wo_b), ad[0], ad[1], i, K.SITE_ATTN_OUT, geo.S, geo.cu, resid=x)
     else:
         x_mid = K.linear_fwd(o, Wo_b, resid=x)
     _, xn2, mean_m, rstd_m = K.layernorm_fwd(x_mid, w_mn, geo.eps, False, True, want_stats)
-    if len(wb) > 6 and wb[6] is not None:  # forward-only call: Wi and GeGLU in one kernel, h and g never exist (bit-identical a)
-        h, g = None, K.gemm_geglu(xn2, wb[6])
-    elif len(wb) > 7 and wb[7]:  # training step, fused pair: Wi_b has interleaved rows and the GEMM stores h' (interleaved columns) and g
+    if Wi_geglu is not None:  # forward-only call: Wi and GeGLU in one kernel, h and g never exist (bit-identical a)
+        h, g = None, K.gemm_geglu(xn2, Wi_geglu)
+    elif fused_train:  # training step, fused pair: Wi_b has interleaved rows and the GEMM stores h' (interleaved columns) and g
         h, g = K.linear_geglu_fwd(xn2, Wi_b)
     else:
         h = K.linear_fwd(xn2, Wi_b)
@@ -304,7 +385,61 @@ def _layer_forward(geo: _Geometry, i: int, x: Tensor, wb, want_stats: bool):
         else:
             g = K.geglu_fwd(h)
     x_out = K.linear_fwd(g, Wo2_b, resid=x_mid)
-    return x_out, (x, xn, mean_a, rstd_a, qkv, o, lse, x_mid, xn2, mean_m, rstd_m, h, g)
+    return x_out, (x_mid, xn2, mean_m, rstd_m, h, g)
+
+
+def _post_attn_backward(geo: _Geometry, i: int, live: list, o: Tensor, wb, wt, need, lora_grads):
+    """Backward of _post_attn_forward.  live = [the output's fp32 gradient, its bf16 twin, x_mid, xn2, mean_m, rstd_m, h, g], a list
+    this function empties: the caller keeps no reference of its own (an argument would stay alive on its stack for the whole call), so
+    each tensor is released where its last reader has run.  o is read, not taken (attention's backward reads it next).
+    -> (the fp32 gradient of x, updated in place; do = the gradient of o; dWo, dw_mn, dWi, dWo2 - None where not needed -; the adapter
+    gradients of Wo, Wi, Wo2)."""
+    gx32, gx16, x_mid, xn2, mean_m, rstd_m, h, g = live
+    live.clear()
+    Wo_b, w_mn, Wi_b, Wo2_b = wb[2:6]
+    _, Wo_t, Wi_t, Wo2_t = wt
+    n_o, n_i, n_o2 = need
+    # ---- MLP branch: x_out = x_mid + g Wo2^T
+    fused = wb[7]  # h is h' (interleaved columns): the Wo2 dgrad's store phase turns dg into the canonical dh
+    dg = None if fused else K.linear_dgrad(gx16, Wo2_b, Wo2_t)
+    dWo2 = K.linear_wgrad(gx16, g) if n_o2 else None
+    l_o2 = lora_grads(3, gx16, g)
+    if fused:
+        dh = K.linear_dgrad_geglu_bwd(gx16, Wo2_t, h)
+    elif geo.drop is not None and geo.drop.mlp:
+        dh = K.geglu_bwd_dropout(dg, h, geo.drop.mlp, geo.drop.seed, i, geo.S, geo.cu)
+    else:
+        dh = K.geglu_bwd(dg, h)
+    del dg, g
+    dxn2 = K.linear_dgrad(dh, Wi_b, Wi_t)
+    dWi = K.linear_wgrad(dh, xn2) if n_i else None
+    l_i = lora_grads(2, dh, xn2)
+    del dh, h, xn2
+    gx32, gx16, dw_mn = K.layernorm_bwd(dxn2, x_mid, w_mn, mean_m, rstd_m, gx32, True)
+    del dxn2, x_mid
+    # ---- attention branch: x_mid = x + o Wo^T  (with attention dropout: x + Z o (o Wo^T))
+    ad = _attn_drop(geo, i)
+    gt16 = gx16 if ad is None else K.dropout_f32(gx32, ad[0], ad[1], i, K.SITE_ATTN_OUT, geo.S, geo.cu, bf16_only=True)
+    do = K.linear_dgrad(gt16, Wo_b, Wo_t)
+    dWo = K.linear_wgrad(gt16, o) if n_o else None
+    l_o = lora_grads(1, gt16, o)
+    return gx32, do, dWo, dw_mn, dWi, dWo2, l_o, l_i, l_o2
+
+
+def _layer_forward(geo: _Geometry, i: int, x: Tensor, wb, want_stats: bool):
+    """One encoder layer on [T, H] rows: -> (x_out, activations needed by its backward)."""
+    xn, mean_a, rstd_a, qkv = _pre_attn_forward(geo, i, x, wb, want_stats)
+    B, S, nh, scale, ad = geo.B, geo.S, geo.nh, geo.hd ** -0.5, _attn_drop(geo, i)
+    if geo.hd != 64:
+        o, lse = K.attn_fwd_generic(qkv, geo.key_mask, B, S, nh, geo.hd, geo.windows[i], scale, drop=ad)
+    elif geo.cu is not None:  # unpadded batch: packed rows, per-token rotary tables
+        o, lse = K.attn_fwd_varlen(qkv, geo.cu, B, geo.max_s, nh, geo.windows[i], scale, prescaled=True, drop=ad)
+    else:
+        o, lse = K.attn_fwd(qkv, geo.key_mask, B, S, nh, geo.windows[i], scale, prescaled=True, drop=ad)
+        if geo.attn_out is not None and len(geo.attn_out) == i:  # output_attentions (not again when a checkpointed layer is recomputed)
+            geo.attn_out.append(K.attn_probs(qkv, lse, geo.key_mask, B, S, nh, geo.windows[i], scale, prescaled=True))
+    x_out, post = _post_attn_forward(geo, i, o, x, wb, want_stats)
+    return x_out, (x, xn, mean_a, rstd_a, qkv, o, lse, *post)
 
 
 def _attn_backward(geo: _Geometry, i: int, qkv: Tensor, o: Tensor, do: Tensor, lse: Tensor, ad: Optional[tuple]) -> Tensor:
@@ -329,33 +464,14 @@ class _EncoderLayerFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, geo: _Geometry, i: int, x: Tensor, *weights: Tensor):
-        it = iter(weights)
-        w_an = None if i == 0 else _f32(next(it))
-        Wqkv, Wo, w_mn, Wi, Wo2 = next(it), next(it), _f32(next(it)), next(it), next(it)
-        # low-rank adapters (cm3p_amd.lora): (A, B, s) per projection in the order Wqkv, Wo, Wi, Wo2; their tensors follow the weights
-        spec = geo.lora[i] if geo.lora is not None else (None,) * 4
-        adapters = [None if sc is None else (next(it).detach(), next(it).detach(), sc) for sc in spec]
-        # forward-only and a shape of the ring kernel: the Wi GEMM stores gelu(h) * g itself (CM3P_GEGLU_FUSED=0: the two-kernel path)
-        fuse_geglu = (not geo.save) and _geglu_fwd_fused(geo.drop, x.shape[0], Wi)
-        # (training: the casts of every layer were made in one launch at the top of the stack, _run_stack; adapted weights: their merged
-        # copies bf16(W + s B A) were made there on every kind of call)
-        pre = geo.wcast if geo.wcast is not None else {}
-        pairs = [pre.get(id(w)) or _bf16_weight_pair(w, geo.save) if not (fuse_geglu and w is Wi) else (None, None) for w in (Wqkv, Wo, Wi, Wo2)]
-        # training step, fused pair (_run_stack decided; CM3P_GEGLU_FUSED=0: the two-kernel path): this Wi's copy has interleaved rows
-        fused_train = geo.save and id(Wi) in geo.fused_mlp
-        Wi_geglu = None
-        if fuse_geglu:
-            Wi_geglu = geo.wcast_geglu[id(Wi)] if adapters[2] is not None else _bf16_weight_cached(Wi, True)
-        wb = (w_an, pairs[0][0], pairs[1][0], w_mn, pairs[2][0], pairs[3][0], Wi_geglu, fused_train)
+        wb, wt, adapters = _layer_operands(geo, i, weights, x.shape[0])
         x_out, acts = _layer_forward(geo, i, x, wb, geo.save)
         if geo.save:
             # gradient checkpointing (ref: supports_gradient_checkpointing, TF GradientCheckpointingLayer): keep only the
             # layer input; its activations are recomputed by the same kernels (bit-identical) in the backward pass
             ctx.saved = (x,) if geo.checkpoint else acts
-            ctx.geo, ctx.i, ctx.wb = geo, i, wb
-            ctx.wt = tuple(p[1] for p in pairs)  # W^T copies for the input-gradient GEMMs
+            ctx.geo, ctx.i, ctx.wb, ctx.wt, ctx.lora = geo, i, wb, wt, adapters
             ctx.wdtypes = [w.dtype for w in weights]
-            ctx.lora = adapters
         return x_out
 
     @staticmethod
@@ -366,11 +482,8 @@ class _EncoderLayerFn(torch.autograd.Function):
         LayerNorm backward rounds LN'(dy) first and the sum again; the single rounding is the more accurate of the two)."""
         geo, i = ctx.geo, ctx.i
         need = ctx.needs_input_grad  # (geo, i, x, *weights)
-        need_w = list(need[3:])
-        if i == 0:
-            need_w.insert(0, False)  # (no attn_norm in layer 0)
         assert not any(a is not None for a in ctx.lora)  # (refused before the forward ran: CM3PEncoder._bf16_stream)
-        n_an, n_qkv, n_o, n_mn, n_i, n_o2 = need_w
+        (n_an, n_qkv, n_o, n_mn, n_i, n_o2), _ = _backward_needs(i, need[3:], ctx.lora)
         g = _take_bf16_from_downstream(geo, dy)
         if geo.checkpoint:
             _, acts = _layer_forward(geo, i, ctx.saved[0], ctx.wb, True)
@@ -409,8 +522,7 @@ class _EncoderLayerFn(torch.autograd.Function):
             _, g, dw_an = K.layernorm_bwd(dxn, x, w_an, mean_a, rstd_a, g, False, bf16_only=True)
             _hand_upstream(geo, g, g)
         # (else: everything below this layer is frozen: the chain ends here)
-        grads = [dWqkv, dWo, dw_mn, dWi, dWo2] if i == 0 else [dw_an, dWqkv, dWo, dw_mn, dWi, dWo2]
-        out = [(gw if gw.dtype == dt else gw.to(dt)) if (nd and gw is not None) else None for gw, dt, nd in zip(grads, ctx.wdtypes, need[3:])]
+        out = _weight_grads(i, dw_an, [dWqkv, dWo, dw_mn, dWi, dWo2], ctx.wdtypes, need[3:])
         return (None, None, g if need[2] else None, *out)
 
     @staticmethod
@@ -419,79 +531,20 @@ class _EncoderLayerFn(torch.autograd.Function):
             return _EncoderLayerFn._backward_bf16(ctx, dy)
         geo, i = ctx.geo, ctx.i
         need = ctx.needs_input_grad  # (geo, i, x, *weights, *adapter tensors)
-        n_base = 5 if i == 0 else 6
-        need_w = list(need[3:3 + n_base])
-        if i == 0:
-            need_w.insert(0, False)  # (no attn_norm in layer 0)
-        n_an, n_qkv, n_o, n_mn, n_i, n_o2 = need_w
-        # adapter gradients (dA, dB) of projection p from the operands its weight-gradient GEMM reads; () when it carries no adapter
-        need_l, lora = iter(need[3 + n_base:]), ctx.lora
-        want_l = [None if a is None else (next(need_l), next(need_l)) for a in lora]
-
-        def lora_grads(p: int, dy_p: Tensor, x_p: Tensor):
-            if lora[p] is None:
-                return ()
-            if not any(want_l[p]):
-                return (None, None)
-            dA, dB = K.lora_grad(x_p, dy_p, *lora[p])
-            return (dA if want_l[p][0] else None, dB if want_l[p][1] else None)
-
-        gx32, gx16 = _take_from_downstream(geo, dy)
-        if geo.checkpoint:
-            _, acts = _layer_forward(geo, i, ctx.saved[0], ctx.wb, True)
-        else:
-            acts = ctx.saved
-        x, xn, mean_a, rstd_a, qkv, o, lse, x_mid, xn2, mean_m, rstd_m, h, g = acts
+        (n_an, n_qkv, n_o, n_mn, n_i, n_o2), lora_grads = _backward_needs(i, need[3:], ctx.lora)
+        live = list(_take_from_downstream(geo, dy))
+        acts = _layer_forward(geo, i, ctx.saved[0], ctx.wb, True)[1] if geo.checkpoint else ctx.saved
+        x, xn, mean_a, rstd_a, qkv, o, lse = acts[:7]
+        live += acts[7:]
         del acts
-        ctx_wb = ctx.wb
-        w_an, Wqkv_b, Wo_b, w_mn, Wi_b, Wo2_b = ctx_wb[:6]
-        Wqkv_t, Wo_t, Wi_t, Wo2_t = ctx.wt
+        wb, wt = ctx.wb, ctx.wt
         ctx.saved = ctx.wb = ctx.wt = None  # release activations as we go
-        # ---- MLP branch: x_out = x_mid + g Wo2^T
-        fused = len(ctx_wb) > 7 and ctx_wb[7]  # h is h' (interleaved columns): the Wo2 dgrad's store phase turns dg into the canonical dh
-        dg = None if fused else K.linear_dgrad(gx16, Wo2_b, Wo2_t)
-        dWo2 = K.linear_wgrad(gx16, g) if n_o2 else None
-        l_o2 = lora_grads(3, gx16, g)
-        if fused:
-            dh = K.linear_dgrad_geglu_bwd(gx16, Wo2_t, h)
-        elif geo.drop is not None and geo.drop.mlp:
-            dh = K.geglu_bwd_dropout(dg, h, geo.drop.mlp, geo.drop.seed, i, geo.S, geo.cu)
-        else:
-            dh = K.geglu_bwd(dg, h)
-        del dg, g
-        dxn2 = K.linear_dgrad(dh, Wi_b, Wi_t)
-        dWi = K.linear_wgrad(dh, xn2) if n_i else None
-        l_i = lora_grads(2, dh, xn2)
-        del dh, h, xn2
-        gx32, gx16, dw_mn = K.layernorm_bwd(dxn2, x_mid, w_mn, mean_m, rstd_m, gx32, True)
-        del dxn2, x_mid
-        # ---- attention branch: x_mid = x + o Wo^T  (with attention dropout: x + Z o (o Wo^T))
-        ad = (geo.drop.attn, geo.drop.seed, i) if geo.drop is not None and geo.drop.attn else None
-        gt16 = gx16 if ad is None else K.dropout_f32(gx32, ad[0], ad[1], i, K.SITE_ATTN_OUT, geo.S, geo.cu, bf16_only=True)
-        do = K.linear_dgrad(gt16, Wo_b, Wo_t)
-        dWo = K.linear_wgrad(gt16, o) if n_o else None
-        l_o = lora_grads(1, gt16, o)
-        del gt16
-        dqkv = _attn_backward(geo, i, qkv, o, do, lse, ad)
+        gx32, do, dWo, dw_mn, dWi, dWo2, l_o, l_i, l_o2 = _post_attn_backward(geo, i, live, o, wb, wt, (n_o, n_i, n_o2), lora_grads)
+        dqkv = _attn_backward(geo, i, qkv, o, do, lse, _attn_drop(geo, i))
         del do, o, qkv
-        dWqkv = K.linear_wgrad(dqkv, xn) if n_qkv else None
-        l_qkv = lora_grads(0, dqkv, xn)
-        if i == 0:
-            dw_an = None
-            if need[2]:
-                dxn = K.linear_dgrad(dqkv, Wqkv_b, Wqkv_t)
-                gx32, _ = K.add_f32(gx32, dxn, want_bf16=False)
-            _hand_upstream(geo, gx32, None)
-        elif need[2] or n_an:
-            dxn = K.linear_dgrad(dqkv, Wqkv_b, Wqkv_t)
-            gx32, gx16, dw_an = K.layernorm_bwd(dxn, x, w_an, mean_a, rstd_a, gx32, True)
-            _hand_upstream(geo, gx32, gx16)
-        else:  # everything below this layer is frozen: the chain ends here
-            dw_an = None
-        grads = [dWqkv, dWo, dw_mn, dWi, dWo2] if i == 0 else [dw_an, dWqkv, dWo, dw_mn, dWi, dWo2]
-        grads += [*l_qkv, *l_o, *l_i, *l_o2]
-        out = [(gw if gw.dtype == dt else gw.to(dt)) if (nd and gw is not None) else None for gw, dt, nd in zip(grads, ctx.wdtypes, need[3:])]
-        return (None, None, gx32 if need[2] else None, *out)
+        dWqkv, l_qkv, dw_an, gx = _pre_attn_backward(geo, i, dqkv, lambda: gx32, (x, xn, mean_a, rstd_a), wb, wt[0], need[2], n_an, n_qkv, lora_grads)
+        out = _weight_grads(i, dw_an, [dWqkv, dWo, dw_mn, dWi, dWo2, *l_qkv, *l_o, *l_i, *l_o2], ctx.wdtypes, need[3:])
+        return (None, None, gx if need[2] else None, *out)
 
 
 class _FinalNormFn(torch.autograd.Function):
@@ -548,202 +601,81 @@ class _TakeRowsFn(torch.autograd.Function):
         return K.scatter_rows(dy.contiguous(), ctx.idx, ctx.rows), None
 
 
-def _row_block_forward(geo: "_Geometry", o_p: Tensor, x_rows: Tensor, Wo_b: Tensor, w_mn: Tensor, Wi_b: Tensor, Wo2_b: Tensor):
-    """The part of a layer behind attention on a block of rows (_ClsLastLayerFn, _RowsLastLayerFn): o_p the attention output and x_rows
-    the residual rows of the block, both filled up with zero rows -> x_out = x_mid + GeGLU(mlp_norm(x_mid) Wi^T) Wo2^T with
-    x_mid = x_rows + o_p Wo^T, and what the backward reads."""
-    x_mid = K.linear_fwd(o_p, Wo_b, resid=x_rows)
-    _, xn2, mean_m, rstd_m = K.layernorm_fwd(x_mid, w_mn, geo.eps, False, True, geo.save)
-    h = K.linear_fwd(xn2, Wi_b)
-    g = K.geglu_fwd(h)
-    x_out = K.linear_fwd(g, Wo2_b, resid=x_mid)
-    return x_out, (x_mid, xn2, mean_m, rstd_m, h, g)
+class _RowSel:
+    """The query rows of the last layer's row node (_LastLayerRowsFn), and what differs between its two kinds as data: idx int64 [n] -
+    the rows in the numbering of the stack's row axis (the packed rows on unpadded execution) -, n their count, attn_fwd / attn_bwd the
+    attention pair with q, the arguments that describe the queries to it, and pad_rows(n, H, I), the rows the block is filled up to."""
+
+    __slots__ = ("idx", "n", "q", "attn_fwd", "attn_bwd", "pad_rows")
+
+    def __init__(self, idx: Tensor, q: tuple, attn_fwd, attn_bwd, pad_rows):
+        self.idx, self.n, self.q, self.attn_fwd, self.attn_bwd, self.pad_rows = idx, idx.numel(), q, attn_fwd, attn_bwd, pad_rows
+
+    @classmethod
+    def listed(cls, idx: Tensor, qcu: Tensor, qmax: int) -> "_RowSel":
+        """A validated list (CM3PEncoder.forward's last_layer_rows): qcu int32 [sequences + 1] its split by sequence, qmax the largest
+        per-sequence count; attention for the listed queries on the matrix cores (csrc/attention_qrows.hip), the block filled up to
+        K.row_block_rows."""
+        return cls(idx, (idx.to(torch.int32), qcu, int(qmax)), K.attn_qrows_fwd, K.attn_qrows_bwd, K.row_block_rows)
+
+    @classmethod
+    def first_rows(cls, qidx: Tensor) -> "_RowSel":
+        """Row 0 of every sequence (cls_only_last_layer; qidx: their row numbers): one query per (sequence, head)
+        (csrc/attention_row.hip), the block filled up to a multiple of 8."""
+        return cls(qidx, (), K.attn_row_fwd, K.attn_row_bwd, lambda n, H, I: (n + 7) // 8 * 8)
 
 
-def _row_block_backward(gx32: Tensor, gx16: Tensor, acts, w_mn: Tensor, wb, wt, need):
-    """Backward of _row_block_forward: the block's output gradient (fp32 and its bf16 twin, not yet filled up) -> the gradient of
-    x_rows (fp32, filled up), do = the gradient of o_p, and the weight gradients dWo, dw_mn, dWi, dWo2 (None where not needed)."""
-    o_p, x_mid, xn2, mean_m, rstd_m, h, g = acts
-    (Wo_b, Wi_b, Wo2_b), (Wo_t, Wi_t, Wo2_t), (n_o, n_i, n_o2) = wb, wt, need
-    Bp = x_mid.shape[0]
-    gx32, gx16 = _zero_padded_rows(gx32, Bp), _zero_padded_rows(gx16, Bp)
-    dg = K.linear_dgrad(gx16, Wo2_b, Wo2_t)
-    dWo2 = K.linear_wgrad(gx16, g) if n_o2 else None
-    dh = K.geglu_bwd(dg, h)
-    del dg, g, h
-    dxn2 = K.linear_dgrad(dh, Wi_b, Wi_t)
-    dWi = K.linear_wgrad(dh, xn2) if n_i else None
-    del dh, xn2
-    gx32, gx16, dw_mn = K.layernorm_bwd(dxn2, x_mid, w_mn, mean_m, rstd_m, gx32, True)
-    del dxn2, x_mid
-    do = K.linear_dgrad(gx16, Wo_b, Wo_t)
-    dWo = K.linear_wgrad(gx16, o_p) if n_o else None
-    return gx32, do, dWo, dw_mn, dWi, dWo2
+class _LastLayerRowsFn(torch.autograd.Function):
+    """The LAST encoder layer where only some rows are consumed - row 0 of every sequence (CM3PEncoder.cls_only_last_layer) or a list
+    (CM3PEncoder.forward's last_layer_rows: the CLS rows and the rows that carry a masked-LM label); `sel` says which and carries what
+    the two differ in: x [T, H] + the layer's weights -> the layer's output on those rows alone, [n, H] (fp32; bf16 on the bf16 residual
+    stream of a forward-only call).
 
-
-class _ClsLastLayerFn(torch.autograd.Function):
-    """The LAST encoder layer where only row 0 of every sequence is consumed (CM3PEncoder.cls_only_last_layer): x [T, H] + the layer's
-    weights -> the layer's output on the query rows alone, [Bn, H] (fp32; bf16 on the bf16 residual stream of a forward-only call).
-
-    attn_norm and the Wqkv + RoPE projection run on all T rows - K and V come from every token - with the kernels of _layer_forward;
-    attention is one query per (sequence, head) (K.attn_row_fwd); the residual rows of the queries are gathered (`qidx`: their row
-    numbers) and Wo + residual, mlp_norm, Wi, GeGLU and Wo2 + residual run on Bn rows (zero rows fill the block up to a multiple of 8).
-    The same function of the same weights as _EncoderLayerFn followed by a row selection.  The backward mirrors it: the row block's
-    chain, K.attn_row_bwd (dqkv in the full layout, its q third zero off the query rows) into the Wqkv weight and input gradients
+    attn_norm and the Wqkv + RoPE projection run on all T rows - K and V come from every token - (_pre_attn_forward); attention runs
+    for the query rows against all keys (sel.attn_fwd); the residual rows of the queries are gathered and Wo + residual, mlp_norm, Wi,
+    GeGLU and Wo2 + residual run on n rows (_post_attn_forward; zero rows fill the block up to sel.pad_rows).  The same function of the
+    same weights as _EncoderLayerFn followed by a row selection.  The backward mirrors it: the block's chain, sel.attn_bwd (dqkv in the
+    full layout, its q third zero off the query rows, dk / dv summed over the queries) into the Wqkv weight and input gradients
     unchanged, and a residual-stream gradient that is zero except on the query rows into attn_norm's backward.
     No dropout, no adapters on this layer, no checkpointing, fp32 stream when a backward is recorded: _run_stack sends every other
     call through the full layer."""
 
     @staticmethod
-    def forward(ctx, geo: _Geometry, i: int, x: Tensor, qidx: Tensor, *weights: Tensor):
-        it = iter(weights)
-        w_an = None if i == 0 else _f32(next(it))
-        Wqkv, Wo, w_mn, Wi, Wo2 = next(it), next(it), _f32(next(it)), next(it), next(it)
-        pre = geo.wcast if geo.wcast is not None else {}
-        pairs = [pre.get(id(w)) or _bf16_weight_pair(w, geo.save) for w in (Wqkv, Wo, Wi, Wo2)]
-        Wqkv_b, Wo_b, Wi_b, Wo2_b = (p[0] for p in pairs)
-        B, S, nh = geo.B, geo.S, geo.nh
-        scale = geo.hd ** -0.5
-        cos, sin = geo.rope[i]
-        if i == 0:
-            xn, mean_a, rstd_a = (x if x.dtype == torch.bfloat16 else K.cast_bf16(x)), None, None
-        else:
-            _, xn, mean_a, rstd_a = K.layernorm_fwd(x, w_an, geo.eps, False, True, geo.save)
-        qkv = K.qkv_linear_rope(xn, Wqkv_b, cos, sin, S, geo.per_batch_pos, q_scale=K.SOFTMAX_Q_SCALE)
-        o, lse = K.attn_row_fwd(qkv, geo.key_mask, geo.cu, B, geo.max_s if geo.cu is not None else S, nh, geo.windows[i], scale, prescaled=True)
-        Bp = (B + 7) // 8 * 8
-        o_p = _zero_padded_rows(o, Bp)
-        x_out, (x_mid, xn2, mean_m, rstd_m, h, g) = _row_block_forward(geo, o_p, _zero_padded_rows(K.gather_rows(x, qidx), Bp), Wo_b, w_mn, Wi_b, Wo2_b)
-        if geo.save:
-            ctx.saved = (x, xn, mean_a, rstd_a, qkv, o, o_p, lse, x_mid, xn2, mean_m, rstd_m, h, g)
-            ctx.geo, ctx.i, ctx.qidx = geo, i, qidx
-            ctx.wn, ctx.wb, ctx.wt = (w_an, w_mn), (Wqkv_b, Wo_b, Wi_b, Wo2_b), tuple(p[1] for p in pairs)
-            ctx.wdtypes = [w.dtype for w in weights]
-        return x_out[:B] if Bp != B else x_out
-
-    @staticmethod
-    def backward(ctx, dy: Tensor):
-        geo, i, qidx = ctx.geo, ctx.i, ctx.qidx
-        need = ctx.needs_input_grad  # (geo, i, x, qidx, *weights)
-        need_w = list(need[4:])
-        if i == 0:
-            need_w.insert(0, False)  # (no attn_norm in layer 0)
-        n_an, n_qkv, n_o, n_mn, n_i, n_o2 = need_w
-        B, S, nh, scale = geo.B, geo.S, geo.nh, geo.hd ** -0.5
-        gx32, gx16 = _take_from_downstream(geo, dy)
-        x, xn, mean_a, rstd_a, qkv, o, o_p, lse, x_mid, xn2, mean_m, rstd_m, h, g = ctx.saved
-        (w_an, w_mn), (Wqkv_b, Wo_b, Wi_b, Wo2_b), (Wqkv_t, Wo_t, Wi_t, Wo2_t) = ctx.wn, ctx.wb, ctx.wt
-        ctx.saved = ctx.wb = ctx.wt = None
-        # ---- the row block: x_out = x_mid + g Wo2^T, x_mid = x[qidx] + o Wo^T
-        gx32, do, dWo, dw_mn, dWi, dWo2 = _row_block_backward(gx32, gx16, (o_p, x_mid, xn2, mean_m, rstd_m, h, g), w_mn, (Wo_b, Wi_b, Wo2_b),
-                                                              (Wo_t, Wi_t, Wo2_t), (n_o, n_i, n_o2))
-        del o_p, x_mid, xn2, h, g
-        # ---- all rows: dqkv in the full layout (q third zero off the query rows), then what every layer does with it
-        dqkv = K.attn_row_bwd(qkv, o, do[:B].contiguous(), lse, geo.key_mask, geo.cu, B, geo.max_s if geo.cu is not None else S, nh, geo.windows[i], scale,
-                              geo.rope[i], geo.per_batch_pos, prescaled=True)
-        del do, o, qkv
-        dWqkv = K.linear_wgrad(dqkv, xn) if n_qkv else None
-        dw_an = None
-        gfull = None
-        if need[2] or n_an:
-            # the residual stream's own gradient: zero except on the query rows
-            gfull = K.scatter_rows(gx32[:B].contiguous(), qidx, x.shape[0])
-            dxn = K.linear_dgrad(dqkv, Wqkv_b, Wqkv_t)
-            if i == 0:
-                gfull, _ = K.add_f32(gfull, dxn, want_bf16=False)
-                _hand_upstream(geo, gfull, None)
-            else:
-                gfull, g16, dw_an = K.layernorm_bwd(dxn, x, w_an, mean_a, rstd_a, gfull, True)
-                _hand_upstream(geo, gfull, g16)
-        grads = [dWqkv, dWo, dw_mn, dWi, dWo2] if i == 0 else [dw_an, dWqkv, dWo, dw_mn, dWi, dWo2]
-        out = [(gw if gw.dtype == dt else gw.to(dt)) if (nd and gw is not None) else None for gw, dt, nd in zip(grads, ctx.wdtypes, need[4:])]
-        return (None, None, gfull if need[2] else None, None, *out)
-
-
-class _RowSel:
-    """A validated list of last-layer rows (CM3PEncoder.forward's last_layer_rows): idx int64 [n] - the rows in the numbering of the
-    stack's row axis (the packed rows on unpadded execution) -, rows the same as int32, qcu int32 [sequences + 1] their split by
-    sequence, qmax the largest per-sequence count."""
-
-    __slots__ = ("idx", "rows", "qcu", "qmax", "n")
-
-    def __init__(self, idx: Tensor, qcu: Tensor, qmax: int):
-        self.idx, self.rows, self.qcu, self.qmax, self.n = idx, idx.to(torch.int32), qcu, int(qmax), idx.numel()
-
-
-class _RowsLastLayerFn(torch.autograd.Function):
-    """The LAST encoder layer where only a list of rows is consumed (CM3PEncoder.forward's last_layer_rows: the CLS rows and the rows
-    that carry a masked-LM label): x [T, H] + the layer's weights -> the layer's output on the listed rows alone, [n, H].
-
-    _ClsLastLayerFn's chain with a list in place of row 0: attn_norm and the Wqkv + RoPE projection on all T rows, attention for the
-    listed queries against all keys on the matrix cores (K.attn_qrows_fwd), then the row block (_row_block_forward) on n rows, filled
-    up with zero rows to K.row_block_rows.  The backward mirrors _ClsLastLayerFn.backward with K.attn_qrows_bwd (dqkv in the full
-    layout, its q third zero off the list, dk / dv summed over the listed queries).  The same limits: _run_stack sends every other call
-    through the full layer."""
-
-    @staticmethod
     def forward(ctx, geo: _Geometry, i: int, x: Tensor, sel: _RowSel, *weights: Tensor):
-        it = iter(weights)
-        w_an = None if i == 0 else _f32(next(it))
-        Wqkv, Wo, w_mn, Wi, Wo2 = next(it), next(it), _f32(next(it)), next(it), next(it)
-        pre = geo.wcast if geo.wcast is not None else {}
-        pairs = [pre.get(id(w)) or _bf16_weight_pair(w, geo.save) for w in (Wqkv, Wo, Wi, Wo2)]
-        Wqkv_b, Wo_b, Wi_b, Wo2_b = (p[0] for p in pairs)
-        B, S, nh = geo.B, geo.S, geo.nh
-        scale = geo.hd ** -0.5
-        cos, sin = geo.rope[i]
-        if i == 0:
-            xn, mean_a, rstd_a = (x if x.dtype == torch.bfloat16 else K.cast_bf16(x)), None, None
-        else:
-            _, xn, mean_a, rstd_a = K.layernorm_fwd(x, w_an, geo.eps, False, True, geo.save)
-        qkv = K.qkv_linear_rope(xn, Wqkv_b, cos, sin, S, geo.per_batch_pos, q_scale=K.SOFTMAX_Q_SCALE)
-        o, lse = K.attn_qrows_fwd(qkv, sel.rows, sel.qcu, sel.qmax, geo.key_mask, geo.cu, B, geo.max_s if geo.cu is not None else S, nh, geo.windows[i],
-                                  scale, prescaled=True)
-        n = sel.n
-        Np = K.row_block_rows(n, geo.H, geo.I)
+        wb, wt, adapters = _layer_operands(geo, i, weights, None)
+        xn, mean_a, rstd_a, qkv = _pre_attn_forward(geo, i, x, wb, geo.save)
+        o, lse = sel.attn_fwd(qkv, *sel.q, geo.key_mask, geo.cu, geo.B, geo.max_s, geo.nh, geo.windows[i], geo.hd ** -0.5, prescaled=True)
+        n, Np = sel.n, sel.pad_rows(sel.n, geo.H, geo.I)
         o_p = _zero_padded_rows(o, Np)
-        x_out, (x_mid, xn2, mean_m, rstd_m, h, g) = _row_block_forward(geo, o_p, _zero_padded_rows(K.gather_rows(x, sel.idx), Np), Wo_b, w_mn, Wi_b, Wo2_b)
+        x_out, post = _post_attn_forward(geo, i, o_p, _zero_padded_rows(K.gather_rows(x, sel.idx), Np), wb, geo.save)
         if geo.save:
-            ctx.saved = (x, xn, mean_a, rstd_a, qkv, o, o_p, lse, x_mid, xn2, mean_m, rstd_m, h, g)
-            ctx.geo, ctx.i, ctx.sel = geo, i, sel
-            ctx.wn, ctx.wb, ctx.wt = (w_an, w_mn), (Wqkv_b, Wo_b, Wi_b, Wo2_b), tuple(p[1] for p in pairs)
+            ctx.saved = (x, xn, mean_a, rstd_a, qkv, o, lse, o_p, *post)
+            ctx.geo, ctx.i, ctx.sel, ctx.wb, ctx.wt, ctx.lora = geo, i, sel, wb, wt, adapters
             ctx.wdtypes = [w.dtype for w in weights]
         return x_out[:n] if Np != n else x_out
 
     @staticmethod
     def backward(ctx, dy: Tensor):
-        geo, i, sel = ctx.geo, ctx.i, ctx.sel
+        geo, i, sel, n = ctx.geo, ctx.i, ctx.sel, ctx.sel.n
         need = ctx.needs_input_grad  # (geo, i, x, sel, *weights)
-        need_w = list(need[4:])
-        if i == 0:
-            need_w.insert(0, False)  # (no attn_norm in layer 0)
-        n_an, n_qkv, n_o, n_mn, n_i, n_o2 = need_w
-        B, S, nh, scale, n = geo.B, geo.S, geo.nh, geo.hd ** -0.5, sel.n
+        (n_an, n_qkv, n_o, n_mn, n_i, n_o2), lora_grads = _backward_needs(i, need[4:], ctx.lora)
         gx32, gx16 = _take_from_downstream(geo, dy)
-        x, xn, mean_a, rstd_a, qkv, o, o_p, lse, x_mid, xn2, mean_m, rstd_m, h, g = ctx.saved
-        (w_an, w_mn), (Wqkv_b, Wo_b, Wi_b, Wo2_b), (Wqkv_t, Wo_t, Wi_t, Wo2_t) = ctx.wn, ctx.wb, ctx.wt
+        x, xn, mean_a, rstd_a, qkv, o, lse, o_p = ctx.saved[:8]
+        # ---- the row block: x_out = x_mid + g Wo2^T, x_mid = x[idx] + o Wo^T; its output gradient is filled up with zero rows like it
+        live = [_zero_padded_rows(gx32, o_p.shape[0]), _zero_padded_rows(gx16, o_p.shape[0]), *ctx.saved[8:]]
+        del gx32, gx16
+        wb, wt = ctx.wb, ctx.wt
         ctx.saved = ctx.wb = ctx.wt = None
-        gx32, do, dWo, dw_mn, dWi, dWo2 = _row_block_backward(gx32, gx16, (o_p, x_mid, xn2, mean_m, rstd_m, h, g), w_mn, (Wo_b, Wi_b, Wo2_b),
-                                                              (Wo_t, Wi_t, Wo2_t), (n_o, n_i, n_o2))
-        del o_p, x_mid, xn2, h, g
-        # ---- all rows: dqkv in the full layout (q third zero off the list), then what every layer does with it
-        dqkv = K.attn_qrows_bwd(qkv, o, do[:n].contiguous(), lse, sel.rows, sel.qcu, sel.qmax, geo.key_mask, geo.cu, B, geo.max_s if geo.cu is not None else S,
-                                nh, geo.windows[i], scale, geo.rope[i], geo.per_batch_pos, prescaled=True)
+        gblock, do, dWo, dw_mn, dWi, dWo2 = _post_attn_backward(geo, i, live, o_p, wb, wt, (n_o, n_i, n_o2), lora_grads)[:6]
+        del o_p
+        # ---- all rows: dqkv in the full layout (q third zero off the query rows), then what every layer does with it; the residual
+        # stream's own gradient is zero except on the query rows
+        dqkv = sel.attn_bwd(qkv, o, do[:n].contiguous(), lse, *sel.q, geo.key_mask, geo.cu, geo.B, geo.max_s, geo.nh, geo.windows[i], geo.hd ** -0.5,
+                            geo.rope[i], geo.per_batch_pos, prescaled=True)
         del do, o, qkv
-        dWqkv = K.linear_wgrad(dqkv, xn) if n_qkv else None
-        dw_an = None
-        gfull = None
-        if need[2] or n_an:
-            gfull = K.scatter_rows(gx32[:n].contiguous(), sel.idx, x.shape[0])  # the residual stream's own gradient: zero off the list
-            dxn = K.linear_dgrad(dqkv, Wqkv_b, Wqkv_t)
-            if i == 0:
-                gfull, _ = K.add_f32(gfull, dxn, want_bf16=False)
-                _hand_upstream(geo, gfull, None)
-            else:
-                gfull, g16, dw_an = K.layernorm_bwd(dxn, x, w_an, mean_a, rstd_a, gfull, True)
-                _hand_upstream(geo, gfull, g16)
-        grads = [dWqkv, dWo, dw_mn, dWi, dWo2] if i == 0 else [dw_an, dWqkv, dWo, dw_mn, dWi, dWo2]
-        out = [(gw if gw.dtype == dt else gw.to(dt)) if (nd and gw is not None) else None for gw, dt, nd in zip(grads, ctx.wdtypes, need[4:])]
+        dWqkv, _, dw_an, gfull = _pre_attn_backward(geo, i, dqkv, lambda: K.scatter_rows(gblock[:n].contiguous(), sel.idx, x.shape[0]),
+                                                    (x, xn, mean_a, rstd_a), wb, wt[0], need[2], n_an, n_qkv, lora_grads)
+        out = _weight_grads(i, dw_an, [dWqkv, dWo, dw_mn, dWi, dWo2], ctx.wdtypes, need[4:])
         return (None, None, gfull if need[2] else None, None, *out)
 
 
@@ -912,7 +844,7 @@ class CM3PEncoder(nn.Module):
         caller-packed rows; with `output_hidden_states` the last entry is that short tensor and the others are unchanged.  The rows are
         the same function of the same weights as row 0 of the full result: attn_norm and the Wqkv + RoPE projection still run on
         every token (K and V come from all of them), attention is one query per (sequence, head) (csrc/attention_row.hip), and
-        Wo, mlp_norm, the GeGLU MLP and the final norm run on B rows (_ClsLastLayerFn).  Supported on that route: the fp32 stream
+        Wo, mlp_norm, the GeGLU MLP and the final norm run on B rows (_LastLayerRowsFn on _RowSel.first_rows).  Supported on that route: the fp32 stream
         (forward-only and training), the bf16 stream of forward-only calls, padded execution, `unpad`, caller-packed rows.
         Where the row route has no form - an active dropout plan, adapters on the last layer, the bf16 stream of a training step,
         head_dim other than 64, gradient checkpointing - the full layer runs and its row 0 is taken, so the output SHAPE does not
@@ -1018,7 +950,7 @@ class CM3PEncoder(nn.Module):
         (n, H), in list order; with `output_hidden_states` the last entry is that short tensor.  The same function of the same
         weights as those rows of the full result: attn_norm and the Wqkv + RoPE projection still run on every token, attention
         runs for the listed queries against all keys (csrc/attention_qrows.hip), Wo, mlp_norm, the GeGLU MLP and the final norm on n
-        rows (_RowsLastLayerFn).  ONE host read validates the list (ascending, in range, with `unpad` every row on a valid token)
+        rows (_LastLayerRowsFn on _RowSel.listed).  ONE host read validates the list (ascending, in range, with `unpad` every row on a valid token)
         and gives the grid its size; a wrong list raises ValueError.  Where the row route has no form - the cases cls_only_last_layer
         names - the full layer runs and the rows are gathered: the output shape does not depend on the route.  Wins over
         cls_only_last_layer when both are given.  `output_attentions` with it raises NotImplementedError."""
@@ -1157,8 +1089,7 @@ class CM3PEncoder(nn.Module):
         # cls_only_last_layer: the row route where it has a form, else the full layer and a row selection behind the final norm
         has_route = geo.hd == 64 and plan is None and not geo.checkpoint and not (bf16 and geo.save) \
             and (lora is None or all(a is None for a in lora[geo.L - 1]))
-        row_route = cls_only and has_route
-        rows_route = sel is not None and sel.n > 0 and has_route  # (an empty list: the full layer and an empty gather)
+        row_route = (cls_only or (sel is not None and sel.n > 0)) and has_route  # (an empty list: the full layer and an empty gather)
         if geo.save and _eval_weights:
             invalidate_weight_cache()  # a backward will follow, so an optimizer will: no copy made before this step may outlive it
         geo.wcast = None
@@ -1203,7 +1134,7 @@ class CM3PEncoder(nn.Module):
                     cast = {id(w) for w in elig}
                     # (not the last layer on the row route: its Wi is a plain GEMM on B rows and reads the canonical copy)
                     geo.fused_mlp = frozenset(id(ws[-2]) for n, ws in enumerate(weights)
-                                              if id(ws[-2]) in cast and id(ws[-1]) in cast and not ((row_route or rows_route) and n == geo.L - 1))
+                                              if id(ws[-2]) in cast and id(ws[-1]) in cast and not (row_route and n == geo.L - 1))
                 plain = [w for w in elig if id(w) not in adapted]
                 pairs = K.cast_bf16_with_transpose_many([w.detach() for w in plain], [id(w) in geo.fused_mlp for w in plain])
                 geo.wcast = {id(w): pair for w, pair in zip(plain, pairs)}
@@ -1211,9 +1142,8 @@ class CM3PEncoder(nn.Module):
                 pairs = K.lora_merge_cast_many([(w.detach(), A.detach().contiguous(), B.detach().contiguous(), s, id(w) in geo.fused_mlp) for w, A, B, s in merged])
                 geo.wcast.update({id(e[0]): pair for e, pair in zip(merged, pairs)})
         n_seq = geo.B - (1 if (packed is not None and packed[4] != packed[3]) else 0)  # (without the pseudo-sequence of alignment rows)
-        qidx = None
-        if cls_only:  # the row of query position 0 of every sequence
-            qidx = geo.cu[:-1].to(torch.int64) if geo.cu is not None else torch.arange(B, device=dev, dtype=torch.int64) * S
+        if cls_only:  # the row of query position 0 of every sequence (never together with a list: the explicit argument wins)
+            sel = _RowSel.first_rows(geo.cu[:-1].to(torch.int64) if geo.cu is not None else torch.arange(B, device=dev, dtype=torch.int64) * S)
         geo.handoff = None
         geo.attn_out = [] if output_attentions else None
         # output_hidden_states: the stack's input and every layer's output (TF:...modeling_modernbert.py:457-470), detached
@@ -1222,26 +1152,20 @@ class CM3PEncoder(nn.Module):
         for i in range(geo.L):
             extra = () if lora is None else tuple(t for a in lora[i] if a is not None for t in a[:2])
             if row_route and i == geo.L - 1:
-                x = _ClsLastLayerFn.apply(geo, i, x, qidx, *weights[i])  # [geo.B, H]
-            elif rows_route and i == geo.L - 1:
-                x = _RowsLastLayerFn.apply(geo, i, x, sel, *weights[i])  # [n, H]
+                x = _LastLayerRowsFn.apply(geo, i, x, sel, *weights[i])  # [sel.n, H]
             else:
                 x = _EncoderLayerFn.apply(geo, i, x, *weights[i], *extra)
             if hiddens is not None:
-                if cls_only and i == geo.L - 1:
-                    hiddens.append((x.detach() if row_route else K.gather_rows(x.detach(), qidx))[:n_seq])
-                elif sel is not None and i == geo.L - 1:
-                    hiddens.append(x.detach() if rows_route else K.gather_rows(x.detach(), sel.idx))
+                if sel is not None and i == geo.L - 1:  # the last layer's output on the query rows alone, whichever route made it
+                    last = x.detach() if row_route else K.gather_rows(x.detach(), sel.idx)
+                    hiddens.append(last[:n_seq] if cls_only else last)
                 else:
                     hiddens.append(x.detach())
         y = _FinalNormFn.apply(geo, x, self.final_norm.weight)
-        if sel is not None and not rows_route:
+        if sel is not None and not row_route:
             y = _TakeRowsFn.apply(y, sel.idx)
-        if cls_only:
-            if not row_route:
-                y = _TakeRowsFn.apply(y, qidx)
-            if n_seq != y.shape[0]:
-                y = y[:n_seq]
+        if cls_only and n_seq != y.shape[0]:
+            y = y[:n_seq]
         attns = tuple(geo.attn_out) if geo.attn_out is not None else None
         geo.attn_out = None
         return y, hiddens, attns
@@ -1315,7 +1239,7 @@ class CM3PEncoder(nn.Module):
             n_seq = B if cu is None else cu.numel() - 1
         n = rows.numel()
         if n == 0:
-            return _RowSel(rows.contiguous(), torch.zeros(n_seq + 1, dtype=torch.int32, device=rows.device), 0)
+            return _RowSel.listed(rows.contiguous(), torch.zeros(n_seq + 1, dtype=torch.int32, device=rows.device), 0)
         rows = rows.contiguous()
         limit = B * S if (cu is None or repack) else total
         ok = (rows[0] >= 0) & (rows[-1] < limit)
@@ -1339,7 +1263,7 @@ class CM3PEncoder(nn.Module):
             raise ValueError(f"last_layer_rows must be strictly ascending row numbers in [0, {limit})" + (" on valid (unmasked) tokens" if repack else ""))
         qcu = torch.zeros(n_seq + 1, dtype=torch.int32, device=rows.device)
         qcu[1:] = torch.cumsum(counts, 0)
-        return _RowSel(idx.contiguous(), qcu, qmax)
+        return _RowSel.listed(idx.contiguous(), qcu, qmax)
 
     @staticmethod
     def _plan_unpadded(mask: Tensor, position_ids: Optional[Tensor]):

@@ -1,5 +1,5 @@
 """`cls_only_last_layer` (CM3PEncoder / the model classes / the fused ModernBERT tower), `-m gpu`: with the switch on, the last encoder
-layer and the final norm run on the pooled CLS row of every sequence only (cm3p_amd/encoder.py _ClsLastLayerFn on csrc/attention_row.hip).
+layer and the final norm run on the pooled CLS row of every sequence only (cm3p_amd/encoder.py _LastLayerRowsFn on csrc/attention_row.hip).
 
   - the reference-made fixtures whose towers pool by CLS, within the class bounds of tests/test_model_gpu.py (FIX_TOL);
   - a 3-layer head-64 tower whose LAST layer is a sliding one, padded / `unpad` / caller-packed, against the float64 oracle on the CPU;

@@ -1,6 +1,6 @@
 """`labelled_rows_last_layer` (CM3PModel, CM3PForMaskedLM, FusedModernBertForMaskedLM) and `last_layer_rows` (CM3PEncoder.forward), `-m gpu`:
 the beatmap tower's last layer, its final norm and the MLM head run on the rows a training step consumes - the CLS row of every
-sequence and the labelled positions - (cm3p_amd/encoder.py _RowsLastLayerFn on csrc/attention_qrows.hip).
+sequence and the labelled positions - (cm3p_amd/encoder.py _LastLayerRowsFn on csrc/attention_qrows.hip).
 
   - the d64 geometry of tests/golden/cases.py with `cls_embed` towers and the decoder head, weights of tests/golden/weights_d64.safetensors,
     B = 4, S = 128, right-padded rows, ~15 % labels (a sequence without a label, a labelled CLS, a label on a row's last valid token):
