@@ -159,6 +159,16 @@ MLM_LOSS_SIGNATURES = {
 MLM_LOSS_ABI_VERSION = 1
 _RETURNS_INT64.update({"cm3p_mlm_lse_workspace_bytes", "cm3p_mlm_dlogits_workspace_bytes"})
 
+# name -> argtypes of include/ext/predict/cm3p_mlm_topk.h (masked-LM top-k predictions without the logits tensor), one to one; a table
+# and a version of its own as above.
+MLM_TOPK_SIGNATURES = {
+    "cm3p_mlm_topk_abi_version": [],
+    "cm3p_mlm_topk": [_P, _P, _P, _L, _L, _L, _L, _I, _P, _P, _P, _P, _L, _P],
+    "cm3p_mlm_topk_workspace_bytes": [_L, _L, _I],
+}
+MLM_TOPK_ABI_VERSION = 1
+_RETURNS_INT64.add("cm3p_mlm_topk_workspace_bytes")
+
 _lib = None
 
 
@@ -178,7 +188,7 @@ def load() -> ctypes.CDLL:
         )
     lib = ctypes.CDLL(LIB_PATH)
     for name, argtypes in (*SIGNATURES.items(), *EXT_SIGNATURES.items(), *ROW_SIGNATURES.items(), *QROWS_SIGNATURES.items(),
-                           *MLM_LOSS_SIGNATURES.items()):
+                           *MLM_LOSS_SIGNATURES.items(), *MLM_TOPK_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if a declared symbol is not exported
         fn.argtypes = argtypes
         fn.restype = c_int64 if name in _RETURNS_INT64 else c_int
@@ -192,6 +202,8 @@ def load() -> ctypes.CDLL:
         raise Cm3pHipError(f"cm3p_attn_qrows.h ABI mismatch: library {lib.cm3p_attn_qrows_abi_version()} vs binding {ATTN_QROWS_ABI_VERSION}; rebuild")
     if lib.cm3p_mlm_loss_abi_version() != MLM_LOSS_ABI_VERSION:
         raise Cm3pHipError(f"ext/cm3p_mlm_loss.h ABI mismatch: library {lib.cm3p_mlm_loss_abi_version()} vs binding {MLM_LOSS_ABI_VERSION}; rebuild")
+    if lib.cm3p_mlm_topk_abi_version() != MLM_TOPK_ABI_VERSION:
+        raise Cm3pHipError(f"ext/predict/cm3p_mlm_topk.h ABI mismatch: library {lib.cm3p_mlm_topk_abi_version()} vs binding {MLM_TOPK_ABI_VERSION}; rebuild")
     if lib.cm3p_build_ablation_flags() != 0 and os.environ.get("CM3P_ALLOW_ABLATED_LIB") != "1":
         raise Cm3pHipError(
             f"{LIB_PATH} was built with timing-only ablation macros (mask {lib.cm3p_build_ablation_flags():#x}): its results are wrong by "

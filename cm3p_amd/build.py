@@ -10,7 +10,7 @@ import subprocess
 import sys
 
 CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
-SOURCES = ["norm.hip", "elementwise.hip", "gemm.hip", "gemm256.hip", "gemm8p.hip", "attention.hip", "attention_fwd.hip", "attention_bwd_fused.hip", "attention_generic.hip", "attention_hd.hip", "head.hip", "conv.hip", "muon.hip", "lora.hip", "attention_row.hip", "attention_qrows.hip", "mlm_loss.hip"]
+SOURCES = ["norm.hip", "elementwise.hip", "gemm.hip", "gemm256.hip", "gemm8p.hip", "attention.hip", "attention_fwd.hip", "attention_bwd_fused.hip", "attention_generic.hip", "attention_hd.hip", "head.hip", "conv.hip", "muon.hip", "lora.hip", "attention_row.hip", "attention_qrows.hip", "mlm_loss.hip", "mlm_topk.hip"]
 LIB = os.path.join(CSRC, "libcm3p_hip.so")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function", "-Wno-inline-asm"]
 # hand-scheduled kernels: SLP-packing adjacent f32 multiplies into v_pk_mul_f32 costs register shuffles (v_mov / v_perm /
@@ -30,7 +30,7 @@ def build(force: bool = False, verbose: bool = True, check_isa: bool = True, aud
     inline-asm MFMAs: isa_check.CHECKS) are re-checked every time they are recompiled; a failed check fails the build, so a
     different hipcc or flag set cannot silently ship a kernel whose waits no longer cover its loads."""
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    headers = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "attn_common.h"), os.path.join(CSRC, "dropout_rng.h"), os.path.join(CSRC, "attention_hd.h"), os.path.join(CSRC, "..", "..", "include", "cm3p_hip.h"), os.path.join(CSRC, "..", "..", "include", "cm3p_lora.h"), os.path.join(CSRC, "..", "..", "include", "cm3p_attn_row.h"), os.path.join(CSRC, "..", "..", "include", "cm3p_attn_qrows.h"), os.path.join(CSRC, "..", "..", "include", "ext", "cm3p_mlm_loss.h")]
+    headers = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "attn_common.h"), os.path.join(CSRC, "dropout_rng.h"), os.path.join(CSRC, "attention_hd.h"), os.path.join(CSRC, "..", "..", "include", "cm3p_hip.h"), os.path.join(CSRC, "..", "..", "include", "cm3p_lora.h"), os.path.join(CSRC, "..", "..", "include", "cm3p_attn_row.h"), os.path.join(CSRC, "..", "..", "include", "cm3p_attn_qrows.h"), os.path.join(CSRC, "..", "..", "include", "ext", "cm3p_mlm_loss.h"), os.path.join(CSRC, "mlm_tile.h"), os.path.join(CSRC, "..", "..", "include", "ext", "predict", "cm3p_mlm_topk.h")]
     objs = []
     procs = []
     for src in SOURCES:
@@ -83,7 +83,7 @@ AUDIT_LIB = os.path.join(CSRC, "libcm3p_hip_audit.so")
 
 def build_audit(force: bool = False, verbose: bool = True) -> str:
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    headers = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "attn_common.h"), os.path.join(CSRC, "dropout_rng.h"), os.path.join(CSRC, "attention_hd.h"), os.path.join(CSRC, "..", "..", "include", "cm3p_hip.h"), os.path.join(CSRC, "..", "..", "include", "cm3p_lora.h"), os.path.join(CSRC, "..", "..", "include", "cm3p_attn_row.h"), os.path.join(CSRC, "..", "..", "include", "cm3p_attn_qrows.h"), os.path.join(CSRC, "..", "..", "include", "ext", "cm3p_mlm_loss.h")]
+    headers = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "attn_common.h"), os.path.join(CSRC, "dropout_rng.h"), os.path.join(CSRC, "attention_hd.h"), os.path.join(CSRC, "..", "..", "include", "cm3p_hip.h"), os.path.join(CSRC, "..", "..", "include", "cm3p_lora.h"), os.path.join(CSRC, "..", "..", "include", "cm3p_attn_row.h"), os.path.join(CSRC, "..", "..", "include", "cm3p_attn_qrows.h"), os.path.join(CSRC, "..", "..", "include", "ext", "cm3p_mlm_loss.h"), os.path.join(CSRC, "mlm_tile.h"), os.path.join(CSRC, "..", "..", "include", "ext", "predict", "cm3p_mlm_topk.h")]
     objs, procs = [], []
     for src in SOURCES:
         s = os.path.join(CSRC, src)

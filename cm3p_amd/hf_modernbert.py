@@ -362,6 +362,25 @@ class FusedModernBertForMaskedLM(ModernBertPreTrainedModel):
             return tuple(v for v in (loss, logits, out.hidden_states, out.attentions) if v is not None)
         return MaskedLMOutput(loss=loss, logits=logits, hidden_states=out.hidden_states, attentions=out.attentions)
 
+    @torch.no_grad()
+    def predict_tokens(self, input_ids: Tensor, attention_mask: Optional[Tensor] = None, position_ids: Optional[Tensor] = None, positions=None,
+                       k: int = 5):
+        """Fill-mask without the (B, S, vocab) logits: the k most likely tokens at the selected positions of a padded (B, S) batch, what
+        `forward(...).logits` followed by torch.topk there gives (13.2 GB of fp32 logits at 8 x 8192 tokens of a 50368-token vocabulary),
+        as `CM3PForMaskedLM.predict_tokens` -> MaskedTokenPredictions.  positions: a (B, S) mask (e.g. input_ids == mask_token_id), a
+        1-D int64 list of strictly ascending global rows b * S + s, or None for every unmasked position."""
+        from .modeling_cm3p import _check_prediction_call, _empty_predictions, _predict_rows, _prediction_rows
+
+        k = _check_prediction_call(self, k)
+        if self.model.cls_only_last_layer:
+            raise ValueError("FusedModernBertForMaskedLM with cls_only_last_layer: the MLM head reads every row of the last layer; switch it off")
+        rows = _prediction_rows(positions, attention_mask, input_ids.shape[0], input_ids.shape[1], input_ids.device)
+        if rows.numel() == 0:
+            return _empty_predictions(k, input_ids.device)
+        out = self.model(input_ids=input_ids, attention_mask=attention_mask, position_ids=position_ids, output_attentions=False,
+                         output_hidden_states=False, return_dict=True, last_layer_rows=rows)
+        return _predict_rows(out.last_hidden_state, rows, self.head, self.decoder, self.config.norm_eps, k)
+
 
 # ----------------------------------------------------------------------------------------------- fuse / unfuse
 def _share_parameters(src: nn.Module, dst: nn.Module) -> None:

@@ -1043,6 +1043,27 @@ def mlm_dlogits(y: Tensor, w: Tensor, bias: Optional[Tensor], cols: int, target:
     return dl, colsum
 
 
+def mlm_topk(y: Tensor, w: Tensor, bias: Optional[Tensor], cols: int, k: int):
+    """The decoder GEMM and a top-k in one, without the logits (include/ext/predict/cm3p_mlm_topk.h): y [T, H] bf16, w [Vp, H] bf16,
+    bias [Vp] fp32 or None, cols = V <= Vp, 1 <= k <= 8 -> (idx int32 [T, k], val fp32 [T, k], lse fp32 [T]): every row's k best columns
+    below V by (logit descending, column ascending), their logits (index -1 and -inf past V when V < k) and log sum exp of the row."""
+    T, H = y.shape
+    Vp = w.shape[0]
+    if not 1 <= int(k) <= 8:
+        raise ValueError(f"mlm_topk: k must lie in 1..8, got {k}")
+    k = int(k)
+    idx = torch.empty((T, k), dtype=torch.int32, device=y.device)
+    val = torch.empty((T, k), dtype=torch.float32, device=y.device)
+    lse = torch.empty((T,), dtype=torch.float32, device=y.device)
+    if T == 0:  # (nothing to launch; an empty tensor has no address to hand over)
+        return idx, val, lse
+    nbytes = query("cm3p_mlm_topk_workspace_bytes", T, Vp, k)
+    ws = torch.empty((max(nbytes, 16),), dtype=torch.uint8, device=y.device)
+    call("cm3p_mlm_topk", ptr(y, torch.bfloat16), ptr(w, torch.bfloat16), ptr(bias, torch.float32) if bias is not None else None, T, H, cols, Vp, k,
+         ptr(idx, torch.int32), ptr(val, torch.float32), ptr(lse, torch.float32), ptr(ws), ws.numel(), stream(), tag="cm3p_mlm_topk", work=2.0 * T * Vp * H)
+    return idx, val, lse
+
+
 def inv_valid_count(target: Tensor, ignore_index: int) -> Tensor:
     out = torch.empty((1,), dtype=torch.float32, device=target.device)
     call("cm3p_inv_valid_count", ptr(target, torch.int64), target.numel(), ignore_index, ptr(out), stream())

@@ -69,6 +69,18 @@ class CM3POutput(ModelOutput):
         return tuple(self[k] if k not in nested else getattr(self, k).to_tuple() for k in self.keys())
 
 
+@dataclass
+class MaskedTokenPredictions(ModelOutput):
+    """What `predict_tokens` returns: for each of the n selected positions the k most likely tokens, best first (equal logits: the
+    lower token id first, torch.argmax's rule).  When the vocabulary has fewer than k tokens the slots past it hold id -1, logit and
+    logprob -inf."""
+
+    rows: Optional[Tensor] = None       # int64 [n]: global row b * S + s of the (B, S) batch, ascending
+    token_ids: Optional[Tensor] = None  # int64 [n, k]
+    logits: Optional[Tensor] = None     # fp32 [n, k]
+    logprobs: Optional[Tensor] = None   # fp32 [n, k] = logits - log sum exp of the row's logits
+
+
 # ----------------------------------------------------------------------------------------------- autograd nodes
 class _PoolFn(torch.autograd.Function):
     """cls: h[:, 0]; else masked mean in fp32 (ref:cm3p/modeling_cm3p.py:385-396,631-642).  The gradient is written in h's dtype
@@ -439,6 +451,72 @@ class _MLMHeadLogitFreeLossFn(torch.autograd.Function):
             dW = K.linear_wgrad(dlb, y[r0:r1])
             dWdec = dW if dWdec is None else K.add_f32(dWdec, dW)[0]
         return (*_mlm_head_backward_below(ctx.pack, ctx.meta, ctx.needs_input_grad[0], dy, dWdec, colsum), None, None, None)
+
+
+# ----------------------------------------------------------------------------------------------- predictions without the logits
+def _mlm_topk_chunk_rows(Vp: int, k: int) -> int:
+    """Rows per cm3p_mlm_topk call: the largest multiple of 128 whose workspace - (k + 1) pairs of 8 bytes per (128-column tile, row) -
+    stays within MLM_LOGIT_FREE_CHUNK_BYTES, at least 128 (_mlm_logit_free_chunk_rows' rule)."""
+    return max(128, MLM_LOGIT_FREE_CHUNK_BYTES // (-(-Vp // 128) * (k + 1) * 8) // 128 * 128)
+
+
+def _prediction_rows(positions, attention_mask: Optional[Tensor], B: int, S: int, device) -> Tensor:
+    """`positions` of predict_tokens -> int64 [n] ascending global rows on `device`.  A (B, S) mask (nonzero = predict) and None (every
+    position whose attention_mask is nonzero) cost one host read for the count; a list is taken as it is (the encoder validates it)."""
+    if positions is None:
+        if attention_mask is None:
+            return torch.arange(B * S, dtype=torch.int64, device=device)
+        positions = attention_mask.reshape(B, S)
+    if not torch.is_tensor(positions):
+        positions = torch.as_tensor(positions, dtype=torch.int64)
+    positions = positions.to(device)
+    if positions.dim() == 2:
+        if tuple(positions.shape) != (B, S):
+            raise ValueError(f"positions as a mask must have the inputs' shape ({B}, {S}), got {tuple(positions.shape)}")
+        return torch.nonzero(positions.reshape(-1) != 0).flatten()
+    if positions.dim() != 1 or positions.dtype != torch.int64:
+        raise ValueError("positions must be a (B, S) mask, a 1-D int64 list of strictly ascending global rows b * S + s, or None")
+    return positions.contiguous()
+
+
+def _empty_predictions(k: int, device) -> MaskedTokenPredictions:
+    z = torch.empty((0, k), dtype=torch.float32, device=device)
+    return MaskedTokenPredictions(rows=torch.empty((0,), dtype=torch.int64, device=device), token_ids=torch.empty((0, k), dtype=torch.int64, device=device),
+                                  logits=z, logprobs=z.clone())
+
+
+def _check_prediction_call(model, k: int) -> int:
+    if model.training:
+        raise ValueError("predict_tokens on a model in training mode: predictions have evaluation semantics (no dropout); call model.eval() first")
+    if not 1 <= int(k) <= 8:
+        raise ValueError(f"predict_tokens: k must lie in 1..8, got {k}")
+    return int(k)
+
+
+def _predict_rows(h: Tensor, rows: Tensor, head, decoder, eps: float, k: int) -> MaskedTokenPredictions:
+    """The MLM head's trunk on the n selected rows h [n, H], then cm3p_mlm_topk on chunks of them: no [n, vocab] tensor exists."""
+    pack, bp, _ = _mlm_head_trunk(h, head.dense.weight, head.dense.bias, head.norm.weight, decoder.weight, decoder.bias, eps)
+    Wdec_b, y, V = pack[2], pack[7], pack[10]
+    n = y.shape[0]
+    step = _mlm_topk_chunk_rows(Wdec_b.shape[0], k)
+    parts = [K.mlm_topk(y[r0:r0 + step], Wdec_b, bp, V, k) for r0 in range(0, n, step)]
+    idx, val, lse = (torch.cat(p) if len(parts) > 1 else p[0] for p in zip(*parts))
+    return MaskedTokenPredictions(rows=rows, token_ids=idx.to(torch.int64), logits=val, logprobs=val - lse[:, None])
+
+
+def masked_lm_accuracy(pred: MaskedTokenPredictions, labels: Tensor, ignore_index: int = -100) -> dict:
+    """The masked-LM accuracy counts of the reference's compute_metrics (ref:train.py:75-90) from `predict_tokens`' output instead of
+    the logits -> dict(total, correct, top5_correct) of int64 scalars on the device (no host read; add them up over the batches and
+    read once).  labels: the batch's (B, S) labels - the entries at pred.rows are taken - or the n labels of pred.rows themselves.
+    A row counts when its label differs from ignore_index; `correct`: its first id is the label; `top5_correct`: the label is among its
+    first min(5, k) ids (with fewer than 5 tokens in the vocabulary the slots past it hold -1 and match no label)."""
+    ids = pred.token_ids
+    lab = labels.to(ids.device).reshape(-1)
+    if lab.numel() != ids.shape[0]:
+        lab = lab[pred.rows]
+    live = lab != ignore_index
+    hit = (ids[:, :5] == lab[:, None]) & live[:, None]
+    return dict(total=live.sum(), correct=hit[:, 0].sum(), top5_correct=hit.any(dim=-1).sum())
 
 
 class _AddScaledFn(torch.autograd.Function):
@@ -1172,6 +1250,27 @@ class CM3PModel(CM3PPreTrainedModel):
                           metadata_embeds=metadata_embeds, beatmap_embeds=beatmap_embeds, logits=logits,
                           metadata_model_output=metadata_outputs, beatmap_model_output=beatmap_outputs)
 
+    @torch.no_grad()
+    def predict_tokens(self, input_ids: Tensor, input_features: Optional[Tensor] = None, attention_mask: Optional[Tensor] = None,
+                       position_ids: Optional[Tensor] = None, positions=None, k: int = 5) -> MaskedTokenPredictions:
+        """CM3PForMaskedLM.predict_tokens on this model's decoder head (`has_decoder_head`): the k most likely tokens at the selected
+        positions - `forward(...).logits` followed by torch.topk there - without the (B, S, vocab) logits.  Only the beatmap tower
+        runs, its last layer on the selected rows; `unpad_inputs` is honoured as in forward."""
+        k = _check_prediction_call(self, k)
+        if not self.config.has_decoder_head:
+            raise ValueError("Cannot return logits when the model is not configured with a decoder head.")
+        if self.beatmap_model.cls_only_last_layer:
+            raise ValueError("cls_only_last_layer with the MLM head (has_decoder_head / output_logits): the head reads every row of the beatmap "
+                             "tower's last layer; switch cls_only_last_layer off on the beatmap tower")
+        rows = _prediction_rows(positions, attention_mask, input_ids.shape[0], input_ids.shape[1], input_ids.device)
+        if rows.numel() == 0:
+            return _empty_predictions(k, input_ids.device)
+        if self.unpad_inputs is not None or getattr(self.config, "_attn_implementation", None) == "flash_attention_2":
+            self.beatmap_model.unpad_inputs = True if self.unpad_inputs is None else bool(self.unpad_inputs)
+        out = self.beatmap_model(input_ids=input_ids, input_features=input_features, attention_mask=attention_mask, position_ids=position_ids,
+                                 output_pooler=False, last_layer_rows=rows)
+        return _predict_rows(out.last_hidden_state, rows, self.head, self.decoder, self.config.beatmap_config.norm_eps, k)
+
 
 # ----------------------------------------------------------------------------------------------- stand-alone variants
 class CM3PMetadataModelWithProjection(CM3PPreTrainedModel):
@@ -1342,6 +1441,25 @@ class CM3PForMaskedLM(CM3PPreTrainedModel):
             lp = _MLMHeadFn.apply(*head_args)
         logits = lp[..., :V] if sparse else lp.view(Bq, Sq, -1)[..., :V]
         return MaskedLMOutput(loss=loss, logits=logits, hidden_states=out.hidden_states, attentions=out.attentions)
+
+    @torch.no_grad()
+    def predict_tokens(self, input_ids: Tensor, input_features: Optional[Tensor] = None, attention_mask: Optional[Tensor] = None,
+                       position_ids: Optional[Tensor] = None, positions=None, k: int = 5) -> MaskedTokenPredictions:
+        """The k most likely tokens at the selected positions of a padded (B, S) batch without the (B, S, vocab) logits: what
+        `forward(...).logits` followed by torch.topk at those positions gives (argmax for k = 1), from cm3p_mlm_topk.
+        positions: a (B, S) mask (nonzero = predict), a 1-D int64 list of strictly ascending global rows b * S + s, or None for every
+        position whose attention_mask is nonzero; with `unpad_inputs` every selected position must be an unmasked one.  The tower's
+        last layer, its final norm and the head run on the selected rows only (CM3PEncoder.forward's last_layer_rows).  An empty
+        selection returns empty tensors and launches nothing.  Evaluation semantics: a model in training mode raises ValueError."""
+        k = _check_prediction_call(self, k)
+        if self.beatmap_model.cls_only_last_layer:
+            raise ValueError("CM3PForMaskedLM with cls_only_last_layer: the MLM head reads every row of the last layer; switch it off")
+        rows = _prediction_rows(positions, attention_mask, input_ids.shape[0], input_ids.shape[1], input_ids.device)
+        if rows.numel() == 0:
+            return _empty_predictions(k, input_ids.device)
+        out = self.beatmap_model(input_ids=input_ids, input_features=input_features, attention_mask=attention_mask, position_ids=position_ids,
+                                 output_pooler=False, last_layer_rows=rows)
+        return _predict_rows(out.last_hidden_state, rows, self.head, self.decoder, self.config.norm_eps, k)
 
 
 class _AddBiasFn(torch.autograd.Function):
