@@ -24,9 +24,15 @@ Z the dropout factor keep / (1 - p) (1 without dropout), dP = dO V^T, delta = ro
   dk   the same with (...)^T |Q|.      Pre-scaled q: the products are taken with q' = bf16(q scale log2 e) and the store multiplies by
                                            the fp32 constant ln 2 (band_dkv_block's epilogue) - scale |q_ref| = ln 2 |q'| exactly, and one
                                            more fp32 rounding: floor.
-  fused dq  + 2 u scale |dS||K|        cm3p_attn_bwd_fused stores every 256-key block's partial dQ as bf16 (u |partial|) and adds the
-                                           blocks of a slab with a packed-bf16 add (u |sum|, include/cm3p_hip.h); both are below
-                                           u scale |dS||K| summed over the blocks.
+  fused dq  + G u scale |dS||K|        cm3p_attn_bwd_fused, G = 2 or 4 key blocks per slab (cm3p_attn_bwd_fused_slab_group).  Counted in
+                                           csrc/attention_bwd_fused.hip: every 256-key block's fp32 dQ^T accumulator is packed to bf16 ONCE
+                                           (post_hook C == 2 / 3, pack_bf16x2), whether it is then stored (position 0 of its group) or handed
+                                           to global_atomic_pk_add_bf16 as the operand (positions 1 .. G - 1): u |partial| each, together at
+                                           most u scale |dS||K| over all blocks.  Each of the G - 1 adds of a group rounds the running bf16 sum
+                                           once, and that sum is bounded by the sum of the |partials| so far, i.e. by the group's share of
+                                           scale |dS||K|: (G - 1) u scale |dS||K|.  The reduce sums the slabs in fp32 (floor).  G = 2 gives
+                                           the 2 u of the pair form.  tests/attention_fused_refs.py holds the table that runs G = 4, more
+                                           than one slab, and the inverse rotation of the epilogues.
 
 fp32 floors.  A score is a 64-term fp32 dot product (+ the reference point / -lse as initial accumulator, one fma for plain q): it
 is off by at most 66 U (A + |m|) <= 132 U Amax[q] in natural-log units, A = scale |q|.|k|, Amax its maximum over the row's visible
@@ -73,15 +79,19 @@ class Case:
     lens: Optional[tuple]  # valid lengths per sequence (right padding); None: B = 2 without a mask (tables A, B, G)
     pre: bool              # the device gets bf16(q * SOFTMAX_Q_SCALE) and q_prescaled = 1
     probe: bool = False    # q = k = 0, v = +-1 by the bits of the key index
+    holes: bool = False    # table F: the five-sequence mask with holes at window -1 (_key_mask)
+    nb: int = 0            # table F: the batch size of a case without a mask (0: 2)
 
     @property
     def name(self):
-        m = "nomask" if self.table != "C" and self.lens is None else ("holes" if self.table == "C" else "pad")
+        m = "holes" if (self.table == "C" or self.holes) else ("nomask" if self.lens is None else "pad")
         return f"{'P' if self.probe else ''}{self.table}-S{self.S}-w{self.window}-{m}-{'pre' if self.pre else 'plain'}"
 
     @property
     def B(self):
-        return 4 if self.table == "C" else (len(self.lens) if self.lens else 2)
+        if self.holes:
+            return 5
+        return 4 if self.table == "C" else (len(self.lens) if self.lens else (self.nb or 2))
 
 
 def _both(table, S, window, lens):
@@ -125,7 +135,21 @@ ALL_INSTANCES = ({"attn_fwd_kernel<1, true, true>", "attn_fwd_kernel<1, false, t
 
 # ================================================================================================ data
 @functools.lru_cache(maxsize=None)
-def _key_mask(table, S, window, lens):
+def _key_mask(table, S, window, lens, holes=False):
+    if holes:
+        # table C's patterns at window -1 for the fused backward's long case (S >= 768): holes everywhere; left AND right padding in one
+        # sequence; no valid key at all; one hole late in the sweep; only the keys of ONE 256-key block (the third) valid
+        g = torch.Generator().manual_seed(4100 + S)
+        m = torch.ones(5, S, dtype=torch.bool)
+        m[0] = torch.rand(S, generator=g) < 0.7
+        cut = 70 + int(torch.randint(0, 60, (1,), generator=g))
+        m[1, :cut] = False
+        m[1, cut + (S - cut) // 2:] = False
+        m[2] = False
+        m[3, S - 40] = False
+        m[4] = False
+        m[4, 512:768] = True
+        return m
     if table != "C":
         return None if lens is None else torch.arange(S)[None] < torch.tensor(lens)[:, None]
     g = torch.Generator().manual_seed(4100 + S)
@@ -144,19 +168,20 @@ def _key_mask(table, S, window, lens):
 
 def key_mask(case):
     """bool [B, S] (True = valid key) or None."""
-    return _key_mask(case.table, case.S, case.window, case.lens)
+    return _key_mask(case.table, case.S, case.window, case.lens, case.holes)
 
 
-def visible(case, km="own"):
-    """The header's rule: key_mask[b, kv] != 0 and (window < 0 or |q - kv| <= window).  bool [B, 1, S, S]."""
+def visible(case, km="own", rows=None):
+    """The header's rule: key_mask[b, kv] != 0 and (window < 0 or |q - kv| <= window).  bool [B, 1, S, S]; rows (a LongTensor of query
+    rows): [B, 1, len(rows), S], built without the S x S one."""
     km = key_mask(case) if isinstance(km, str) else km
     S = case.S
-    vis = torch.ones(case.B, 1, S, S, dtype=torch.bool)
+    qi = torch.arange(S) if rows is None else rows
+    vis = torch.ones(case.B, 1, len(qi), S, dtype=torch.bool)
     if km is not None:
         vis = vis & km[:, None, None, :]
     if case.window >= 0:
-        i = torch.arange(S)
-        vis = vis & ((i[:, None] - i[None, :]).abs() <= case.window)[None, None]
+        vis = vis & ((qi[:, None] - torch.arange(S)[None, :]).abs() <= case.window)[None, None]
     return vis
 
 
@@ -198,8 +223,8 @@ def bernoulli_keep(case, p, seed=5):
 
 
 # ================================================================================================ float64 reference and bounds
-def softmax64(case, x):
-    vis = visible(case)
+def softmax64(case, x, rows=None):
+    vis = visible(case, rows=rows)
     s = (x["q"] @ x["k"].transpose(-1, -2)) * SCALE
     dead = ~vis.any(-1)  # [B, 1, S]
     s = s.masked_fill(~vis, float("-inf"))
@@ -219,22 +244,39 @@ def _floors(case, x, vis, p, pz, dS, out, zmax):
 
 
 def _backward_bounds(x, p, dS, ds_floor, derr):
-    """-> bound_dq, bound_dk and the extra term of the fused backward's dq."""
+    """-> bound_dq, bound_dk and the UNIT of the fused backward's extra dq term, u scale |dS||K|: the term is G units (module docstring)."""
     t = 2.0 * U16 * dS.abs() + p * derr + ds_floor
     bq = SCALE * (t @ x["k"].abs()) * SECOND + FTZ
     bk = SCALE * (t.transpose(-1, -2) @ x["q"].abs()) * SECOND + FTZ
-    fused = 2.0 * U16 * SCALE * (dS.abs() @ x["k"].abs()) * SECOND
-    return bq, bk, fused
+    unit = U16 * SCALE * (dS.abs() @ x["k"].abs()) * SECOND
+    return bq, bk, unit
 
 
-def reference(case, keep=None, p_drop=0.0, x=None):
+def bound_fused_dq(ref, G=2):
+    """The dq bound of cm3p_attn_bwd_fused at G key blocks per slab (ref: what reference / conditioned return)."""
+    assert G in (2, 4)
+    return ref["bound"]["dq"] + float(G) * ref["fused_unit"]
+
+
+def _rows_of(x, rows):
+    """inputs(case) with q and dO cut to the query rows `rows` (k and v stay whole)."""
+    return dict(x, q=x["q"][:, :, rows], do=x["do"][:, rows])
+
+
+def reference(case, keep=None, p_drop=0.0, x=None, rows=None):
     """float64 autograd of softmax(scale q k^T + mask) v [with P o Z, Z = keep / (1 - p_drop)] and the componentwise bounds of the
     module docstring.  Dead rows: exact zeros, lse = -inf (the kernels store +inf).  x: inputs(case) with another dO (the packed
-    entry points have no padded query rows: their dO is zero)."""
+    entry points have no padded query rows: their dO is zero).
+    rows (LongTensor): the same for these query rows only - out, lse, dq, dead, nvis and their bounds are [.., len(rows), ..] and equal
+    the rows of the full reference; dk and dv (sums over ALL query rows) are not returned.  Nothing larger than [B, NH, len(rows), S]
+    is built (no dropout form)."""
     x = x or inputs(case)
+    if rows is not None:
+        assert keep is None
+        x = _rows_of(x, rows)
     q, k, v = (x[n].clone().requires_grad_(True) for n in "qkv")
     xx = dict(x, q=q, k=k, v=v)
-    vis, dead, s, p = softmax64(case, xx)
+    vis, dead, s, p = softmax64(case, xx, rows)
     zmax = 1.0 / (1.0 - p_drop)
     z = keep.double() * zmax if keep is not None else None
     pz = p * z if z is not None else p
@@ -252,20 +294,27 @@ def reference(case, keep=None, p_drop=0.0, x=None):
         b_out = (2.0 * U16 + 3.0 * e32) * pv * SECOND + FTZ
         b_dv = (2.0 * U16 * (pz.transpose(-1, -2) @ do.abs()) + 3.0 * ((e32 * pz).transpose(-1, -2) @ do.abs())) * SECOND + FTZ
         derr = (do.abs() * b_out).sum(-1, keepdim=True)
-        b_dq, b_dk, fused = _backward_bounds(x, p, dS, ds_floor, derr)
-    return dict(out=out, lse=lse, dq=q.grad, dk=k.grad, dv=v.grad, dead=dead.expand(-1, NH, -1).clone(), nvis=vis.sum(-1).expand(-1, NH, -1).clone(),
-                bound=dict(out=b_out, dq=b_dq, dk=b_dk, dv=b_dv), bound_fused_dq=b_dq + fused, e32=e32,
-                l2_rows=rel_l2_rows(vis) if keep is not None else None)
+        b_dq, b_dk, unit = _backward_bounds(x, p, dS, ds_floor, derr)
+    res = dict(out=out, lse=lse, dq=q.grad, dk=k.grad, dv=v.grad, dead=dead.expand(-1, NH, -1).clone(), nvis=vis.sum(-1).expand(-1, NH, -1).clone(),
+               bound=dict(out=b_out, dq=b_dq, dk=b_dk, dv=b_dv), bound_fused_dq=b_dq + 2.0 * unit, fused_unit=unit, e32=e32,
+               l2_rows=rel_l2_rows(vis) if keep is not None else None)
+    if rows is not None:
+        for nm in ("dk", "dv"):
+            del res[nm], res["bound"][nm]
+    return res
 
 
-def conditioned(case, out_got, keep=None, p_drop=0.0, x=None):
+def conditioned(case, out_got, keep=None, p_drop=0.0, x=None, rows=None):
     """dq and dk of the float64 backward that takes delta from the out the kernels STORED (what band_dq_block and the fused prep
     kernel do), and their bounds without the delta term: what is left is (1) and (2) of the module docstring and the floors.  A
     backward whose dq and dk do not use one and the same delta - the published one - fails this where the rounding of out matters
-    most: rows whose softmax is nearly one-hot (dS small next to the rounding of delta)."""
+    most: rows whose softmax is nearly one-hot (dS small next to the rounding of delta).  rows: as in reference (out_got: those rows; dq only)."""
     x = x or inputs(case)
+    if rows is not None:
+        assert keep is None
+        x = _rows_of(x, rows)
     with torch.no_grad():
-        vis, dead, s, p = softmax64(case, x)
+        vis, dead, s, p = softmax64(case, x, rows)
         zmax = 1.0 / (1.0 - p_drop)
         z = keep.double() * zmax if keep is not None else None
         do = heads(x["do"].double())
@@ -273,8 +322,12 @@ def conditioned(case, out_got, keep=None, p_drop=0.0, x=None):
         dP = do @ x["v"].transpose(-1, -2)
         dS = p * ((dP * z if z is not None else dP) - (do * out).sum(-1, keepdim=True))
         _, ds_floor = _floors(case, x, vis, p, p, dS, out, zmax)
-        b_dq, b_dk, fused = _backward_bounds(x, p, dS, ds_floor, 0.0)
-        return dict(dq=SCALE * (dS @ x["k"]), dk=SCALE * (dS.transpose(-1, -2) @ x["q"]), bound=dict(dq=b_dq, dk=b_dk), bound_fused_dq=b_dq + fused)
+        b_dq, b_dk, unit = _backward_bounds(x, p, dS, ds_floor, 0.0)
+        res = dict(dq=SCALE * (dS @ x["k"]), dk=SCALE * (dS.transpose(-1, -2) @ x["q"]), bound=dict(dq=b_dq, dk=b_dk), bound_fused_dq=b_dq + 2.0 * unit,
+                   fused_unit=unit)
+        if rows is not None:
+            del res["dk"], res["bound"]["dk"]
+        return res
 
 
 # ================================================================================================ the checks both test files run
@@ -304,10 +357,10 @@ def rel_l2_rows(vis):
     return dict(dq=(~one_key[..., 0]).expand(-1, NH, -1), dk=(~only_one_key_rows).expand(-1, NH, -1))
 
 
-def check_float64(ref, got, fused=False, quantities=("out", "lse", "dq", "dk", "dv")):
+def check_float64(ref, got, fused=False, quantities=("out", "lse", "dq", "dk", "dv"), G=2):
     """-> (measured: {quantity: worst error / bound, d*_rel_l2, lse_max_abs}, failures: [str]).  got: out, dq, dk, dv [B, NH, S, 64] and
     lse [B, NH, S] (any of `quantities`).  The relative L2 error of a gradient is taken over the whole tensor, or, against a dropout
-    reference, over rel_l2_rows."""
+    reference, over rel_l2_rows.  fused: dq within bound_fused_dq(ref, G)."""
     seen, fails = {}, []
     for nm in quantities:
         if nm == "lse":
@@ -318,7 +371,7 @@ def check_float64(ref, got, fused=False, quantities=("out", "lse", "dq", "dk", "
             if not bool((err <= LSE_ATOL + LSE_RTOL * b.abs()).all()):
                 fails.append(f"lse: max abs error {seen['lse_max_abs']:.3e} on live rows")
             continue
-        bound = ref["bound_fused_dq"] if (fused and nm == "dq") else ref["bound"][nm]
+        bound = bound_fused_dq(ref, G) if (fused and nm == "dq") else ref["bound"][nm]
         seen[nm], nbad = _ratio(got[nm], ref[nm], bound)
         if nbad:
             fails.append(f"{nm}: {nbad} elements outside the bound, worst error / bound = {seen[nm]:.3f}")
@@ -333,10 +386,12 @@ def check_float64(ref, got, fused=False, quantities=("out", "lse", "dq", "dk", "
     return seen, fails
 
 
-def check_conditioned(cond, got, fused=False):
+def check_conditioned(cond, got, fused=False, G=2):
     seen, fails = {}, []
     for nm in ("dq", "dk"):
-        bound = cond["bound_fused_dq"] if (fused and nm == "dq") else cond["bound"][nm]
+        if nm not in cond:  # (a row-subset reference has no dk)
+            continue
+        bound = bound_fused_dq(cond, G) if (fused and nm == "dq") else cond["bound"][nm]
         seen[f"{nm}_given_out"], nbad = _ratio(got[nm], cond[nm], bound)
         if nbad:
             fails.append(f"{nm} given the stored out: {nbad} elements outside the bound, worst error / bound = {seen[f'{nm}_given_out']:.3f}")
@@ -460,12 +515,42 @@ def all_dropped_rows(case, keep):
     return vis.any(-1).expand(-1, NH, -1) & ~(vis & keep).any(-1)
 
 
-def emulate(case, keep=None, p_drop=0.0, wrong=None, fused=False):
+WRONG_FUSED_SLABS = ("block_never_added", "last_partial_slab_dropped", "block_added_twice", "slab_of_the_other_head")
+
+
+def fused_dq_sum(parts, G, wrong=None):
+    """The fused backward's dQ from its per-256-key-block bf16 partials [B, NH, S, 64] (fp32 tensors holding bf16 values): the G partials
+    of a group are added one after another in bf16, acc = bf16(acc + part), starting from the stored first one (the packed-bf16 atomic
+    adds of positions 1 .. G - 1, stream-ordered); the slabs are summed in fp32 in slab order (dq_reduce_tile).
+    wrong: block_never_added - positions 2 and 3 of every group are missing (the stage bits of G = 2 sent to a library running G = 4);
+    last_partial_slab_dropped - the reduce counts full groups only; block_added_twice - position 1 of every group; slab_of_the_other_head
+    - the reduce reads the LAST slab from the other head."""
+    slabs = []
+    for j in range(0, len(parts), G):
+        grp = parts[j:j + G]
+        if wrong == "block_never_added":
+            grp = grp[:2]
+        acc = grp[0]
+        for part in grp[1:]:
+            acc = _bf(acc + part)
+        if wrong == "block_added_twice" and len(grp) > 1:
+            acc = _bf(acc + grp[1])
+        slabs.append(acc)
+    if wrong == "last_partial_slab_dropped" and len(parts) % G:
+        slabs[-1] = torch.zeros_like(slabs[-1])
+    if wrong == "slab_of_the_other_head":
+        slabs[-1] = slabs[-1].flip(1)
+    return functools.reduce(lambda a, b: a + b, slabs)
+
+
+def emulate(case, keep=None, p_drop=0.0, wrong=None, fused=False, G=2, x=None):
     """A torch fp32 restatement of the kernels' documented arithmetic: fp32 scores of the device's q (exp2 units), p~ = exp2(s - m),
     l = sum p~, bf16(p~ o keep) V / l [/ (1 - p)] stored as bf16; backward p = exp2(s - lse log2 e), delta from the STORED out,
-    dS = p (Z dP - delta) and p o Z rounded to bf16, bf16 stores; fused: one bf16 partial dq per 256-key block, pairs added in bf16.
-    wrong: one of WRONG or (with a keep mask) WRONG_DROP - the same arithmetic with one mistake."""
-    x = inputs(case)
+    dS = p (Z dP - delta) and p o Z rounded to bf16, bf16 stores; fused: one bf16 partial dq per 256-key block, the G of a slab added in bf16.
+    wrong: one of WRONG or (with a keep mask) WRONG_DROP - the same arithmetic with one mistake; fused: or one of WRONG_FUSED_SLABS, at G
+    key blocks per slab (fused_dq_sum).  x: inputs(case) with another dO.  Also returned: dq_acc and dk_acc, the fp32 sums the epilogues
+    rotate, scale (dk_mul for dk) and round (tests/attention_fused_refs.py)."""
+    x = x or inputs(case)
     S = case.S
     qkv = x["qkv_dev"].float()
     qd, k, v = (heads(qkv[:, :, j]) for j in range(3))
@@ -520,15 +605,15 @@ def emulate(case, keep=None, p_drop=0.0, wrong=None, fused=False):
     ds16, dsq16 = _bf(dS), _bf(dS_q)
     if fused:
         parts = [_bf(dsq16[..., j:j + 256] @ k[:, :, j:j + 256]) for j in range(0, Sk, 256)]
-        slabs = [_bf(parts[j] + parts[j + 1]) if j + 1 < len(parts) else parts[j] for j in range(0, len(parts), 2)]
-        dq_acc = functools.reduce(lambda a, b: a + b, slabs)
+        dq_acc = fused_dq_sum(parts, G, wrong)
     else:
         dq_acc = dsq16 @ k
     dq = (dq_acc * SCALE).to(torch.bfloat16)
-    dk = ((ds16.transpose(-1, -2) @ qd) * (LN2 if case.pre else SCALE)).to(torch.bfloat16)[:, :, :S]
+    dk_acc, dk_mul = (ds16.transpose(-1, -2) @ qd)[:, :, :S], (LN2 if case.pre else SCALE)
+    dk = (dk_acc * dk_mul).to(torch.bfloat16)
     pz16 = _bf(p * keepk * zs) if (keepk is not None and wrong != "dv_no_z") else _bf(p)
     dv = (pz16.transpose(-1, -2) @ do).to(torch.bfloat16)[:, :, :S]
-    return dict(out=out, lse=lse, dq=dq, dk=dk, dv=dv, delta=delta[..., 0])
+    return dict(out=out, lse=lse, dq=dq, dk=dk, dv=dv, delta=delta[..., 0], dq_acc=dq_acc, dk_acc=dk_acc, dk_mul=dk_mul)
 
 
 # ================================================================================================ index arithmetic

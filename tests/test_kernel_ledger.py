@@ -20,6 +20,7 @@ MG = "tests/test_model_gpu.py::"
 RK = "tests/test_row_kernels_gpu.py::"
 GK = "tests/test_gemm_kernels_gpu.py::"
 AD = "tests/test_attention_d64_gpu.py::"
+AF = "tests/test_attention_fused_gpu.py::"
 MK = "tests/test_muon_kernels_gpu.py::"
 LH = "tests/test_loss_head_gpu.py::"
 AG = "tests/test_attn_generic_gpu.py::"
@@ -63,7 +64,8 @@ LEDGER = {
                         RK + "test_rope_apply_against_the_float64_rotation"],
     "cm3p_attn_fwd": [KG + "test_attention_global_nopad", KG + "test_attention_random_shapes", KG + "test_attention_sliding_window",
                       AD + "test_matches_float64", AD + "test_exact_conditions", AD + "test_count_probe", AD + "test_window0_copies_v_and_dout",
-                      AD + "test_the_largest_window_is_the_window_s_in_bits"],
+                      AD + "test_the_largest_window_is_the_window_s_in_bits",
+                      AF + "test_matches_float64", AF + "test_count_probe", AF + "test_the_length_rule_picks_four_key_blocks_per_slab"],
     "cm3p_attn_probs": [MG + "test_output_attentions_matches_the_reference_eager_probabilities",
                         AD + "test_probs"],
     "cm3p_attn_bwd": [KG + "test_attention_global_backward_both_implementations", KG + "test_attention_random_shapes",
@@ -84,7 +86,10 @@ LEDGER = {
     "cm3p_rope_apply_generic": [KG + "test_generic_rope_is_the_reference_rotation_and_its_transpose",
                                 RK + "test_rope_apply_against_the_float64_rotation"],
     "cm3p_attn_bwd_fused": [KG + "test_attention_global_backward_both_implementations",
-                            AD + "test_matches_float64"],
+                            AD + "test_matches_float64",
+                            AF + "test_matches_float64", AF + "test_same_bits", AF + "test_one_valid_key_block_moved_along_the_sequence",
+                            AF + "test_rope_epilogues_match_float64", AF + "test_packed_equals_padded_and_matches_float64", AF + "test_count_probe",
+                            AF + "test_the_length_rule_picks_four_key_blocks_per_slab"],
     "cm3p_attn_fwd_dropout": [DR + "test_attention_dropout_matches_fp32_restatement",
                               AD + "test_dropout_at_other_windows",
                               DK + "test_attention_dropout_matches_float64", DK + "test_attention_dropout_with_a_top_bit_seed_and_another_layer"],
@@ -144,9 +149,9 @@ LEDGER = {
     "cm3p_pointwise_loss": [CH + "test_pointwise_loss_against_float64"],
     "cm3p_first_zero_index": [KG + "test_head_kernels", LH + "test_first_zero_index_is_the_argmax_of_the_zero_mask"],
     "cm3p_attn_fwd_varlen": [KG + "test_attention_varlen_equals_padded_on_valid_rows",
-                             AD + "test_varlen_equals_padded"],
+                             AD + "test_varlen_equals_padded", AF + "test_packed_equals_padded_and_matches_float64"],
     "cm3p_attn_bwd_varlen": [KG + "test_attention_varlen_equals_padded_on_valid_rows",
-                             AD + "test_varlen_equals_padded"],
+                             AD + "test_varlen_equals_padded", AF + "test_packed_equals_padded_and_matches_float64"],
     "cm3p_gather_rows_f32": [KG + "test_gather_scatter_rows",
                              RK + "test_gather_and_scatter_rows_bit_for_bit"],
     "cm3p_scatter_rows_f32": [KG + "test_gather_scatter_rows",

@@ -797,7 +797,7 @@ def test_pipelined_global_forward_agrees_with_the_three_wave_kernel(K, S, lens, 
 
 @pytest.mark.parametrize("nkb,lens", [(1, None), (2, [512 - 17, 300]), (3, None), (5, [1280 - 100, 1025, 300])])
 def test_fused_backward_with_four_key_blocks_per_slab_at_short_sequences(K, monkeypatch, nkb, lens):
-    """CM3P_FUSED_SLAB_GROUP=4 (the rule only picks it from 24 key blocks = S > 5888 on, which no kernel test reaches): partial groups,
+    """CM3P_FUSED_SLAB_GROUP=4 (the rule only picks it from 24 key blocks = S > 5888 on: tests/test_attention_fused_gpu.py runs S = 5900 and holds G = 4 to float64): partial groups,
     a single key block, padded rows - against the fp32 reference and against the group size 2 the same call picks by itself."""
     S = 256 * nkb - (17 if lens is None else 0)
     if lens is not None:
